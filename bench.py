@@ -22,6 +22,8 @@ all_gather of the observation rows, as the north star prescribes.
 Also reported: the roofline of the physics kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s), VALU issue rate
 (from the committed PMC pass), throughput at small action scales, and -- on rank 0 at N = 1 -- the fp64 oracle timed on the
 host cores as a CPU baseline ("port") together with the 1 000-substep drift of the HIP path against that same oracle run.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as .npy files: the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -37,6 +40,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2   # wave-instructions/s: 1 024 SIMD-32 units, one wave64 VALU instruction per 2 cycles, 2.4 GHz
 PMC_FILE = os.path.join(ROOT, "profiles", "r05_pmc.json")
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload
 
 
 def parse_args(argv=None):
@@ -70,7 +74,33 @@ def parse_args(argv=None):
     ap.add_argument("--set-option", action="append", default=[], help="name=value passed to jaco_set_option (e.g. compensated=0); repeatable")
     ap.add_argument("--dry-gather", action="store_true",
                     help="CPU rehearsal of the N > 1 plumbing (spawn, rendezvous, gather, max-over-ranks timing) on gloo: no GPU, no physics")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (env level: obs, reward, done; ctrl level: qpos, qvel, "
+                         "qacc) as DIR/<name>.npy in float32, rank 0's envs only; above %d MB in all, a fixed seeded sample of env rows "
+                         "(row numbers in DIR/env_index.npy)" % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """`arrays`: {name: tensor with one row per env}, written as float32 .npy files; a seeded sample of the rows when all of them would
+    exceed DUMP_MAX_BYTES, so that runs with the same arguments write the same rows."""
+    import numpy as np
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * (t[0].numel() if t.dim() > 1 else 1) for t in arrays.values())
+    budget = DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)   # (room for the .npy headers)
+    idx = None
+    if n * row_bytes > budget:
+        k = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
+    if idx is not None:
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
 
 
 def self_launch(args):
@@ -339,13 +369,12 @@ def env_level_drift(args):
     try:
         import numpy as np
         import env_drift
-        path = os.path.join(ROOT, "gpurun_out", "bench_env_drift_gpu_%d.npz" % os.getpid())
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--env-drift-gpu-leg", path], timeout=600, check=True, stdout=subprocess.DEVNULL)
-        t = time.time()
-        ref = env_drift.oracle_leg(ENV_DRIFT_ENVS, ENV_DRIFT_STEPS)
-        res = env_drift.summarize(dict(np.load(path)), ref)
-        os.remove(path)
+        with tempfile.TemporaryDirectory(prefix="jaco_bench_") as td:   # (not under ROOT: the checkout may be read-only)
+            path = os.path.join(td, "env_drift_gpu.npz")
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--env-drift-gpu-leg", path], timeout=600, check=True, stdout=subprocess.DEVNULL)
+            t = time.time()
+            ref = env_drift.oracle_leg(ENV_DRIFT_ENVS, ENV_DRIFT_STEPS)
+            res = env_drift.summarize(dict(np.load(path)), ref)
         res["metric"] = "max-abs qpos error of the HIP env vs the fp64 oracle env, same actions + injected noise, env level (OSC every substep), frame_skip 50"
         res["oracle"] = ORACLE_STATUS
         res["oracle_seconds"] = time.time() - t
@@ -405,13 +434,13 @@ def main():
     small = small_action_runs(args) if (args.level == "env" and world == 1 and args.extra_scales) else {}
     pol_leg = policy_run(args) if (args.level == "env" and world == 1) else None
     cfg_legs = config_legs(args) if (world == 1 and args.config_legs) else {}
-    drift_npz = None
+    drift_npz, drift_dir = None, None
     env_drift_res = None
     if world == 1 and not args.no_cpu_baseline and args.level == "env":
         env_drift_res = env_level_drift(args)
     if world == 1 and not args.no_cpu_baseline:   # the HIP leg of the drift metric, in a child process before this one touches the GPU
-        drift_npz = os.path.join(ROOT, "gpurun_out", "bench_drift_gpu_%d.npz" % os.getpid())
-        os.makedirs(os.path.dirname(drift_npz), exist_ok=True)
+        drift_dir = tempfile.TemporaryDirectory(prefix="jaco_bench_")   # (not under ROOT: the checkout may be read-only)
+        drift_npz = os.path.join(drift_dir.name, "drift_gpu.npz")
         try:
             subprocess.run([sys.executable, os.path.abspath(__file__), "--drift-gpu-leg", drift_npz, "--model", args.model], timeout=600, check=True,
                            stdout=subprocess.DEVNULL)
@@ -456,7 +485,7 @@ def main():
 
         abuf = torch.empty(B, nact, device=dev)
         done_each = torch.zeros(B, dtype=torch.int32, device=dev)
-        pol, cur_obs = None, [None]
+        pol, cur_obs, last = None, [None], {}
         if args.policy:
             from mujoco_jaco_amd.policy import HPCPolicy
             path = args.policy if os.path.exists(args.policy) else os.path.join(ROOT, "tests", "golden", "policy_%s.npz" % args.policy)
@@ -474,6 +503,7 @@ def main():
                 o = genv.reset(d)  # masked jaco_reset of the finished envs: no host sync; their obs rows become the new episode's first
             # (default: option auto_reset -- the same reset, done inside jaco_step by the wave that finished the episode)
             cur_obs[0] = o
+            last.update(obs=o, reward=r, done=d)   # (references to the handle's output buffers: --dump-outputs)
             if world > 1:          # one collective per rollout step: concatenate the observation rows of all shards (issued on a
                 gather.start(o)    # side stream: it overlaps the next step's launch set; the timed region ends on a full device sync)
     else:
@@ -543,6 +573,8 @@ def main():
     step_ms = env.step_time_ms()
     kern_ms, launches = env.kernel_time_ms()
     env.enable_timing(False)
+    if args.dump_outputs and rank == 0:   # what the last timed step handed its caller, before the flag census below steps on
+        dump_outputs(args.dump_outputs, last if args.level == "env" else dict(zip(("qpos", "qvel", "qacc"), env.get_state())))
     if args.level == "env":
         done_count.add_(done_each.sum())
     done_fraction = float(done_count.item()) / (B * args.steps)
@@ -627,9 +659,9 @@ def main():
             out["cpu_baseline"], out["drift"] = cpu_baseline_and_drift(args.model, fs, drift_npz)
             if out["drift"] is not None:
                 out["drift"]["env_level_closed_loop"] = env_drift_res
-            if drift_npz and os.path.exists(drift_npz):
-                os.remove(drift_npz)
         print(json.dumps(out))
+    if drift_dir is not None:
+        drift_dir.cleanup()
     env.close()
     if world > 1:
         dist.destroy_process_group()

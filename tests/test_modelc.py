@@ -6,7 +6,7 @@ import pytest
 
 from mujoco_jaco_amd.modelc import mjcf
 
-REF_ASSETS = "/root/reference/env_script/assets/jaco2"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_numeric_attributes_are_read_like_mujoco_reads_them():
@@ -22,13 +22,14 @@ def test_numeric_attributes_are_read_like_mujoco_reads_them():
     assert np.array_equal(mjcf._floats(".3", n=3, default=(1, 2, 3)), [0.3, 2, 3])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reads the reference's model data (build container only)")
-def test_sibling_mjcfs_parse():
-    """jaco2_torque.xml (12 hinge joints incl. the sprung distal finger joints, :109-133) and the old curtain model parse now; the
-    default model and the arm-only model keep the sizes SURVEY.md section 8a lists."""
+def test_sibling_models_keep_their_sizes():
+    """The compiled sibling models (mujoco_jaco_amd/assets/*.jacomdl, what modelc/compile.py made of the reference's MJCF files, which
+    are not part of this repository): jaco2_torque (12 hinge joints incl. the sprung distal finger joints, xml:109-133) and the old
+    curtain model are there; the default model and the arm-only model keep the sizes SURVEY.md section 8a lists."""
+    from mujoco_jaco_amd.modelc import blob
     sizes = {}
-    for name in ("jaco2_curtain_torque", "jaco2_reaching_torque", "jaco2_torque", "jaco2_curtain_torque_old", "jaco2_sensor_torque"):
-        M, names = mjcf.parse(os.path.join(REF_ASSETS, name + ".xml"), timestep=0.001)
+    for name in ("jaco2_curtain_torque", "jaco2_reaching_torque", "jaco2_torque", "jaco2_curtain_torque_old", "jaco2_curtain_torque_sensor"):
+        M = blob.load(os.path.join(ROOT, "mujoco_jaco_amd", "assets", name + ".jacomdl"))
         sizes[name] = (int(M["nq"][0]), int(M["nv"][0]), int(M["nu"][0]), int(M["njnt"][0]))
     assert sizes["jaco2_curtain_torque"] == (23, 21, 9, 11) and sizes["jaco2_reaching_torque"] == (9, 9, 9, 9)
     assert sizes["jaco2_torque"] == (12, 12, 9, 12) and sizes["jaco2_curtain_torque_old"][3] == 13
