@@ -173,6 +173,27 @@ int jaco_get_markers(JacoHandle* h, float* out_dev, void* stream);
 int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream);
 int jaco_set_frame_skip(JacoHandle* h, int frame_skip);
 
+/* ---- robot-configuration queries: MujocoConfig.J / M / g / R / quaternion / Tx (mujoco_config.py:201-447) and Mujoco.get_xyz /
+ * get_orientation (mujoco.py:148-215), batched.  The values are those of a sim.forward() on the given state: body poses, the
+ * Jacobians at the requested points, the dense mass matrix and qfrc_bias.  (The reference's controller, with use_sim_state=True,
+ * reads them one substep stale -- SURVEY 3.1; a caller who wants that lag keeps the previous substep's query result.)
+ * A frame: `body` = fused body index (-1 = world-fixed), pose (pos, row-major mat) in that body's frame, Jacobian reference `point` in
+ * the frame's own coordinates (mujoco_jaco_amd/robot_config.py builds frames from MJCF body names; the body's COM gives mj_jacBodyCom).
+ * Outputs (device pointers, fp32, row-major per env; NULL = not wanted, its work is skipped where that is cheap):
+ *   xpos [num_envs][nframes][3], xmat [num_envs][nframes][9]  -- frame position and rotation (MuJoCo's xmat layout);
+ *   jac [num_envs][nframes][6][nv]  -- rows 0-2 translational, 3-5 rotational Jacobian at the frame's point; a column is zero for a dof
+ *        that does not move the frame's body (mj_jacBodyCom / mj_jac);
+ *   qM [num_envs][nv][nv]  -- dense, symmetric (mj_fullM);   qfrc_bias [num_envs][nv]  -- Coriolis, centrifugal and gravity forces.
+ * State: qpos_dev [num_envs][nq] / qvel_dev [num_envs][nv] override the handle's state (NULL = its current state, the fp32 words
+ * jaco_get_state returns).  Nothing of the handle is written: state, task rows, flags and sensordata stay as they are.
+ * Asynchronous on `stream`: no allocation, no synchronisation, no host copy (the frames travel in the kernel arguments).
+ * JACO_EINVAL when nframes is outside [0, JACO_QUERY_MAX_FRAMES] or a frame's body outside [-1, number of fused bodies). */
+#define JACO_QUERY_MAX_FRAMES 16
+typedef struct JacoFrame { int body; float pos[3]; float mat[9]; float point[3]; } JacoFrame;
+typedef struct JacoQueryOut { float* xpos; float* xmat; float* jac; float* qM; float* qfrc_bias; } JacoQueryOut;
+int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nframes, const float* qpos_dev, const float* qvel_dev,
+               const JacoQueryOut* out, void* stream);
+
 /* Solver / collision options, MuJoCo <option> names: "iterations", "tolerance", "ls_iterations",
  * "disable_contact" (contact flag), "mpr_iterations", "mpr_tolerance", "mpr_output"; "compensated" (1 default, see jaco_set_state).
  * "auto_reset" (0 default): jaco_step resets an env whose step ended its episode inside the same call -- sim.reset(), the draws of _reset

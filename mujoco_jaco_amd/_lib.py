@@ -11,6 +11,18 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("JACO_ENV_LIB", "libjaco_env.so"))
 ASSETS = os.path.join(_HERE, "assets")
 
 
+JACO_QUERY_MAX_FRAMES = 16
+
+
+class JacoFrame(ctypes.Structure):
+    """JacoFrame of include/jaco_env.h: fused body (-1 world), pose in that body's frame, Jacobian reference point in the frame."""
+    _fields_ = [("body", ctypes.c_int), ("pos", ctypes.c_float * 3), ("mat", ctypes.c_float * 9), ("point", ctypes.c_float * 3)]
+
+
+class JacoQueryOut(ctypes.Structure):
+    _fields_ = [("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("jac", ctypes.c_void_p), ("qM", ctypes.c_void_p), ("qfrc_bias", ctypes.c_void_p)]
+
+
 class JacoConfig(ctypes.Structure):
     _fields_ = [("model_blob", ctypes.c_void_p), ("model_blob_size", ctypes.c_size_t), ("num_envs", ctypes.c_int),
                 ("device", ctypes.c_int), ("frame_skip", ctypes.c_int), ("task", ctypes.c_int), ("seed", ctypes.c_uint64)]
@@ -60,6 +72,7 @@ SYMBOLS = {
     "jaco_enable_timing": (_ci, [_vp, _ci]),
     "jaco_step_time_ms": (_ci, [_vp, ctypes.POINTER(_cd)]),
     "jaco_stage_profile": (_ci, [_vp, ctypes.POINTER(ctypes.c_uint64), _ci]),
+    "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
 }
 
 _libs = {}

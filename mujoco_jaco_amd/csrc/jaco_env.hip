@@ -927,3 +927,36 @@ extern "C" int jaco_step_time_ms(JacoHandle* h, double* avg_ms) {
   HIPCHK(h, hipDeviceSynchronize());
   return event_mean(h, h->events, avg_ms);
 }
+
+// ---- robot-configuration queries (query.h): one wavefront per env, nothing of the handle written --------------------------------
+static_assert(sizeof(JacoFrame) == sizeof(JacoQueryFrame) && offsetof(JacoFrame, pos) == offsetof(JacoQueryFrame, pos) &&
+                  offsetof(JacoFrame, mat) == offsetof(JacoQueryFrame, mat) && offsetof(JacoFrame, point) == offsetof(JacoQueryFrame, point) &&
+                  JACO_QUERY_MAX_FRAMES == JQ_MAXFRAMES, "JacoFrame of the public header and the kernel's frame record must agree");
+extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nframes, const float* qpos_dev, const float* qvel_dev,
+                          const JacoQueryOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  if (nframes < 0 || nframes > JACO_QUERY_MAX_FRAMES || (nframes > 0 && !frames_host)) {
+    h->err = "jaco_query: nframes " + std::to_string(nframes) + " outside [0, " + std::to_string(JACO_QUERY_MAX_FRAMES) + "]";
+    return JACO_EINVAL;
+  }
+  JacoQueryArgs Q{};
+  for (int f = 0; f < nframes; f++) {
+    if (frames_host[f].body < -1 || frames_host[f].body >= h->model_host.nbody) {
+      h->err = "jaco_query: frame " + std::to_string(f) + ": body " + std::to_string(frames_host[f].body) + " outside [-1, " +
+               std::to_string(h->model_host.nbody) + ")";
+      return JACO_EINVAL;
+    }
+    memcpy(&Q.fr[f], &frames_host[f], sizeof(JacoFrame));
+  }
+  ENTER(h);
+  Q.model = h->model_dev;
+  Q.qpos = qpos_dev ? qpos_dev : h->qpos;
+  Q.qvel = qvel_dev ? qvel_dev : h->qvel;
+  if (out) { Q.xpos = out->xpos; Q.xmat = out->xmat; Q.jac = out->jac; Q.qM = out->qM; Q.bias = out->qfrc_bias; }
+  Q.nenv = h->num_envs;
+  Q.nframes = nframes;
+  jaco_launch_query((unsigned)h->num_envs, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

@@ -2732,3 +2732,6 @@ JACO_DEFINE_LAUNCHER(7, jaco_physics_kernel_huge_drain)
 JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #endif
 #endif
+
+// the robot-configuration query kernel (jaco_query): translation unit 9
+#include "query.h"

@@ -114,6 +114,15 @@ class JacoBatchedEnv:
         self._amin = torch.tensor(self.act_min, dtype=torch.float32, device=self.device)
         self._amax = torch.tensor(self.act_max, dtype=torch.float32, device=self.device)
 
+    @property
+    def robot_config(self):
+        """robot_config.BatchedMujocoConfig of this env's sim (MujocoConfig: J, M, g, R, quaternion, Tx), created on first use; arm =
+        the chain of "EE" (two arms: of "EE_1"; pass full=True for every dof).  Sim tier only, so it works with n_robots=2 as well."""
+        if getattr(self, "_robot_config", None) is None:
+            from .robot_config import BatchedMujocoConfig
+            self._robot_config = BatchedMujocoConfig(self.sim, ee="EE" if self.n_robots == 1 else "EE_1")
+        return self._robot_config
+
     # ---- helpers
     def _p(self, t):
         return ctypes.c_void_p(t.data_ptr())
@@ -141,6 +150,7 @@ class JacoBatchedEnv:
                                       "set_state); the reference's env loop (env_mujoco_util.py:73-83) drives one arm")
 
     def reset(self, mask=None):
+        self.sim.state_version += 1
         self._env_tier()
         self.current_steps = 0
         m = self._mask(mask)
@@ -159,11 +169,13 @@ class JacoBatchedEnv:
         self.sim._chk(self.L.jaco_set_markers(self.h, self._p(t), self.sim._stream()))
 
     def _placing_hold(self, mask=None, nsub=150):
+        self.sim.state_version += 1
         """The held part of the placing reset on its own (env_mujoco_util.py:106-117); reset() runs it for task 'placing'."""
         m = self._mask(mask)
         self.sim._chk(self.L.jaco_placing_hold(self.h, self._p(m) if m is not None else None, int(nsub), self.sim._stream()))
 
     def _grasping_prereach(self, mask=None, max_substeps=4000):
+        self.sim.state_version += 1
         """The pre-reach loops of the grasping reset on their own (env_mujoco_util.py:123-170); reset() runs them for task 'grasping'."""
         m = self._mask(mask)
         self.sim._chk(self.L.jaco_grasping_prereach(self.h, self._p(m) if m is not None else None, int(max_substeps), self._p(self._obs), self.sim._stream()))
@@ -218,6 +230,7 @@ class JacoBatchedEnv:
         self.sim._chk(self.L.jaco_set_subgoal(self.h, self._p(sg)))
 
     def step(self, action, weight=None, subgoal=None, id=None):
+        self.sim.state_version += 1
         """env_mujoco.py:116-139.  With num_envs > 1 the returned obs / reward / done tensors are the handle's own output buffers (done: a
         bool view of the kernel's byte flags): valid until the next step() / reset() call, `.clone()` what has to outlive it."""
         self._env_tier()
@@ -241,6 +254,7 @@ class JacoBatchedEnv:
         return t
 
     def set_task_state(self, t):
+        self.sim.state_version += 1
         t = t.to(self.device, torch.float32).contiguous()
         self.sim._chk(self.L.jaco_set_task_state(self.h, self._p(t), self.sim._stream()))
 

@@ -146,8 +146,7 @@ def fuse(M, names, pairs):
 
     def rel(b, w):
         """pose of body b in the frame of its weld root w (constant: no joints in between)."""
-        qw = rot.quat_conj(xquat[w])
-        return rot.rot_vec(qw, xpos[b] - xpos[w]), rot.quat_normalize(rot.quat_mul(qw, xquat[b]))
+        return kin.rel_pose(xpos, xquat, b, w)
 
     F = {}
     fparent, fpos, fquat, faxis, fjpos, fq0, fmass, fcom, finert = [], [], [], [], [], [], [], [], []

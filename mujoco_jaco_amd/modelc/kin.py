@@ -52,6 +52,13 @@ def fk(M, qpos, mocap_pos=None, mocap_quat=None):
     return xpos, xquat, xanchor, xaxis
 
 
+def rel_pose(xpos, xquat, b, w):
+    """Pose (position, unit quaternion) of body b in the frame of body w, from world poses: constant when b is welded to w (no joint
+    in between).  The model compiler fuses weld groups with it (compile.fuse); robot_config builds its body frames with it."""
+    qw = rot.quat_conj(xquat[w])
+    return rot.rot_vec(qw, xpos[b] - xpos[w]), rot.quat_normalize(rot.quat_mul(qw, xquat[b]))
+
+
 def jac_point(M, xpos, xquat, xanchor, xaxis, body, point):
     """3 x nv translational and rotational Jacobians of a world point moving with `body`."""
     nv = int(M["nv"][0])

@@ -1,7 +1,7 @@
 """Ctrl-level batched physics: the `Mujoco` sim-interface tier of the reference, batched.
 
-Mirrors /root/reference/env_script/mujoco.py (send_forces :258-278, set_joint_state :332-347,
-get_feedback :349-359, get/set state :213-246) for `num_envs` environments resident on one MI355X.
+Mirrors /root/reference/env_script/mujoco.py (send_forces :258-278, get_feedback :349-359, get/set state :213-246,
+get_xyz / get_orientation :148-210, get_obj_vel :212-215) for `num_envs` environments resident on one MI355X.
 PyTorch is used only to own device buffers and streams; every computation is in libjaco_env.so.
 """
 import ctypes
@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .robot_config import FrameTable
 
 
 class JacoError(RuntimeError):
@@ -34,6 +35,11 @@ class BatchedMujoco:
         self._chk(self.L.jaco_dims(self.h, *[ctypes.byref(d) for d in dims]))
         self.nq, self.nv, self.nu, self.nsensor, self.nobs, self.nact = [d.value for d in dims]
         self.num_envs = int(num_envs)
+        self.robot_file = robot_file
+        self.frames = FrameTable.for_model(robot_file)   # MJCF body name -> kernel frame (robot_config.py)
+        # bumped by every call that changes the state (and by JacoBatchedEnv's reset / step / state setters): cached query results
+        # (BatchedMujocoConfig) are valid while it stands still
+        self.state_version = 0
 
     def _chk(self, rc):
         if rc != 0:
@@ -62,6 +68,7 @@ class BatchedMujoco:
 
     # ---- state (sim.get_state / set_state)
     def set_state(self, qpos=None, qvel=None, qacc_warmstart=None):
+        self.state_version += 1
         self._chk(self.L.jaco_set_state(self.h, self._dev(qpos, self.nq), self._dev(qvel, self.nv),
                                         self._dev(qacc_warmstart, self.nv), self._stream()))
 
@@ -77,19 +84,66 @@ class BatchedMujoco:
         return self.get_state()
 
     def reset_state(self):
+        self.state_version += 1
         self._chk(self.L.jaco_reset_state(self.h, self._stream()))
 
     # ---- send_forces
     def send_forces(self, ctrl, nsub=1):
+        self.state_version += 1
         self._chk(self.L.jaco_physics_step(self.h, self._dev(ctrl, self.nu), int(nsub), self._stream()))
 
     def send_forces_debug(self, ctrl, env, nsub=1):
         n = self.L.jaco_debug_dump_floats()
         out = np.zeros(n, np.float32)
         torch.cuda.synchronize()
+        self.state_version += 1
         self._chk(self.L.jaco_physics_step_debug(self.h, self._dev(ctrl, self.nu), int(nsub), int(env),
                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n))
         return out
+
+    # ---- robot-configuration queries (jaco_query; MujocoConfig: robot_config.BatchedMujocoConfig)
+    def query(self, frames, qpos=None, qvel=None, xpos=True, xmat=True, jac=True, qM=True, qfrc_bias=True):
+        """One query launch on the current stream: {"xpos": [B, nf, 3], "xmat": [B, nf, 9], "jac": [B, nf, 6, nv], "qM": [B, nv, nv],
+        "qfrc_bias": [B, nv]} (the outputs asked for) of the frames (_lib.JacoFrame list, FrameTable.jaco_frame) at the current state or at
+        the given qpos [B, nq] / qvel [B, nv].  The values of a sim.forward() on that state; the handle's state is not touched."""
+        nf, B, dev = len(frames), self.num_envs, self.device
+        want = {"xpos": (xpos, (B, nf, 3)), "xmat": (xmat, (B, nf, 9)), "jac": (jac, (B, nf, 6, self.nv)), "qM": (qM, (B, self.nv, self.nv)),
+                "qfrc_bias": (qfrc_bias, (B, self.nv))}
+        res = {k: torch.empty(shape, device=dev) for k, (on, shape) in want.items() if on}
+        ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
+        out = _lib.JacoQueryOut(ptr("xpos"), ptr("xmat"), ptr("jac"), ptr("qM"), ptr("qfrc_bias"))
+        arr = (_lib.JacoFrame * max(nf, 1))(*frames)
+        self._chk(self.L.jaco_query(self.h, ctypes.cast(arr, ctypes.c_void_p), nf, self._dev(qpos, self.nq), self._dev(qvel, self.nv),
+                                    ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        return res
+
+    def get_xyz(self, name):
+        """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
+        return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]
+
+    def get_orientation(self, name):
+        """[num_envs, 4] orientation of an MJCF body as a unit quaternion, w first (sim.data.get_body_xquat, mujoco.py:172-210)."""
+        from .robot_config import mat2quat
+        return mat2quat(self.query([self.frames.jaco_frame(name)], xpos=False, jac=False, qM=False, qfrc_bias=False)["xmat"][:, 0])
+
+    def get_obj_vel(self):
+        """[num_envs, 3] linear velocity of the object (qvel[9:12], what the step kernel's terminal test reads; mujoco.py:212-215)."""
+        return self.get_state()[1][:, 9:12]
+
+    def get_feedback(self, ee=None):
+        """{"q": [num_envs, n_arm], "dq": [num_envs, n_arm]}: joint angles and velocities of the arm dofs (the hinge joints on the
+        kinematic chain of `ee`; default "EE", on the two-arm model both arms' chains) -- mujoco.py:349-359."""
+        if ee is None:
+            ee = ["EE"] if "EE" in self.frames.bodies else [n for n in ("EE_1", "EE_2") if n in self.frames.bodies]
+        elif isinstance(ee, str):
+            ee = [ee]
+        qadr, dadr = [], []
+        for n in ee:
+            a, d = self.frames.chain(n)
+            qadr += a
+            dadr += d
+        qpos, qvel, _ = self.get_state()
+        return {"q": qpos[:, qadr], "dq": qvel[:, dadr]}
 
     def sensordata(self):
         out = torch.empty(self.num_envs, self.nsensor, device=self.device)

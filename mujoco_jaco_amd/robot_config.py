@@ -1,0 +1,198 @@
+"""Robot-configuration queries: the `MujocoConfig` half of the reference, batched.
+
+Mirrors /root/reference/env_script/mujoco_config.py:201-447 (J, M, g, R, quaternion, Tx) and the body-pose getters of mujoco.py:148-215
+for `num_envs` environments.  Every number comes from one jaco_query launch (include/jaco_env.h; kernel mujoco_jaco_amd/csrc/query.h):
+the values of a sim.forward() on the current (or a given) state.
+
+FrameTable maps MJCF body names (assets/<model>.names.txt) to the frames the kernel takes: a body welded to a moving body becomes that
+weld root's fused index plus its constant pose in the root's frame (the pose compile.fuse uses, modelc.kin.rel_pose); a body welded to
+the world becomes a world-fixed frame.  The default Jacobian reference point is the body's own centre of mass (body_ipos): mj_jacBodyCom.
+"""
+import numpy as np
+
+from . import _lib
+from .modelc import blob as blobmod
+from .modelc import kin
+
+
+def read_names(path):
+    """{kind: [name or None]} of a shipped assets/<model>.names.txt (MJCF order; "-" = unnamed)."""
+    out = {}
+    for line in open(path):
+        if ":" in line:
+            k, v = line.split(":", 1)
+            out[k.strip()] = [None if n == "-" else n for n in v.split()]
+    return out
+
+
+def quat2mat32(q):
+    """Row-major fp32 rotation of a unit quaternion, rounded exactly as the library's model loader rounds its frames (model_blob.cpp)."""
+    w, x, y, z = (float(c) for c in q)
+    return np.array([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], np.float64).astype(np.float32)
+
+
+class FrameTable:
+    """MJCF body name -> kernel frame (fused body, pose in it), built from the model blob and its names file."""
+
+    def __init__(self, M, names):
+        self.M, self.names = M, names
+        self.bodies = names["body"]
+        nbody = int(M["nbody"][0])
+        self.weld = M["body_weldid"]
+        self.xpos0, self.xquat0, _, _ = kin.fk(M, M["qpos0"])
+        self.fid = {0: -1}
+        for i, r in enumerate([b for b in range(1, nbody) if self.weld[b] == b]):
+            self.fid[r] = i
+
+    @classmethod
+    def for_model(cls, robot_file):
+        path = _lib.model_path(robot_file)
+        return cls(blobmod.load(path), read_names(path[:-len(".jacomdl")] + ".names.txt"))
+
+    def body_id(self, name):
+        if name not in self.bodies:
+            raise ValueError("unknown body %r: the model's bodies are %s" % (name, [n for n in self.bodies if n]))
+        b = self.bodies.index(name)
+        if self.M["body_mocapid"][b] >= 0:
+            raise ValueError("body %r is a mocap body (a task-layer marker): its pose is not a function of the state; read it with env.markers()" % name)
+        return b
+
+    def frame(self, name):
+        """(fused body or -1, position, unit quaternion) of the body in that fused body's frame (fp64), as compile.fuse computes it."""
+        b = self.body_id(name)
+        w = self.weld[b]
+        if w == 0:
+            return -1, np.array(self.xpos0[b], np.float64), np.array(self.xquat0[b], np.float64)
+        p, q = kin.rel_pose(self.xpos0, self.xquat0, b, w)
+        return self.fid[w], np.asarray(p, np.float64), np.asarray(q, np.float64)
+
+    def com(self, name):
+        """The body's centre of mass in its own frame (body_ipos): mj_jacBodyCom's point."""
+        return np.asarray(self.M["body_ipos"].reshape(-1, 3)[self.body_id(name)], np.float64)
+
+    def jaco_frame(self, name, point=None):
+        """The kernel's frame record (_lib.JacoFrame) of a body; point: Jacobian reference point in the body's frame (default: its COM)."""
+        fb, p, q = self.frame(name)
+        f = _lib.JacoFrame()
+        f.body = fb
+        f.pos[:] = [float(v) for v in np.asarray(p, np.float64).astype(np.float32)]
+        f.mat[:] = [float(v) for v in quat2mat32(q)]
+        f.point[:] = [float(v) for v in np.asarray(self.com(name) if point is None else point, np.float64).astype(np.float32)]
+        return f
+
+    def chain(self, name):
+        """(qpos addresses, dof addresses) of the joints on the kinematic chain from the world to body `name`, root first
+        (get_joints_in_ee_kinematic_tree, mujoco.py:115-146).  Hinge joints only: they are what `q` can be spliced into."""
+        b = self.body_id(name)
+        joints = []
+        while b > 0:
+            ja, jn = int(self.M["body_jntadr"][b]), int(self.M["body_jntnum"][b])
+            joints = list(range(ja, ja + jn)) + joints
+            b = int(self.M["body_parentid"][b])
+        for j in joints:
+            if self.M["jnt_type"][j] != kin.JNT_HINGE:
+                raise ValueError("body %r hangs from a free joint: it has no arm chain of hinge joints" % name)
+        return [int(self.M["jnt_qposadr"][j]) for j in joints], [int(self.M["jnt_dofadr"][j]) for j in joints]
+
+
+def mat2quat(R):
+    """[..., 9] row-major rotations -> [..., 4] unit quaternions, w first, w >= 0 (mju_mat2Quat's branches)."""
+    import torch
+    m = R.reshape(*R.shape[:-1], 3, 3)
+    m00, m01, m02 = m[..., 0, 0], m[..., 0, 1], m[..., 0, 2]
+    m10, m11, m12 = m[..., 1, 0], m[..., 1, 1], m[..., 1, 2]
+    m20, m21, m22 = m[..., 2, 0], m[..., 2, 1], m[..., 2, 2]
+    tr = m00 + m11 + m22
+    c0 = torch.stack([1 + tr, m21 - m12, m02 - m20, m10 - m01], -1)
+    c1 = torch.stack([m21 - m12, 1 + m00 - m11 - m22, m01 + m10, m02 + m20], -1)
+    c2 = torch.stack([m02 - m20, m01 + m10, 1 - m00 + m11 - m22, m12 + m21], -1)
+    c3 = torch.stack([m10 - m01, m02 + m20, m12 + m21, 1 - m00 - m11 + m22], -1)
+    pick = torch.stack([tr, m00, m11, m22], -1).argmax(-1)
+    q = torch.where((pick == 0)[..., None], c0, torch.where((pick == 1)[..., None], c1, torch.where((pick == 2)[..., None], c2, c3)))
+    q = q / q.norm(dim=-1, keepdim=True)
+    return torch.where(q[..., :1] < 0, -q, q)
+
+
+class BatchedMujocoConfig:
+    """MujocoConfig (mujoco_config.py:201-447) over a BatchedMujoco: J, M, g, R, quaternion, Tx for every env at once.
+
+    `arm` = the dofs of the hinge joints on the kinematic chain of `ee` (get_joints_in_ee_kinematic_tree, mujoco.py:115-146): dofs 0-5 on
+    the single-arm models, one arm's six on the two-arm model (ee = "EE_1" / "EE_2").  Accessors return [num_envs, ...] tensors on the
+    sim's device restricted to the arm (full=True: all nv dofs).  q: [num_envs, n_arm] joint angles spliced into the current qpos (the
+    current qvel stays); q=None: the current state.  One query launch fills every output for the registered frames (at most 16 body
+    names, registered on first use); accessors reuse that result until the sim's state changes (BatchedMujoco.state_version).
+    """
+
+    def __init__(self, sim, ee="EE"):
+        self.sim = sim
+        self.table = sim.frames
+        self.ee = ee
+        self.arm_qadr, self.arm = self.table.chain(ee)
+        self.n_arm = len(self.arm)
+        self._names, self._frames = [], []
+        self._cache, self._cache_key = None, None
+        self._register(ee)
+
+    def _register(self, name):
+        if name in self._names:
+            return self._names.index(name)
+        if len(self._names) >= _lib.JACO_QUERY_MAX_FRAMES:
+            raise ValueError("at most %d frames per BatchedMujocoConfig (registered: %s)" % (_lib.JACO_QUERY_MAX_FRAMES, self._names))
+        f = self.table.jaco_frame(name)   # (raises ValueError for unknown and mocap bodies)
+        self._names.append(name)
+        self._frames.append(f)
+        self._cache = None
+        return len(self._names) - 1
+
+    def _result(self, q):
+        if q is None:
+            key = self.sim.state_version
+            if self._cache is None or self._cache_key != key:
+                self._cache = self.sim.query(self._frames)
+                self._cache_key = key
+            return self._cache
+        import torch
+        qpos = self.sim.get_state()[0]
+        q = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], self.n_arm)
+        qpos[:, self.arm_qadr] = q
+        return self.sim.query(self._frames, qpos=qpos.contiguous())
+
+    def _cols(self, t, full):
+        return t if full else t[..., self.arm]
+
+    def J(self, name, q=None, full=False):
+        """[num_envs, 6, n_arm]: translational rows 0-2, rotational rows 3-5 at the body's COM (mj_jacBodyCom)."""
+        i = self._register(name)
+        return self._cols(self._result(q)["jac"][:, i], full)
+
+    def M(self, q=None, full=False):
+        """[num_envs, n_arm, n_arm] joint-space inertia (mj_fullM)."""
+        qM = self._result(q)["qM"]
+        return qM if full else qM[:, self.arm][:, :, self.arm]
+
+    def g(self, q=None, full=False):
+        """[num_envs, n_arm]: -qfrc_bias (gravity, Coriolis and centrifugal forces at the current qvel)."""
+        return -self._cols(self._result(q)["qfrc_bias"], full)
+
+    def R(self, name, q=None):
+        """[num_envs, 3, 3] body rotation (xmat)."""
+        i = self._register(name)
+        return self._result(q)["xmat"][:, i].reshape(-1, 3, 3)
+
+    def quaternion(self, name, q=None):
+        """[num_envs, 4] body orientation, w first."""
+        i = self._register(name)
+        return mat2quat(self._result(q)["xmat"][:, i])
+
+    def Tx(self, name, q=None, x=None):
+        """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
+        i = self._register(name)
+        r = self._result(q)
+        p = r["xpos"][:, i]
+        if x is None:
+            return p
+        import torch
+        x = torch.as_tensor(x, dtype=p.dtype, device=p.device).reshape(3)
+        return p + (r["xmat"][:, i].reshape(-1, 3, 3) @ x)
