@@ -19,9 +19,13 @@ progress, not the 25 steps after a global reset.  `--level ctrl` times the ctrl-
 torques, `--frame-skip` substeps per step, default 1) used for oracle parity.
 Environments are independent, so ranks shard them with no data-path collective; the only collective is the per-step
 all_gather of the observation rows, as the north star prescribes.
-Also reported: the roofline of the physics kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s), VALU issue rate
-(from the committed PMC pass), throughput at small action scales, and -- on rank 0 at N = 1 -- the fp64 oracle timed on the
-host cores as a CPU baseline ("port") together with the 1 000-substep drift of the HIP path against that same oracle run.
+Also reported: the roofline of the physics kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s) and VALU issue rate
+(from the committed PMC pass).
+A plain run does only what the headline needs: set-up and pre-roll, warm-up, the timed steps, --dump-outputs, the JSON line.
+`--full` adds the measurements that take runs of their own: throughput at small action scales, with the shipped policy and in
+BASELINE configs 2 and 4 (child processes), a flag census after the timed window, and -- on rank 0 at N = 1 -- the fp64 oracle
+timed on the host cores as a CPU baseline ("port") together with the 1 000-substep drift of the HIP path against that same
+oracle run (ctrl level and closed-loop env level).  Each of them can also be asked for on its own by its option.
 `--dump-outputs DIR` writes what the last timed step returned to its caller as .npy files: the inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
 """
@@ -41,6 +45,7 @@ HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2   # wave-instructions/s: 1 024 SIMD-32 units, one wave64 VALU instruction per 2 cycles, 2.4 GHz
 PMC_FILE = os.path.join(ROOT, "profiles", "r05_pmc.json")
 DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload
+FULL_DEFAULTS = {"extra_scales": "0.3,0.05", "policy_leg": "picking", "config_legs": "2,4", "flag_census": 20}   # side measurements of a --full run
 
 
 def parse_args(argv=None):
@@ -58,19 +63,26 @@ def parse_args(argv=None):
                     help="untimed env steps (finished envs reset as in the timed loop) before warmup; default = one full episode length: with the step "
                          "counters staggered over [0, 700) every env has then been reset once and the episodes' physical ages are spread over [0, 700) "
                          "(profiles/r04_soak_curve.txt: ms/step does not depend on the rollout's age from step 50 on)")
-    ap.add_argument("--extra-scales", default="0.3,0.05", help="action scales also timed (briefly, each in a child process before the headline run); '' = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the legs of --extra-scales, --policy-leg and --config-legs, the flag census and, unless "
+                         "--no-cpu-baseline, the CPU baseline and the drift legs; without it a run does what the headline needs and nothing else")
+    ap.add_argument("--extra-scales", default=None,
+                    help="action scales also timed (briefly, each in a child process before the headline run); '' = none (default: %s with --full, none without)" % FULL_DEFAULTS["extra_scales"])
     ap.add_argument("--policy", default=None,
                     help="actions from one of the reference's shipped policies instead of U(-1,1): 'picking' | 'placing' (tests/golden/policy_<task>.npz) or a policy.zip / .npz path; the policy's forward pass is inside the timed step")
-    ap.add_argument("--policy-leg", default="picking", help="policy also timed (briefly, in a child process before the headline run); '' = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--policy-leg", default=None,
+                    help="policy also timed (briefly, in a child process before the headline run); '' = none (default: %s with --full, none without)" % FULL_DEFAULTS["policy_leg"])
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no drift legs (a run without --full has none)")
     ap.add_argument("--hints", type=int, default=None, help="tier hint mode of the env handle (diagnostic; default = the library's)")
     ap.add_argument("--drift-gpu-leg", default=None, help=argparse.SUPPRESS)   # internal: child process that steps the HIP path on the drift workload
     ap.add_argument("--env-drift-gpu-leg", default=None, help=argparse.SUPPRESS)   # internal: child process, HIP leg of the env-level closed-loop drift
     ap.add_argument("--no-reset", action="store_true", help="finished envs stay frozen (BASELINE config 4: termination masking, no auto-reset)")
     ap.add_argument("--explicit-reset", action="store_true", help="reset finished envs with a masked jaco_reset launch chain after every step instead of inside jaco_step (option auto_reset)")
     ap.add_argument("--no-contact", action="store_true", help="contacts disabled (BASELINE config 2: arm-only model)")
-    ap.add_argument("--config-legs", default="2,4", help="BASELINE configs also timed (briefly, each in a child process before the headline run); '' = none")
-    ap.add_argument("--flag-census", type=int, default=20, help="untimed env steps after the timed window in which error flags are counted per step (0 = off)")
+    ap.add_argument("--config-legs", default=None,
+                    help="BASELINE configs also timed (briefly, each in a child process before the headline run); '' = none (default: %s with --full, none without)" % FULL_DEFAULTS["config_legs"])
+    ap.add_argument("--flag-census", type=int, default=None,
+                    help="untimed env steps after the timed window in which error flags are counted per step; 0 = off (default: %d with --full, 0 without)" % FULL_DEFAULTS["flag_census"])
     ap.add_argument("--set-option", action="append", default=[], help="name=value passed to jaco_set_option (e.g. compensated=0); repeatable")
     ap.add_argument("--dry-gather", action="store_true",
                     help="CPU rehearsal of the N > 1 plumbing (spawn, rendezvous, gather, max-over-ranks timing) on gloo: no GPU, no physics")
@@ -81,6 +93,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for k, v in FULL_DEFAULTS.items():   # a side measurement runs when --full or its own option asks for it
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else type(v)())
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
     return args
 
 
@@ -156,11 +172,12 @@ def leg_flags(line):
 def small_action_runs(args):
     """Throughput at the smaller action scales (the regime a converged policy lives in: the EE sits on its "hand" marker), each in
     its own child process started BEFORE this process touches the GPU: the parent's launch statistics (rocprofv3 --stats, HIP-event
-    kernel time) then hold the headline workload only."""
+    kernel time) then hold the headline workload only.
+    The side legs are --full runs with their own side legs and CPU baseline switched off: each keeps its flag census (LEG_FLAGS)."""
     out = {}
     for sc in [x for x in args.extra_scales.split(",") if x]:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--action-scale", sc, "--steps", "6", "--warmup", "2", "--preroll", "16",
-               "--batch", str(args.batch), "--model", args.model, "--task", args.task, "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
+               "--batch", str(args.batch), "--model", args.model, "--task", args.task, "--full", "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
         if args.frame_skip is not None:
             cmd += ["--frame-skip", str(args.frame_skip)]
         cmd += [x for kv in args.set_option for x in ("--set-option", kv)]   # (library options follow into the side legs: A/B runs)
@@ -181,7 +198,7 @@ def policy_run(args):
     if not args.policy_leg or args.policy:
         return None
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--policy", args.policy_leg, "--task", args.policy_leg, "--steps", "10", "--warmup", "2",
-           "--preroll", "180", "--batch", str(args.batch), "--model", args.model, "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
+           "--preroll", "180", "--batch", str(args.batch), "--model", args.model, "--full", "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
     if args.frame_skip is not None:
         cmd += ["--frame-skip", str(args.frame_skip)]
     cmd += [x for kv in args.set_option for x in ("--set-option", kv)]   # (library options follow into the side legs: A/B runs)
@@ -202,7 +219,7 @@ def config_legs(args):
               launch = `frame_skip` (50) substeps;
     config 4: 65 536 envs, full model, env-level step with frame_skip 4 and termination masking (finished envs stay frozen, no reset)."""
     out = {}
-    common = ["--gpus", "1", "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
+    common = ["--gpus", "1", "--full", "--no-cpu-baseline", "--extra-scales", "", "--policy-leg", "", "--config-legs", ""]
     legs = {"2": ["--level", "ctrl", "--model", "jaco2_reaching_torque", "--batch", "4096", "--frame-skip", "50", "--no-contact", "--steps", "200", "--warmup", "20"],
             "4": ["--level", "env", "--model", args.model, "--task", args.task, "--batch", str(args.batch), "--frame-skip", "4", "--no-reset", "--steps", "60", "--warmup", "10", "--preroll", "60"]}
     for c in [x for x in args.config_legs.split(",") if x]:
@@ -632,7 +649,7 @@ def main():
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s: %d envs/GPU, %s, %s reset distribution, %s" % (cfgname, B, args.model, args.task, workload_desc),
-                       "level": args.level, "action_scale": args.action_scale, "preroll_steps": args.preroll if args.level == "env" else 0,
+                       "level": args.level, "full": args.full, "action_scale": args.action_scale, "preroll_steps": args.preroll if args.level == "env" else 0,
                        "envs_per_gpu": B, "frame_skip": fs, "substeps_per_s": world * B * args.steps * fs / dt,
                        "done_fraction": done_fraction,
                        "small_action_env_steps_per_s": small, "policy_driven": pol_leg,

@@ -1,4 +1,4 @@
-"""One-line digest of a bench.py JSON line (headline, side legs, tier shares): python tools/bench_summary.py <bench.json>"""
+"""One-line digest of a `bench.py --full` JSON line (headline, side legs, tier shares): python tools/bench_summary.py <bench.json>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c = d["config"]
 print("headline %.3f M (%.2f ms) | scale 0.3 / 0.05: %s | policy %.3f M (bigger-tier share %.2f) | config2 %.2f M | config4 %.2f M (%s launches) | bigger-tier share %.2f | roofline frac %.3g | cpu %s" % (
