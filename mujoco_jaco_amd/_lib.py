@@ -23,6 +23,18 @@ class JacoQueryOut(ctypes.Structure):
     _fields_ = [("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("jac", ctypes.c_void_p), ("qM", ctypes.c_void_p), ("qfrc_bias", ctypes.c_void_p)]
 
 
+class JacoContact(ctypes.Structure):
+    """JacoContact of include/jaco_env.h: one record of the contact record (jaco_set_contact_record), 96 bytes."""
+    _fields_ = [("dist", ctypes.c_float), ("pos", ctypes.c_float * 3), ("frame", ctypes.c_float * 9), ("force", ctypes.c_float * 6),
+                ("geom", ctypes.c_int32 * 2), ("body", ctypes.c_int32 * 2), ("dim", ctypes.c_int32)]
+
+
+JACO_CONTACT_MAX_CAPACITY = 1024
+CONTACT_WORDS = ctypes.sizeof(JacoContact) // 4        # 24 32-bit words per record
+CONTACT_FLOATS = JacoContact.geom.offset // 4          # the first 19 are floats (dist, pos, frame, force), then 5 int32 (geom, body, dim)
+assert ctypes.sizeof(JacoContact) == 96 and CONTACT_FLOATS == 19
+
+
 class JacoConfig(ctypes.Structure):
     _fields_ = [("model_blob", ctypes.c_void_p), ("model_blob_size", ctypes.c_size_t), ("num_envs", ctypes.c_int),
                 ("device", ctypes.c_int), ("frame_skip", ctypes.c_int), ("task", ctypes.c_int), ("seed", ctypes.c_uint64)]
@@ -73,6 +85,7 @@ SYMBOLS = {
     "jaco_step_time_ms": (_ci, [_vp, ctypes.POINTER(_cd)]),
     "jaco_stage_profile": (_ci, [_vp, ctypes.POINTER(ctypes.c_uint64), _ci]),
     "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
 }
 
 _libs = {}

@@ -89,6 +89,9 @@ struct JacoHandle {
   int min_nsub_order = 8;     // option "min_nsub_order": shortest step that gets the cost-ordered launch (two small launches in front of the light grid); at frame_skip 4 the
                               // ordering does not pay: 19.4-19.7 M env-steps/s with it, 20.1 M without (round 5, tools/gpu_cfg4_options.sh)
   const float* noise = nullptr;
+  JacoContactRec* con_rec = nullptr;   // contact record (jaco_set_contact_record): caller-owned [num_envs][con_cap], or nullptr = off
+  int* con_n = nullptr;                // [num_envs] true contact counts
+  int con_cap = 0;
   const float* subgoal = nullptr;   // obs_mode 1: the policy's sub-goal offsets for the "subgoal_reach" marker
   int obs_mode = 0;
   unsigned long long* prof = nullptr;
@@ -539,6 +542,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   A.env_mode = io.mode; A.task_id = h->task; A.nact = (h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PUSHING) ? 6 : 7; A.seed = h->seed;
   A.task = h->task_rows; A.cache = h->cache; A.action = io.action; A.noise = h->noise; A.obs_mode = h->obs_mode; A.subgoal = h->subgoal; A.obs = io.obs; A.reward = io.reward; A.done = io.done; A.terminal = h->terminal; A.terminal_obs = h->terminal_obs; A.goal_buf = h->goal_buf; A.goal_n = h->goal_n; A.goal_stride = h->goal_stride; A.mask = io.mask; A.marker = h->marker;
   A.cost = h->cost;
+  if (io.mode <= 1 && h->con_rec) { A.con_rec = h->con_rec; A.con_n = h->con_n; A.con_cap = h->con_cap; }   // (forward passes and resets record nothing)
   // auto-reset folds draws + sim.forward() + observation into the step wave: the tasks whose reset is nothing more (placing holds the
   // object for 150 substeps, grasping pre-reaches: those keep the explicit jaco_reset)
   A.auto_reset = h->auto_reset && io.mode == 1 && (h->task == JACO_TASK_PICKING || h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PICKANDPLACE || h->task == JACO_TASK_PUSHING);
@@ -730,6 +734,20 @@ extern "C" int jaco_terminal_inspection(JacoHandle* h, uint8_t* done_dev, float*
 extern "C" int jaco_set_noise(JacoHandle* h, const float* noise_dev) {
   if (!h) return JACO_EINVAL;
   h->noise = noise_dev;
+  return JACO_OK;
+}
+static_assert(sizeof(JacoContact) == sizeof(JacoContactRec) && offsetof(JacoContact, force) == offsetof(JacoContactRec, force) &&
+              offsetof(JacoContact, geom) == offsetof(JacoContactRec, geom) && offsetof(JacoContact, dim) == offsetof(JacoContactRec, dim),
+              "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
+extern "C" int jaco_set_contact_record(JacoHandle* h, JacoContact* rec_dev, int32_t* ncon_dev, int capacity) {
+  if (!h) return JACO_EINVAL;
+  if (!rec_dev) { h->con_rec = nullptr; h->con_n = nullptr; h->con_cap = 0; return JACO_OK; }
+  if (!ncon_dev || capacity < 1 || capacity > JACO_CONTACT_MAX_CAPACITY) {
+    h->err = "jaco_set_contact_record: needs a count buffer and 1 <= capacity <= " + std::to_string(JACO_CONTACT_MAX_CAPACITY);
+    return JACO_EINVAL;
+  }
+  if ((reinterpret_cast<uintptr_t>(rec_dev) & 15u) != 0) { h->err = "jaco_set_contact_record: the record buffer must be 16-byte aligned"; return JACO_EINVAL; }
+  h->con_rec = reinterpret_cast<JacoContactRec*>(rec_dev); h->con_n = ncon_dev; h->con_cap = capacity;
   return JACO_OK;
 }
 extern "C" int jaco_set_subgoal(JacoHandle* h, const float* subgoal_dev) {

@@ -116,6 +116,14 @@ JDEV void jprof_stamp(JProfCtx& pc, int i, int lane) {
 #define JSTAMP_NARROW(i)
 #endif
 
+// One contact of the contact record (jaco_set_contact_record): = JacoContact of include/jaco_env.h (static_assert in jaco_env.hip), 96 bytes
+struct JacoContactRec {
+  float dist, pos[3], frame[9];   // MuJoCo's contact: distance, position, frame (row 0 = normal, from geom 1 towards geom 2)
+  float force[6];                 // mj_contactForce (pyramidal cone): normal, two tangential, torsional, two rolling, in the contact frame
+  int geom[2], body[2], dim;      // the pair's kernel geom ids (JacoPairParam g1 / g2), the geoms' original (unfused) bodies, condim
+};
+#define JCONREC_WORDS 24
+
 struct JacoStepArgs {
   const JacoModelDev* model;
   const float* hull;   // float4 per hull vertex
@@ -182,6 +190,10 @@ struct JacoStepArgs {
   unsigned long long* prof;  // diagnostic build only: [nenv][JPROF_N] cycle sums, else nullptr
   float* dbg;          // optional stage dump of env dbg_env (see JDBG_* offsets), else nullptr
   int dbg_env;
+  // contact record (jaco_set_contact_record), modes 0 / 1 only: the contacts of the last integrating substep of the launch, or nullptr = off
+  JacoContactRec* con_rec;   // [nenv][con_cap]
+  int* con_n;                // [nenv] the true contact count (may exceed con_cap: the records past it are dropped)
+  int con_cap;
 };
 
 // The kernel's argument block, read afresh from the kernarg segment.  The block holds ~50 pointers (100 SGPRs' worth); read through
@@ -1867,6 +1879,43 @@ JDEV void hint_raise(const JacoStepArgs& A, int env, int tier, int lane) {
 }
 
 // ---------------------------------------------------------------- the kernels
+// ---------------------------------------------------------------- contact record (jaco_set_contact_record)
+// What data.contact and mj_contactForce give after mj_step, for the last substep of a mode 0 / 1 launch, written by run_env's epilogue:
+// lane = contact (the first `cap`), each lane sums its own contact's rows -- rows in the light tier's side buffer are read there, as
+// stage_touch does -- and writes the 96-byte record as six 16-byte stores; lane 0 writes the true count.  (In the epilogue rather than
+// next to the stage dump inside the substep loop: there it cost the light kernel 8 bytes of scratch per lane.)
+// Plain stores: the record is written once per env per launch, by the one workgroup that finishes the env's step (a hand-off to a bigger
+// tier or a hand-back leaves substeps to the next one and writes nothing), and nothing reads it before the launch set is over.  No other workgroup reads or rewrites these bytes in between, which is what the write-through stores of the state rows
+// guard against.
+template <class L>
+JDEV void stage_record(const JacoModelDev* m, L& s, JacoContactRec* rec, int* nout, int cap, int env, int lane) {
+  const int ncon = L::Caps::CONTACT ? wave_uniform_i(s.ncon) : 0;
+  if (lane == 0) nout[env] = ncon;
+  if constexpr (L::Caps::CONTACT) {
+    const int n = ncon < cap ? ncon : cap;
+    for (int ci = lane; ci < n; ci += 64) {
+      const int cd = s.c_dim[ci], nrow = cd == 1 ? 1 : 2 * (cd - 1), r0 = s.c_efc[ci], obs = s.c_ob[ci];
+      const float* f = (SideRows<L>::on && r0 >= JSIDE_BASE) ? side_buf(s) + JSIDE_F + (r0 - JSIDE_BASE) : s.e_f + r0;
+      const JacoPairParam& P = m->pair[s.c_pair[ci]];
+      // mju_decodePyramid: normal = sum of the 2 (dim - 1) edge forces, component k = mu[k - 1] (f[2k - 2] - f[2k - 1])
+      float fc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int e = 0; e < nrow; e++) fc[0] += f[e];
+#pragma unroll
+      for (int k = 1; k < 6; k++) if (k < cd) fc[k] = P.mu[k - 1] * (f[2 * k - 2] - f[2 * k - 1]);
+      const float* fr = s.c_frame[ci];
+      v4* o = reinterpret_cast<v4*>(rec + (size_t)env * cap + ci);
+      const auto bits = [](int i) { return __builtin_bit_cast(float, i); };
+      o[0] = v4{s.c_dist[ci], s.c_pos[ci][0], s.c_pos[ci][1], s.c_pos[ci][2]};
+      o[1] = v4{fr[0], fr[1], fr[2], fr[3]};
+      o[2] = v4{fr[4], fr[5], fr[6], fr[7]};
+      o[3] = v4{fr[8], fc[0], fc[1], fc[2]};
+      o[4] = v4{fc[3], fc[4], fc[5], bits(P.g1)};
+      o[5] = v4{bits(P.g2), bits(obs & 0xFF), bits((obs >> 16) & 0xFF), bits(cd)};
+    }
+  }
+}
+static_assert(sizeof(JacoContactRec) == 4 * JCONREC_WORDS && JCONREC_WORDS % 4 == 0, "contact record: whole 16-byte stores");
+
 // One substep loop for one env; returns the number of substeps NOT done (light tier bail-out) or 0.
 // TIER: 0 light, 1 medium, 2 heavy, 3 huge.  Tiers below 3 stop at a capacity overflow (*why = 1) and leave the env to the next
 // tier; tiers above 0 can give the env back to the tier below once it would fit again (handback; *why = 2).
@@ -2292,6 +2341,9 @@ again:
     }
   }
   Ap = args_view(A_);   // (the epilogue reads the argument block afresh: nothing of it was carried through the substep loop)
+  // contact record: the contacts of the substep this call ended with, still in LDS (Euler and the position update touch neither the contact
+  // list nor the row forces).  Not of a forward pass, a reset or the auto-reset's forward pass (fwd); nothing when the env was handed on.
+  if (A.con_rec && left == 0 && !fwd && emode <= 1 && nsub > sub0) stage_record(m, s, A.con_rec, A.con_n, A.con_cap, env, lane);
   bool reset_now = false, term_now = false;
   // Write-through stores for everything another workgroup may read or REWRITE before this launch set is over: an env that is handed over
   // (bailed), and -- option auto_reset -- every normal step's outputs, because a step that ends its episode is followed by the in-kernel

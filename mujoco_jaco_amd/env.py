@@ -123,6 +123,19 @@ class JacoBatchedEnv:
             self._robot_config = BatchedMujocoConfig(self.sim, ee="EE" if self.n_robots == 1 else "EE_1")
         return self._robot_config
 
+    def record_contacts(self, capacity=16):
+        """BatchedMujoco.record_contacts of this env's sim: every step() records each env's contacts of its last substep and their
+        forces (capacity 0: off).  reset() writes nothing; with auto_reset the record after a terminal step is the terminal step's."""
+        self.sim.record_contacts(capacity)
+
+    def contacts(self):
+        """BatchedMujoco.contacts: the contact record of the last step() (device tensors, MJCF geom / body ids)."""
+        return self.sim.contacts()
+
+    def net_contact_force(self, body_a, body_b):
+        """[num_envs, 3] world-frame force MJCF body body_a exerts on body_b in the last step() (BatchedMujoco.net_contact_force)."""
+        return self.sim.net_contact_force(body_a, body_b)
+
     # ---- helpers
     def _p(self, t):
         return ctypes.c_void_p(t.data_ptr())

@@ -10,11 +10,46 @@ import numpy as np
 import torch
 
 from . import _lib
-from .robot_config import FrameTable
+from .robot_config import ContactNames, FrameTable
 
 
 class JacoError(RuntimeError):
     pass
+
+
+class Contacts:
+    """One contact record (BatchedMujoco.contacts): the fields of include/jaco_env.h JacoContact as [B, K, ...] device tensors."""
+
+    def __init__(self, rec, ncon, gmap):
+        B, K, _ = rec.shape
+        f = rec[..., :_lib.CONTACT_FLOATS]
+        i = rec.view(torch.int32)[..., _lib.CONTACT_FLOATS:]
+        self.ncon = ncon.clone()
+        self.valid = torch.arange(K, device=rec.device)[None, :] < self.ncon[:, None]
+        v = self.valid
+        z = lambda t: torch.where(v.reshape(B, K, *([1] * (t.dim() - 2))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+        self.dist = z(f[..., 0])
+        self.pos = z(f[..., 1:4])
+        self.frame = z(f[..., 4:13]).reshape(B, K, 3, 3)
+        self.force = z(f[..., 13:19])
+        ids = i.long()
+        geom = gmap[ids[..., 0:2].clamp(0, gmap.numel() - 1)]
+        neg = torch.full((), -1, dtype=torch.int64, device=rec.device)
+        self.geom = torch.where(v[..., None], geom, neg)
+        self.body = torch.where(v[..., None], ids[..., 2:4], neg)
+        self.dim = torch.where(v, i[..., 4], torch.zeros((), dtype=torch.int32, device=rec.device))
+
+    def world_force(self):
+        """[B, K, 3] contact force in world coordinates: the force geom 1's body exerts on geom 2's body (MuJoCo's sign: J = frame (J2 - J1))."""
+        return (self.frame[..., :3, :] * self.force[..., :3, None]).sum(-2)
+
+    def net_force(self, body_a, body_b):
+        """[B, 3] world-frame force that MJCF body id body_a exerts on body_b, summed over the recorded contacts between them."""
+        fw = self.world_force()
+        ab = (self.body[..., 0] == body_a) & (self.body[..., 1] == body_b)
+        ba = (self.body[..., 0] == body_b) & (self.body[..., 1] == body_a)
+        sgn = ab.to(fw.dtype) - ba.to(fw.dtype)
+        return (fw * sgn[..., None]).sum(1)
 
 
 class BatchedMujoco:
@@ -144,6 +179,48 @@ class BatchedMujoco:
             dadr += d
         qpos, qvel, _ = self.get_state()
         return {"q": qpos[:, qadr], "dq": qvel[:, dadr]}
+
+    # ---- contact readout (jaco_set_contact_record; data.contact + mj_contactForce after mj_step)
+    def record_contacts(self, capacity=16):
+        """Turn the contact record on with room for `capacity` contacts per env (0: off).  From the next step call on, every
+        jaco_physics_step / jaco_step writes each env's contacts of its last integrating substep and their contact-frame forces; read
+        them with contacts().  Forward passes and resets write nothing (with auto_reset the record holds the terminal step's contacts)."""
+        capacity = int(capacity)
+        if capacity <= 0:
+            self._chk(self.L.jaco_set_contact_record(self.h, None, None, 0))
+            self._crec = self._cn = None
+            return
+        # [B][capacity] JacoContact records (CONTACT_WORDS 32-bit words each) and [B] counts; zeroed so that contacts() before the
+        # first step reads "no contact"
+        rec = torch.zeros(self.num_envs, capacity, _lib.CONTACT_WORDS, dtype=torch.float32, device=self.device)
+        cn = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self._chk(self.L.jaco_set_contact_record(self.h, ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(cn.data_ptr()), capacity))
+        self._crec, self._cn = rec, cn   # (kept alive here: the library only holds the pointers)
+        if getattr(self, "_gmap", None) is None:
+            self.contact_names = ContactNames.for_model(self.robot_file)
+            self._gmap = torch.tensor(self.contact_names.kernel_geom, dtype=torch.int64, device=self.device)
+
+    def contacts(self):
+        """The record of the last step call as device tensors (copies; no host synchronisation).  B envs, K = capacity:
+        ncon [B] int32, the TRUE contact count (> K: records past K were dropped);  valid [B, K] bool (slot < min(ncon, K));
+        dist [B, K];  pos [B, K, 3];  frame [B, K, 3, 3] (row 0 = normal, from geom 1 towards geom 2);  force [B, K, 6] in the contact
+        frame (mj_contactForce: normal, two tangential, torsional, two rolling);  dim [B, K] int32;  geom [B, K, 2] / body [B, K, 2]
+        MJCF geom / body ids (-1 in invalid slots).  Invalid slots are zero."""
+        if getattr(self, "_crec", None) is None:
+            raise JacoError("contacts(): call record_contacts(capacity) first")
+        return Contacts(self._crec, self._cn, self._gmap)
+
+    def net_contact_force(self, body_a, body_b, contacts=None):
+        """[num_envs, 3] world-frame force that MJCF body `body_a` exerts on `body_b` (names or ids), summed over their recorded contacts
+        (those past the capacity are not in the record).  Computed in torch from contacts() (or the `contacts` given)."""
+        return (contacts if contacts is not None else self.contacts()).net_force(self._body(body_a), self._body(body_b))
+
+    def _body(self, b):
+        if isinstance(b, str):
+            if getattr(self, "contact_names", None) is None:
+                self.contact_names = ContactNames.for_model(self.robot_file)
+            return self.contact_names.body_id(b)
+        return int(b)
 
     def sensordata(self):
         out = torch.empty(self.num_envs, self.nsensor, device=self.device)

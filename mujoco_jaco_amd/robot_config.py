@@ -97,6 +97,42 @@ class FrameTable:
         return [int(self.M["jnt_qposadr"][j]) for j in joints], [int(self.M["jnt_dofadr"][j]) for j in joints]
 
 
+class ContactNames:
+    """MJCF geom / body names <-> the ids of the contact record (BatchedMujoco.contacts): geoms and bodies are reported as MJCF ids
+    (assets/<model>.names.txt order).  The kernel's geom ids, which the library writes, map to MJCF ids through the blob's f_geom_orig
+    (`kernel_geom`); bodies are the original (unfused) MJCF bodies already."""
+
+    def __init__(self, M, names):
+        self.M, self.names = M, names
+        self.bodies, self.geoms = names["body"], names["geom"]
+        self.kernel_geom = np.asarray(M["f_geom_orig"], np.int64)   # kernel geom id -> MJCF geom id
+
+    @classmethod
+    def for_model(cls, robot_file):
+        path = _lib.model_path(robot_file)
+        return cls(blobmod.load(path), read_names(path[:-len(".jacomdl")] + ".names.txt"))
+
+    def body_id(self, name):
+        if name not in self.bodies:
+            raise ValueError("unknown body %r: the model's bodies are %s" % (name, [n for n in self.bodies if n]))
+        return self.bodies.index(name)
+
+    def geom_id(self, name):
+        if name not in self.geoms:
+            raise ValueError("unknown geom %r: the model's named geoms are %s" % (name, [n for n in self.geoms if n]))
+        return self.geoms.index(name)
+
+    def body_name(self, i):
+        return self.bodies[int(i)] if 0 <= int(i) < len(self.bodies) else None
+
+    def geom_name(self, i):
+        return self.geoms[int(i)] if 0 <= int(i) < len(self.geoms) else None
+
+    def geom_body(self, i):
+        """MJCF body id of MJCF geom i."""
+        return int(self.M["geom_bodyid"][int(i)])
+
+
 def mat2quat(R):
     """[..., 9] row-major rotations -> [..., 4] unit quaternions, w first, w >= 0 (mju_mat2Quat's branches)."""
     import torch

@@ -1,0 +1,161 @@
+"""CPU tier: the contact record (jaco_set_contact_record) of the *unmodified* kernel source under the wavefront emulator
+(tests/emu/contacts.mk), against the fp64 oracle's forward() at the same fp32-rounded state: data.contact and mj_contactForce
+restated from its efc_force.  One-substep ctrl-level steps on jaco2_curtain_torque; the record is that substep's forward pass."""
+import os
+
+import numpy as np
+import pytest
+
+import contacts_binding as cb
+from mujoco_jaco_amd.modelc import blob
+from mujoco_jaco_amd.robot_config import ContactNames, FrameTable
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _model(name="jaco2_curtain_torque"):
+    return blob.load(os.path.join(ROOT, "mujoco_jaco_amd", "assets", name + ".jacomdl"))
+
+
+def _record(qs, ctrl, cap=128, layout=""):
+    e = cb.EmuContactEnv(nenv=len(qs), layout=layout)
+    e.qpos[:] = qs; e.qvel[:] = 0; e.qacc_ws[:] = 0
+    rec, n = e.step_rec(ctrl, nsub=1, cap=cap)
+    return e, cb.unpack(rec, n)
+
+
+def _check_against_oracle(M, qs, ctrl, layout=""):
+    e, R = _record(qs, ctrl, layout=layout)
+    worst = {k: np.zeros(4) for k in cb.BOUNDS}
+    for i, q in enumerate(qs):
+        oc = cb.oracle_contacts(cb.oracle_forward("jaco2_curtain_torque", q, ctrl), M)
+        w = cb.compare({k: v[i] for k, v in R.items()}, int(R["ncon"][i]), oc, M)
+        for k in worst:
+            worst[k] = np.maximum(worst[k], w[k])
+    for kind, (bd, bp, bn) in cb.BOUNDS.items():
+        d, p, n, f = worst[kind]
+        assert d < bd and p < bp and n < bn, (kind, worst[kind])
+    assert max(w[3] for w in worst.values()) < cb.FORCE_BOUND, worst
+    return e, R, worst
+
+
+def test_resting_object_matches_oracle(names):
+    """Object on its holder, pedestal on the floor (box-box and plane-box contacts, condim 3), 6 reset draws; in one of them two arm links
+    reach into the pedestal (box-hull contacts 5 and 12 mm deep).  Measured: analytic dist 1.1e-8, pos 1.0e-8, normal 0; hull dist 2.6e-8,
+    pos 5.6e-8, normal 3.9e-6 (the 12 mm one); force 3.3e-6 of the env's largest normal force."""
+    M = _model()
+    e, R, worst = _check_against_oracle(M, cb.rest_states(M, 6), np.zeros(9))
+    print("resting object: worst [dist, pos, normal, force rel]", worst)
+    assert (R["ncon"] >= 8).all() and (R["ncon"] == 8).sum() >= 4
+
+
+@pytest.mark.parametrize("substeps", [30, 40])
+def test_fingers_closed_on_the_object_match_oracle(names, substeps):
+    """Fingers closed on the object: condim-6 hull contacts (MPR) with torsional / rolling force components.
+    After 30 closing substeps: 72 rows, on the light tier with the pedestal's 16 in the side buffer (forces read from there).
+    Measured (40 substeps): analytic dist 4.0e-8, pos 4.1e-8, normal 9.5e-8; hull dist 4.1e-8, pos 1.3e-7, normal 3.4e-7; force 2.9e-6 of the
+    largest normal force."""
+    M = _model()
+    q = cb.grasp_state(M, names, substeps)
+    e, R, worst = _check_against_oracle(M, q[None], cb.GRASP_CTRL)
+    print("grasp: worst [dist, pos, normal, force rel]", worst)
+    n = int(R["ncon"][0])
+    assert n >= 8 and (R["dim"][0, :n] == 6).any()
+    assert np.abs(R["force"][0, :n, 3:]).max() > 0   # torsional / rolling components present
+    if substeps == 30:
+        assert e.stats[0, 1] > 64 and not e.flags[0] & 32   # light tier beyond its 64 rows: side rows
+
+
+def test_deep_overlap_reset_on_the_huge_tier_matches_oracle():
+    """A reset with the hand inside the pedestal: 68 contacts / 308 rows, beyond the heavy tier -- the record is written by the huge tier.
+    Measured: dist 3.9e-8, pos 6.3e-8, normal 4.0e-8, force 1.3e-6 of the largest normal force."""
+    M = _model()
+    e, R, worst = _check_against_oracle(M, cb.deep_state(M)[None], np.zeros(9))
+    print("deep overlap: worst [dist, pos, normal, force rel]", worst, "stats", e.stats[0])
+    assert int(R["ncon"][0]) > 64 and (e.flags[0] & 32) and (e.flags[0] & 7) == 0   # more contacts than the heavy tier holds: huge tier, nothing dropped
+
+
+def test_capacity_truncates_and_reports_the_true_count():
+    M = _model()
+    q = cb.deep_state(M)[None]
+    e4 = cb.EmuContactEnv(); e4.qpos[:] = q; e4.qvel[:] = 0; e4.qacc_ws[:] = 0
+    rec4, n4 = e4.step_rec(np.zeros(9), cap=4, guard=8)
+    _, R = _record(q, np.zeros(9), cap=128)
+    assert n4[0] == R["ncon"][0] > 4                        # the true count
+    assert np.isnan(e4.guard).all()                         # nothing written past the 4 slots
+    assert np.array_equal(rec4[0].view(np.int32), np.stack([np.concatenate([R[k][0, :4].reshape(4, -1).view(np.int32) for k in
+                                                                            ("dist", "pos", "frame", "force", "geom", "body", "dim")], 1)])[0])
+
+
+def test_recording_changes_no_result():
+    """Record on or off, the state, sensors, flags and stats of a 5-substep step are bit-identical -- and equal to the plain emulator
+    driver's (tests/emu/libjaco_emu.so); the record holds the last substep's contacts."""
+    from emu_binding import EmuEnv
+    from mujoco_jaco_amd import workload
+    M = _model()
+    qs = np.concatenate([cb.rest_states(M, 3), cb.deep_state(M)[None]])
+    ctrl = workload.random_ctrl(4, seed=9, scale=0.3).astype(np.float32)
+    out = []
+    for cap in (0, 4, 64):
+        e = cb.EmuContactEnv(nenv=4); e.qpos[:] = qs
+        rec, n = e.step_rec(ctrl, nsub=5, cap=cap)
+        out.append((e.qpos.copy(), e.qvel.copy(), e.qacc_ws.copy(), e.sensordata.copy(), e.flags.copy(), e.stats.copy()))
+        if cap:
+            assert np.array_equal(n, e.stats[:, 0])   # the last substep's count (stats hold the same)
+    p = EmuEnv(nenv=4); p.qpos[:] = qs
+    p.step(ctrl, nsub=5)
+    out.append((p.qpos, p.qvel, p.qacc_ws, p.sensordata, p.flags, p.stats))
+    for o in out[1:]:
+        for a, b in zip(out[0], o):
+            assert np.array_equal(a, b)
+
+
+def test_contact_free_steps_record_no_contact():
+    M = _model()
+    e = cb.EmuContactEnv(nenv=2); e.qpos[:] = cb.rest_states(M, 2)
+    rec, n = e.step_rec(np.zeros(9), cap=8, disable_contact=True)   # (the contact-free kernel)
+    assert (n == 0).all() and np.isnan(rec).all()
+
+
+def test_record_names_map_to_mjcf_bodies_and_geoms(names):
+    """The record's ids, mapped as BatchedMujoco.contacts() maps them: the object's contacts on its holder name `object_body` and
+    `object_holder`, the ids FrameTable gives those bodies, and geoms of those bodies."""
+    M = _model()
+    _, R = _record(cb.rest_states(M, 1), np.zeros(9))
+    CN = ContactNames.for_model("jaco2_curtain_torque")
+    T = FrameTable.for_model("jaco2_curtain_torque")
+    assert CN.body_id("object_body") == T.body_id("object_body") == names["body"].index("object_body")
+    n = int(R["ncon"][0])
+    pairs = {tuple(sorted(CN.body_name(b) for b in R["body"][0, k])) for k in range(n)}
+    assert ("object_body", "object_holder") in pairs and ("object_dest", "world") in pairs, pairs
+    for k in range(n):
+        for h in range(2):
+            g = CN.kernel_geom[R["geom"][0, k, h]]
+            assert CN.geom_body(g) == R["body"][0, k, h]   # each geom sits on its reported body
+    assert CN.geom_name(CN.kernel_geom[0]) == "floor_wood" and CN.geom_id("floor_wood") == 0
+    with pytest.raises(ValueError):
+        CN.body_id("no_such_body")
+
+
+@pytest.mark.parametrize("layout", ["_wrench", "_nolook", "_mprpairs"])
+def test_ab_build_options_record_the_same_contacts(layout, names):
+    """The kernel's A/B build options (body-space rows, no Newton look-ahead, MPR two pairs per wave) compile with the record and agree
+    with the oracle to the same bounds."""
+    M = _model()
+    _check_against_oracle(M, np.concatenate([cb.rest_states(M, 2), cb.grasp_state(M, names)[None]]), np.zeros(9), layout=layout)
+
+
+def test_dual_arm_layout_counts_match_the_oracle():
+    """The _d30 layout (jaco2_dual_torque, ctrl level): the arm-on-arm poses of tests/golden/dual_cross_poses.npz give the oracle's contact counts."""
+    P = np.load(os.path.join(ROOT, "tests", "golden", "dual_cross_poses.npz"))
+    qs = P["qpos"][:4]
+    M = _model("jaco2_dual_torque")
+    e = cb.EmuContactEnv("jaco2_dual_torque", nenv=len(qs), layout="_d30")
+    e.qpos[:] = qs
+    rec, n = e.step_rec(np.zeros(18), cap=64)
+    R = cb.unpack(rec, n)
+    for i, q in enumerate(qs):
+        oc = cb.oracle_contacts(cb.oracle_forward("jaco2_dual_torque", q, np.zeros(18)), M)
+        assert n[i] == oc["ncon"] == P["ncon"][i], (i, n[i], oc["ncon"])
+        m = min(int(n[i]), 64)
+        assert np.isfinite(R["force"][i, :m]).all() and (R["force"][i, :m, 0] >= 0).all()
