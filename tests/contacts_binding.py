@@ -1,29 +1,10 @@
-"""ctypes binding of tests/emu/libjaco_emu_contacts*.so (tests/emu/contacts.mk) and the oracle side of the contact record -- TEST
-INFRASTRUCTURE ONLY.  Shared by the CPU tests (tests/test_contacts_emu.py) and the GPU tests (tests/test_gpu_contacts.py).
+"""The oracle side of the contact record, and how to read the emulator's (emu_binding.EmuEnv.step_rec) -- TEST INFRASTRUCTURE ONLY.
+Shared by the CPU tests (tests/test_contacts_emu.py) and the GPU tests (tests/test_gpu_contacts.py).
 
 Record layout: include/jaco_env.h JacoContact = 19 floats (dist, pos[3], frame[9], force[6]) then 5 int32 (geom[2], body[2], dim)."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 
-from emu_binding import EMU_DIR, EmuEnv
-
 NF = 19   # float words of a record; then geom[2], body[2], dim
-_libs = {}
-
-
-def lib(layout=""):
-    if layout not in _libs:
-        name = "libjaco_emu_contacts%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, "-f", "contacts.mk", name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        fp, ip, up, vp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint), ctypes.c_void_p
-        L.emu_contacts_step.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, up, ip,
-                                        vp, ip, ctypes.c_int, ip]
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def unpack(rec, ncon):
@@ -32,34 +13,6 @@ def unpack(rec, ncon):
     i = rec.view(np.int32)[..., NF:]
     return {"ncon": ncon.copy(), "dist": f[..., 0], "pos": f[..., 1:4], "frame": f[..., 4:13].reshape(*f.shape[:-1], 3, 3), "force": f[..., 13:19],
             "geom": i[..., 0:2], "body": i[..., 2:4], "dim": i[..., 4]}
-
-
-class EmuContactEnv(EmuEnv):
-    """EmuEnv whose ctrl-level step can record contacts (cap = 0: off)."""
-
-    def __init__(self, model="jaco2_curtain_torque", nenv=1, layout=""):
-        super().__init__(model, nenv)
-        self.CL = lib(layout)
-        assert self.CL.emu_contact_words() == 24
-
-    def step_rec(self, ctrl, nsub=1, cap=16, disable_contact=False, guard=0):
-        """One ctrl-level step with the record on (cap > 0) or off (cap = 0): (rec [nenv][cap][24] words, ncon [nenv]).  `guard` extra
-        records after the buffer's end are passed in NaN-filled and returned as self.guard (a write past the capacity would show there)."""
-        ctrl = np.ascontiguousarray(np.broadcast_to(np.asarray(ctrl, np.float32), (self.nenv, self.nu)))
-        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        buf = np.full(self.nenv * max(cap, 1) + guard, np.nan, np.float32).repeat(24).reshape(-1, 24)   # (NaN: a slot the kernel did not write stands out)
-        rec = buf[:self.nenv * max(cap, 1)].reshape(self.nenv, max(cap, 1), 24)
-        ncon = np.full(self.nenv, -7, np.int32)
-        hv = ctypes.c_int(0)
-        rc = self.CL.emu_contacts_step(self.blob, len(self.blob), self.nenv, nsub, int(disable_contact), fp(self.qpos), fp(self.qvel), fp(self.qacc_ws),
-                                       fp(ctrl), fp(self.sensordata), self.flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
-                                       self.stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                       ctypes.c_void_p(buf.ctypes.data) if cap > 0 else None,
-                                       ncon.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if cap > 0 else None, cap, ctypes.byref(hv))
-        assert rc == 0, rc
-        self.heavy_envs = hv.value
-        self.guard = buf[self.nenv * max(cap, 1):]
-        return (rec, ncon) if cap > 0 else (None, None)
 
 
 def oracle_contacts(o, M):

@@ -1,25 +1,42 @@
 // TEST INFRASTRUCTURE: runs the unmodified kernel source under the lockstep wavefront emulator.
-// Built by tests/emu/Makefile into libjaco_emu.so; used by CPU-side (-m "not gpu") kernel checks.
+// Built by tests/emu/Makefile into every libjaco_emu*.so; used by CPU-side (-m "not gpu") kernel checks: ctrl-level steps (with the
+// contact record of jaco_set_contact_record), env-level calls and robot-configuration queries (jaco_query).
 #include <algorithm>
+#include <cstdio>
 #include <functional>
 #include <string>
 #include <vector>
 
+#include "../../include/jaco_env.h"
 #include "../../mujoco_jaco_amd/csrc/model_blob.h"
 #include "../../mujoco_jaco_amd/csrc/physics_kernel.h"
 
 void emu_run_wave(int block, std::function<void()> body);
+
+static_assert(sizeof(JacoContact) == sizeof(JacoContactRec), "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
 
 extern "C" int emu_dbg_size() { return JDBG_SIZE; }
 extern "C" int emu_lds_bytes() { return (int)sizeof(JacoLDS<JacoLight>); }
 extern "C" int emu_lds_bytes_heavy() { return (int)sizeof(JacoLDS<JacoHeavy>); }
 extern "C" int emu_lds_bytes_medium() { return (int)sizeof(JacoLDS<JacoMedium>); }
 extern "C" int emu_lds_bytes_huge() { return (int)sizeof(JacoLDS<JacoHuge>); }
+extern "C" int emu_query_lds_bytes() { return (int)sizeof(JacoLDS<JacoArm>); }
+extern "C" int emu_contact_words() { return (int)(sizeof(JacoContact) / 4); }
+extern "C" int emu_task_floats() { return JTASK_N; }
+extern "C" int emu_cache_floats() { return JCACHE_N; }
 
-static int g_mpr_output_fwd();
+// the model of the last call: every entry loads its blob into it (the loader starts from a zeroed model and a fresh hull table)
 static JacoModelDev g_model;
 static std::vector<float> g_hull;
-static int g_no_tier_return_fwd();
+static int g_mpr_output = -1;   // -1: the model loader's default
+extern "C" void emu_set_mpr_output(int v) { g_mpr_output = v; }
+static int load_model(const void* blob, long blob_size) {
+  std::string err;
+  if (jaco_model_from_blob(blob, (size_t)blob_size, &g_model, &g_hull, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return -1; }
+  if (g_mpr_output >= 0) g_model.mpr_output = g_mpr_output;
+  return 0;
+}
+
 static std::vector<int> g_hint;
 static int g_use_hints = 0;
 static int g_obs_mode = 0;
@@ -39,8 +56,10 @@ extern "C" void emu_set_pair_list(int on) { g_no_pairlist = !on; }   // 0: every
 static int g_handdown = 0, g_handed_down = 0;
 extern "C" void emu_set_handdown(int on) { g_handdown = on; }
 extern "C" int emu_handed_down() { return g_handed_down; }   // envs passed from the heavy drain to the second medium drain so far
+static int g_no_tier_return = 0;
+extern "C" void emu_set_tier_return(int on) { g_no_tier_return = !on; }
 static int emu_launch(JacoStepArgs A, int* heavy_envs) {
-  A.no_tier_return = g_no_tier_return_fwd();
+  A.no_tier_return = g_no_tier_return;
   A.no_pairlist = g_no_pairlist;
   A.mpr_pairs = g_mpr_pairs;
   if (g_sepdir.size() != (size_t)A.nenv * JMAXPAIR * 4) g_sepdir.assign((size_t)A.nenv * JMAXPAIR * 4, 0.f);
@@ -107,9 +126,7 @@ extern "C" void emu_reset_env(int task_id, unsigned long long seed, int env, int
 extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode, int frame_skip, int task_id, int nact, unsigned long long seed,
                             float* qpos, float* qvel, float* qacc_ws, float* sensordata, unsigned* flags, int* stats, float* task, float* cache,
                             const float* action, const float* noise, float* obs, float* reward, unsigned char* done, float* marker, int* heavy_envs) {
-  std::string err;
-  if (jaco_model_from_blob(blob, (size_t)blob_size, &g_model, &g_hull, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return -1; }
-  if (g_mpr_output_fwd() >= 0) g_model.mpr_output = g_mpr_output_fwd();
+  if (load_model(blob, blob_size)) return -1;
   JacoStepArgs A{};
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = qvel; A.sensordata = sensordata;
   A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = mode == 2 ? 1 : frame_skip; A.env_mode = mode; A.task_id = task_id; A.nact = nact;
@@ -120,31 +137,38 @@ extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode
 }
 // rest pose of the two task-layer markers (what jaco_reset_state writes): 24 floats
 extern "C" int emu_marker_rest(const void* blob, long blob_size, float* out) {
-  std::string err;
-  if (jaco_model_from_blob(blob, (size_t)blob_size, &g_model, &g_hull, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return -1; }
+  if (load_model(blob, blob_size)) return -1;
   for (int k = 0; k < 24; k++) out[k] = g_model.marker_rest[k / 12][k % 12];
   return 0;
 }
-static int g_no_tier_return = 0;
-static int g_mpr_output = -1;   // -1: the model loader's default
-extern "C" void emu_set_mpr_output(int v) { g_mpr_output = v; }
-extern "C" void emu_set_tier_return(int on) { g_no_tier_return = !on; }
-extern "C" int emu_task_floats() { return JTASK_N; }
-extern "C" int emu_cache_floats() { return JCACHE_N; }
 
-extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int nsub, int disable_contact, float* qpos, float* qvel,
-                                float* qacc_ws, const float* ctrl, float* sensordata, unsigned* flags, int* stats, float* dbg, int dbg_env, int* heavy_envs) {
-  static JacoModelDev model;
-  static std::vector<float> hull;
-  std::string err;
-  if (jaco_model_from_blob(blob, (size_t)blob_size, &model, &hull, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return -1; }
-  if (g_mpr_output >= 0) model.mpr_output = g_mpr_output;
+// ctrl-level step (jaco_physics_step): the contact record rec [nenv][cap] / ncon [nenv], or rec = NULL (off; what
+// jaco_set_contact_record(h, NULL, ...) leaves); the stage dump dbg of env dbg_env (dbg_env < 0: none)
+extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int nsub, int disable_contact, float* qpos, float* qvel, float* qacc_ws,
+                                const float* ctrl, float* sensordata, unsigned* flags, int* stats, JacoContact* rec, int* ncon, int cap,
+                                float* dbg, int dbg_env, int* heavy_envs) {
+  if (rec && (!ncon || cap < 1 || cap > JACO_CONTACT_MAX_CAPACITY)) return JACO_EINVAL;
+  if (load_model(blob, blob_size)) return -1;
   JacoStepArgs A{};
-  A.model = &model; A.hull = hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = ctrl; A.sensordata = sensordata;
+  A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = ctrl; A.sensordata = sensordata;
   A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = nsub; A.disable_contact = disable_contact; A.dbg = dbg; A.dbg_env = dbg_env;
-  static JacoModelDev* keep = &model; (void)keep;
+  A.con_rec = reinterpret_cast<JacoContactRec*>(rec); A.con_n = rec ? ncon : nullptr; A.con_cap = rec ? cap : 0;
   return emu_launch(A, heavy_envs);
 }
 
-static int g_no_tier_return_fwd() { return g_no_tier_return; }
-static int g_mpr_output_fwd() { return g_mpr_output; }
+// the host half of jaco_query (argument checks, frame table by value) and the grid of the kernel: one wavefront per env
+extern "C" int emu_query(const void* blob, long blob_size, int nenv, const float* qpos, const float* qvel, const JacoFrame* frames, int nframes,
+                         float* xpos, float* xmat, float* jac, float* qM, float* qfrc_bias) {
+  if (load_model(blob, blob_size)) return -1;
+  if (nframes < 0 || nframes > JACO_QUERY_MAX_FRAMES) return JACO_EINVAL;
+  JacoQueryArgs Q{};
+  for (int f = 0; f < nframes; f++) {
+    if (frames[f].body < -1 || frames[f].body >= g_model.nbody) return JACO_EINVAL;
+    memcpy(&Q.fr[f], &frames[f], sizeof(JacoFrame));
+  }
+  Q.model = &g_model; Q.qpos = qpos; Q.qvel = qvel; Q.xpos = xpos; Q.xmat = xmat; Q.jac = jac; Q.qM = qM; Q.bias = qfrc_bias;
+  Q.nenv = nenv; Q.nframes = nframes;
+  emu_grid = nenv;   // (the kernel reads only blockIdx; the grid jaco_query launches)
+  for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_query_kernel(Q); });
+  return 0;
+}

@@ -1,8 +1,10 @@
-"""ctypes binding of tests/emu/libjaco_emu.so -- TEST INFRASTRUCTURE ONLY.
+"""ctypes binding of tests/emu/libjaco_emu*.so -- TEST INFRASTRUCTURE ONLY.
 
 Runs the *unmodified* HIP kernel source (mujoco_jaco_amd/csrc/physics_kernel.h) compiled for the host
 against a lockstep 64-lane wavefront emulator, so kernel logic can be checked against the oracle
 without a GPU.  Not a product path: the product library refuses to run without a HIP device.
+One library per layout / build option holds every entry: ctrl-level steps (with the contact record),
+env-level calls and robot-configuration queries (tests/query_binding.py), and one set of option switches.
 """
 import ctypes
 import sys
@@ -24,15 +26,23 @@ def lib(layout=""):
     "_d30": the build for jaco2_dual_torque.xml (two arms + two objects, 30 dofs; ctrl level); "_wrench" / "_nolook" / "_mprpairs": A/B builds of the default layout
     (body-space constraint rows; the Newton solver without its look-ahead stop; MPR two pairs per wave)."""
     if layout not in _libs:
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR] + (["libjaco_emu%s.so" % layout] if layout in ("_wrench", "_nolook", "_mprpairs") else []))   # (A/B builds: on demand)
-        L = ctypes.CDLL(os.path.join(EMU_DIR, "libjaco_emu%s.so" % layout))
+        name = "libjaco_emu%s.so" % layout
+        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
+        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
         fp, ip, up = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint)
-        L.emu_physics_step.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, up, ip, fp, ctypes.c_int, ip]
+        L.emu_physics_step.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, up, ip,
+                                       ctypes.c_void_p, ip, ctypes.c_int, fp, ctypes.c_int, ip]
         L.emu_env_call.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong,
                                    fp, fp, fp, fp, up, ip, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_ubyte), fp, ip]
+        L.emu_query.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, fp, fp, ctypes.c_void_p, ctypes.c_int, fp, fp, fp, fp, fp]
         L.emu_marker_rest.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]
         L.emu_set_auto_reset.argtypes = [ctypes.c_int, fp, ctypes.c_int]
         L.emu_reset_env.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp]
+        L.emu_set_init_buffer.argtypes = [fp, ctypes.c_int, ctypes.c_int]
+        for switch in ("obs_mode", "hints", "sep_cache", "mpr_pairs", "pair_list", "handdown", "mpr_output", "tier_return"):
+            getattr(L, "emu_set_" + switch).argtypes = [ctypes.c_int]
+        L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; L.emu_get_counter.restype = ctypes.c_long
+        L.emu_last_terminal.argtypes = []; L.emu_last_terminal.restype = fp
         _libs[layout] = L
     return _libs[layout]
 
@@ -58,6 +68,20 @@ class EmuEnv:
         self.dbg = np.zeros(self.L.emu_dbg_size(), np.float32)
 
     def step(self, ctrl, nsub=1, disable_contact=False, dbg_env=-1):
+        self._physics_step(ctrl, nsub, disable_contact, None, None, 0, dbg_env)
+
+    def step_rec(self, ctrl, nsub=1, cap=16, disable_contact=False, guard=0):
+        """One ctrl-level step with the record on (cap > 0) or off (cap = 0): (rec [nenv][cap][24] words, ncon [nenv]).  `guard` extra
+        records after the buffer's end are passed in NaN-filled and returned as self.guard (a write past the capacity would show there)."""
+        assert self.L.emu_contact_words() == 24
+        buf = np.full(self.nenv * max(cap, 1) + guard, np.nan, np.float32).repeat(24).reshape(-1, 24)   # (NaN: a slot the kernel did not write stands out)
+        rec = buf[:self.nenv * max(cap, 1)].reshape(self.nenv, max(cap, 1), 24)
+        ncon = np.full(self.nenv, -7, np.int32)
+        self._physics_step(ctrl, nsub, disable_contact, buf if cap > 0 else None, ncon if cap > 0 else None, cap, -1)
+        self.guard = buf[self.nenv * max(cap, 1):]
+        return (rec, ncon) if cap > 0 else (None, None)
+
+    def _physics_step(self, ctrl, nsub, disable_contact, rec, ncon, cap, dbg_env):
         ctrl = np.ascontiguousarray(np.broadcast_to(np.asarray(ctrl, np.float32), (self.nenv, self.nu)))
         fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         hv = ctypes.c_int(0)
@@ -65,9 +89,11 @@ class EmuEnv:
                                      fp(self.qacc_ws), fp(ctrl), fp(self.sensordata),
                                      self.flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
                                      self.stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                     ctypes.c_void_p(rec.ctypes.data) if rec is not None else None,
+                                     ncon.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if ncon is not None else None, cap,
                                      fp(self.dbg) if dbg_env >= 0 else None, dbg_env, ctypes.byref(hv))
+        assert rc == 0, rc
         self.heavy_envs = hv.value
-        assert rc == 0
 
 
 class EmuJacoEnv(EmuEnv):
@@ -122,7 +148,6 @@ class EmuJacoEnv(EmuEnv):
 
     def set_init_buffer(self, rows):
         """kwarg init_buffer (jaco_set_init_buffer of the library): recorded rows every reset draws its reaching goal from; None = sampled goals."""
-        self.L.emu_set_init_buffer.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int]
         if rows is None:
             self.L.emu_set_init_buffer(None, 0, 0)
             return

@@ -1,29 +1,18 @@
-"""ctypes binding of tests/emu/libjaco_emu_query{,_d12,_d30}.so (query.mk) -- TEST INFRASTRUCTURE ONLY.
+"""The robot-configuration query kernel (mujoco_jaco_amd/csrc/query.h) under the wavefront emulator (emu_query of
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
-The robot-configuration query kernel (mujoco_jaco_amd/csrc/query.h) under the wavefront emulator, plus the fp64 oracle's answers to the
-same questions, and a stand-in for BatchedMujoco's query surface backed by the emulator (CPU tests of robot_config.BatchedMujocoConfig).
+Also the fp64 oracle's answers to the same questions, and a stand-in for BatchedMujoco's query surface backed by the emulator (CPU tests of
+robot_config.BatchedMujocoConfig).
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
-from emu_binding import EMU_DIR, ASSETS
+import emu_binding
+from emu_binding import ASSETS
 
-_libs = {}
 OUTS = ("xpos", "xmat", "jac", "qM", "qfrc_bias")
-
-
-def lib(layout=""):
-    if layout not in _libs:
-        name = "libjaco_emu_query%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, "-f", "query.mk", name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        fp = ctypes.POINTER(ctypes.c_float)
-        L.emu_query.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, fp, fp, ctypes.c_void_p, ctypes.c_int, fp, fp, fp, fp, fp]
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def blob_of(model):
@@ -34,7 +23,7 @@ def query(model, qpos, qvel, frames, want=OUTS):
     """Emulated jaco_query: {output: array} at the fp32 states qpos [B, nq] / qvel [B, nv] for a list of _lib.JacoFrame."""
     from mujoco_jaco_amd import _lib as product_lib
     blob = blob_of(model)
-    L = lib(product_lib.variant_for(blob))
+    L = emu_binding.lib(product_lib.variant_for(blob))
     qpos = np.ascontiguousarray(qpos, np.float32)
     qvel = np.ascontiguousarray(qvel, np.float32)
     B, nv, nf = qpos.shape[0], qvel.shape[1], len(frames)

@@ -1,5 +1,5 @@
 """CPU tier: the contact record (jaco_set_contact_record) of the *unmodified* kernel source under the wavefront emulator
-(tests/emu/contacts.mk), against the fp64 oracle's forward() at the same fp32-rounded state: data.contact and mj_contactForce
+(emu_binding.EmuEnv.step_rec), against the fp64 oracle's forward() at the same fp32-rounded state: data.contact and mj_contactForce
 restated from its efc_force.  One-substep ctrl-level steps on jaco2_curtain_torque; the record is that substep's forward pass."""
 import os
 
@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import contacts_binding as cb
+from emu_binding import EmuEnv
 from mujoco_jaco_amd.modelc import blob
 from mujoco_jaco_amd.robot_config import ContactNames, FrameTable
 
@@ -18,7 +19,7 @@ def _model(name="jaco2_curtain_torque"):
 
 
 def _record(qs, ctrl, cap=128, layout=""):
-    e = cb.EmuContactEnv(nenv=len(qs), layout=layout)
+    e = EmuEnv(nenv=len(qs), layout=layout)
     e.qpos[:] = qs; e.qvel[:] = 0; e.qacc_ws[:] = 0
     rec, n = e.step_rec(ctrl, nsub=1, cap=cap)
     return e, cb.unpack(rec, n)
@@ -78,7 +79,7 @@ def test_deep_overlap_reset_on_the_huge_tier_matches_oracle():
 def test_capacity_truncates_and_reports_the_true_count():
     M = _model()
     q = cb.deep_state(M)[None]
-    e4 = cb.EmuContactEnv(); e4.qpos[:] = q; e4.qvel[:] = 0; e4.qacc_ws[:] = 0
+    e4 = EmuEnv(); e4.qpos[:] = q; e4.qvel[:] = 0; e4.qacc_ws[:] = 0
     rec4, n4 = e4.step_rec(np.zeros(9), cap=4, guard=8)
     _, R = _record(q, np.zeros(9), cap=128)
     assert n4[0] == R["ncon"][0] > 4                        # the true count
@@ -88,16 +89,15 @@ def test_capacity_truncates_and_reports_the_true_count():
 
 
 def test_recording_changes_no_result():
-    """Record on or off, the state, sensors, flags and stats of a 5-substep step are bit-identical -- and equal to the plain emulator
-    driver's (tests/emu/libjaco_emu.so); the record holds the last substep's contacts."""
-    from emu_binding import EmuEnv
+    """Record on or off, the state, sensors, flags and stats of a 5-substep step are bit-identical -- and equal to those of a plain
+    EmuEnv.step, the record-off path of the same entry; the record holds the last substep's contacts."""
     from mujoco_jaco_amd import workload
     M = _model()
     qs = np.concatenate([cb.rest_states(M, 3), cb.deep_state(M)[None]])
     ctrl = workload.random_ctrl(4, seed=9, scale=0.3).astype(np.float32)
     out = []
     for cap in (0, 4, 64):
-        e = cb.EmuContactEnv(nenv=4); e.qpos[:] = qs
+        e = EmuEnv(nenv=4); e.qpos[:] = qs
         rec, n = e.step_rec(ctrl, nsub=5, cap=cap)
         out.append((e.qpos.copy(), e.qvel.copy(), e.qacc_ws.copy(), e.sensordata.copy(), e.flags.copy(), e.stats.copy()))
         if cap:
@@ -112,7 +112,7 @@ def test_recording_changes_no_result():
 
 def test_contact_free_steps_record_no_contact():
     M = _model()
-    e = cb.EmuContactEnv(nenv=2); e.qpos[:] = cb.rest_states(M, 2)
+    e = EmuEnv(nenv=2); e.qpos[:] = cb.rest_states(M, 2)
     rec, n = e.step_rec(np.zeros(9), cap=8, disable_contact=True)   # (the contact-free kernel)
     assert (n == 0).all() and np.isnan(rec).all()
 
@@ -150,7 +150,7 @@ def test_dual_arm_layout_counts_match_the_oracle():
     P = np.load(os.path.join(ROOT, "tests", "golden", "dual_cross_poses.npz"))
     qs = P["qpos"][:4]
     M = _model("jaco2_dual_torque")
-    e = cb.EmuContactEnv("jaco2_dual_torque", nenv=len(qs), layout="_d30")
+    e = EmuEnv("jaco2_dual_torque", nenv=len(qs), layout="_d30")
     e.qpos[:] = qs
     rec, n = e.step_rec(np.zeros(18), cap=64)
     R = cb.unpack(rec, n)

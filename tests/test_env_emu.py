@@ -283,8 +283,6 @@ def test_kernel_terminal_inspection_against_the_references_own_outputs(model_arr
                 assert e.task[0, 29] == float(bool(rd) and rb > 100)     # success flag (the 4th value the reference's tuple lacks)
             assert e.task[0, 2] == GG["g_nsteps"][k] + 1 and e.task[0, 1] == 1
             if rd:   # the terminal step latches (success, wb) for jaco_get_last_terminal (what survives an in-kernel reset)
-                import ctypes
-                e.L.emu_last_terminal.restype = ctypes.POINTER(ctypes.c_float)
                 lt = e.L.emu_last_terminal()
                 assert lt[0] == e.task[0, 29] and abs(lt[1] - rwb) < 1e-5
 
@@ -374,10 +372,12 @@ def test_auto_reset_equals_the_explicit_reset_chain(names, model_arrays):
     nz = np.full((1, 12), 0.25, np.float32)
     ea, eb = make(), make()
     ea.set_auto_reset(1)
-    oa, ra, da = ea.env_step(a, nz); ob, rb, db = eb.env_step(a, nz)
-    assert da[0] == 0 and np.array_equal(oa, ob) and np.array_equal(ea.qpos, eb.qpos)                 # no episode end: nothing differs
-    oa, ra, da = ea.env_step(a, nz)                              # time-out: auto path resets in the same call
-    ea.set_auto_reset(0)
+    try:
+        oa, ra, da = ea.env_step(a, nz); ob, rb, db = eb.env_step(a, nz)
+        assert da[0] == 0 and np.array_equal(oa, ob) and np.array_equal(ea.qpos, eb.qpos)             # no episode end: nothing differs
+        oa, ra, da = ea.env_step(a, nz)                          # time-out: auto path resets in the same call
+    finally:
+        ea.set_auto_reset(0)
     ob, rb, db = eb.env_step(a, nz)                              # explicit path: terminal step ...
     assert da[0] == 1 and db[0] == 1 and ra[0] == rb[0] and abs(ra[0] + 10.0) < 0.2
     eb.reset_env(0)                                              # ... then jaco_reset(mask): reset kernel's work + forward pass
@@ -406,8 +406,10 @@ def test_auto_reset_forward_pass_survives_a_tier_hand_off(names, model_arrays, s
     a = np.zeros(7, np.float32); nz = np.full((1, 12), 0.25, np.float32)
     ea, eb = make(), make()
     ea.set_auto_reset(1)
-    oa, ra, da = ea.env_step(a, nz)
-    ea.set_auto_reset(0)
+    try:
+        oa, ra, da = ea.env_step(a, nz)
+    finally:
+        ea.set_auto_reset(0)
     ob, rb, db = eb.env_step(a, nz)
     assert da[0] == 1 and db[0] == 1 and ra[0] == rb[0]
     eb.reset_env(0); eb.flags[:] = 0
@@ -448,13 +450,10 @@ def test_pair_list_does_not_change_results(names, model_arrays):
     """Broadphase pair list (collision.h "Pair list"): the list pass runs the same exact test on a superset of the pairs that can
     pass it, so state, observation, contact / row / candidate counts must equal those of the all-pairs pass BIT FOR BIT -- over
     env steps with large actions (the list is rebuilt inside a step: markers jump, the arm sweeps several cm) and with the arm at rest."""
-    import ctypes
     nenv, fs = 6, 25
     runs, passes = [], {}
     for on in (1, 0):
         e = EmuJacoEnv(nenv=nenv, frame_skip=fs)
-        e.L.emu_set_pair_list.argtypes = [ctypes.c_int]
-        e.L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; e.L.emu_get_counter.restype = ctypes.c_long
         e.L.emu_set_pair_list(on)
         e.L.emu_get_counter(0, 1); e.L.emu_get_counter(1, 1)
         try:

@@ -272,7 +272,6 @@ def test_separating_direction_cache_does_not_change_results(model_arrays, names)
     """Hull narrowphase with the per-pair separating-direction cache (collision.h): only provable misses are skipped, so a free run of
     the in-hand grasp scenario (fingers closing onto the object: hull hits, near misses that come and go) must give the same state,
     contact / row counts and sensor values BIT FOR BIT with the cache on and off -- while spending fewer support queries."""
-    import ctypes
     from mujoco_jaco_amd.modelc import rot
     o = Oracle()
     q = model_arrays["qpos0"].copy()
@@ -284,8 +283,6 @@ def test_separating_direction_cache_does_not_change_results(model_arrays, names)
     runs, queries = [], []
     for on in (1, 0):
         e = EmuEnv()
-        e.L.emu_set_sep_cache.argtypes = [ctypes.c_int]
-        e.L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; e.L.emu_get_counter.restype = ctypes.c_long
         e.L.emu_set_sep_cache(on)
         try:
             e.qpos[0] = q
@@ -360,12 +357,9 @@ def test_pair_list_on_the_d30_build_keeps_floor_contacts():
     objects' floor contacts.  (A chunk's plane flag was once read from the default layout's bit 22 = bit 3 of g2 here; this scene alone does not
     expose that -- chunk 0 also holds entries with that bit set -- the fix is the shared expression JPL_KBITS + 2 JPL_GBITS; the test is the d30
     build's on / off regression for both execution options.)"""
-    import ctypes
     runs = []
     for pl_on, sc_on in ((1, 1), (0, 1), (1, 0)):
         e = EmuEnv("jaco2_dual_torque")
-        e.L.emu_set_pair_list.argtypes = [ctypes.c_int]; e.L.emu_set_sep_cache.argtypes = [ctypes.c_int]
-        e.L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; e.L.emu_get_counter.restype = ctypes.c_long
         e.L.emu_set_pair_list(pl_on); e.L.emu_set_sep_cache(sc_on)
         e.L.emu_get_counter(0, 1); e.L.emu_get_counter(1, 1)
         try:
@@ -430,13 +424,11 @@ def test_newton_look_ahead_stop_saves_hessian_builds_and_keeps_the_solution(mode
     off -- is below MuJoCo's tolerance (physics_kernel.h newton_next_round_is_idle).  Against the build without the rule
     (-DJACO_NEWTON_LOOKAHEAD=0, on demand): fewer matrix-core Hessian builds per constrained solve, and the solution (qacc, compared with the fp64
     oracle's after every synchronised substep of the contact workload) is as close to the oracle's as before."""
-    import ctypes
     res = {}
     q = workload.reset_states(model_arrays["qpos0"], 6, seed=31)
     c = workload.random_ctrl(6, seed=32, scale=0.2)
     for layout in ("", "_nolook"):
         o = Oracle(); e = EmuEnv(layout=layout)
-        e.L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; e.L.emu_get_counter.restype = ctypes.c_long
         e.L.emu_get_counter(8, 1); e.L.emu_get_counter(9, 1)
         errs, solves = [], 0
         for k in range(6):
@@ -460,7 +452,6 @@ def test_mpr_pairs_do_not_change_results(model_arrays, names):
     arithmetic, its order and the tie-breaking are those of the one-pair routine, so a free run of the in-hand grasp scenario (fingers closing onto
     the object: ~10 hull pairs per substep, hits, near misses, cached separating directions coming and going) must give the same state, contact /
     row counts and sensor values BIT FOR BIT with the option on and off -- and the two-pair routine must really have run."""
-    import ctypes
     from mujoco_jaco_amd.modelc import rot
     o = Oracle()
     q = model_arrays["qpos0"].copy()
@@ -473,8 +464,6 @@ def test_mpr_pairs_do_not_change_results(model_arrays, names):
         runs, passes, calls = [], [], []
         for on in (1, 0):
             e = EmuEnv(layout="_mprpairs")   # (the build option's own emulator library, made on demand)
-            e.L.emu_set_mpr_pairs.argtypes = [ctypes.c_int]; e.L.emu_set_sep_cache.argtypes = [ctypes.c_int]
-            e.L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; e.L.emu_get_counter.restype = ctypes.c_long
             e.L.emu_set_mpr_pairs(on); e.L.emu_set_sep_cache(cache)
             try:
                 e.qpos[0] = q
