@@ -317,7 +317,7 @@ extern "C" int jaco_reset_state(JacoHandle* h, void* stream) {
 }
 
 #define JACO_PLACING_HOLD_SUBSTEPS 150   // reset_frame_skip (env_mujoco_util.py:114)
-struct EnvIO { int mode = 0; const float* action = nullptr; float* obs = nullptr; float* reward = nullptr; unsigned char* done = nullptr; const unsigned char* mask = nullptr;
+struct EnvIO { int mode = JM_CTRL; const float* action = nullptr; float* obs = nullptr; float* reward = nullptr; unsigned char* done = nullptr; const unsigned char* mask = nullptr;
                bool listed = false; };   // listed: h->order[0 .. order_ctl[67]) holds the envs of `mask` (written by jaco_reset_kernel): launch a small grid over that list
 
 // Launch order for the next env step: envs sorted by the cost of their previous step, most expensive first (32 buckets of
@@ -422,7 +422,7 @@ __global__ void jaco_drain_round2_kernel(int* ctl, int medium_grid, int heavy_gr
 static __device__ void jaco_queue_limits(const int* prev, int* ctl, int mode, int wm, int wh, int wg, int light_wgs) {
   // (the demand that counts is that of the last real step, not of a reset-time forward pass in between)
   for (int t = 0; t < 3; t++) {
-    if (prev[JQ_LASTMODE] <= 1) {
+    if (JM_REAL_STEP(prev[JQ_LASTMODE])) {
       // (what came by a second time -- handed down by the heavy drain, overflowed again after that -- is not new demand)
       ctl[JQ_PREV_COUNT + t] = (t < 2 && prev[JQ_ROUND1 + t] >= 0) ? prev[JQ_ROUND1 + t] : prev[JQ_COUNT + t];
       ctl[JQ_PREV_HINTED + t] = prev[JQ_HINTED + t];
@@ -513,12 +513,12 @@ __global__ void jaco_prepare_kernel(int* ctl, const int* prev_ctl, int* lists, i
 }
 
 static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t st, float* dbg, int dbg_env, const EnvIO& io = EnvIO()) {
-  if ((!ctrl && io.mode == 0) || nsub <= 0) { h->err = "jaco_physics_step: bad arguments"; return JACO_EINVAL; }
+  if ((!ctrl && io.mode == JM_CTRL) || nsub <= 0) { h->err = "jaco_physics_step: bad arguments"; return JACO_EINVAL; }
 #if JNV > 21
   // the two-arm layout serves the sim-interface tier (jaco_physics_step and the state accessors).  The env tier is one arm's task layer; the
   // reference's own env loop is single-robot too (_step_simulation stacks ONE gripper command onto the controller output,
   // env_mujoco_util.py:73-83: 15 values for the dual model's 18 controls)
-  if (io.mode != 0) { h->err = "this build of the library (two-arm layout) steps models at the ctrl level only: jaco_physics_step / jaco_get_state / jaco_set_state"; return JACO_EINVAL; }
+  if (io.mode != JM_CTRL) { h->err = "this build of the library (two-arm layout) steps models at the ctrl level only: jaco_physics_step / jaco_get_state / jaco_set_state"; return JACO_EINVAL; }
 #endif
   ENTER(h);
   JacoStepArgs A{};
@@ -542,14 +542,14 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   A.env_mode = io.mode; A.task_id = h->task; A.nact = (h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PUSHING) ? 6 : 7; A.seed = h->seed;
   A.task = h->task_rows; A.cache = h->cache; A.action = io.action; A.noise = h->noise; A.obs_mode = h->obs_mode; A.subgoal = h->subgoal; A.obs = io.obs; A.reward = io.reward; A.done = io.done; A.terminal = h->terminal; A.terminal_obs = h->terminal_obs; A.goal_buf = h->goal_buf; A.goal_n = h->goal_n; A.goal_stride = h->goal_stride; A.mask = io.mask; A.marker = h->marker;
   A.cost = h->cost;
-  if (io.mode <= 1 && h->con_rec) { A.con_rec = h->con_rec; A.con_n = h->con_n; A.con_cap = h->con_cap; }   // (forward passes and resets record nothing)
+  if (JM_REAL_STEP(io.mode) && h->con_rec) { A.con_rec = h->con_rec; A.con_n = h->con_n; A.con_cap = h->con_cap; }   // (forward passes and resets record nothing)
   // auto-reset folds draws + sim.forward() + observation into the step wave: the tasks whose reset is nothing more (placing holds the
   // object for 150 substeps, grasping pre-reaches: those keep the explicit jaco_reset)
-  A.auto_reset = h->auto_reset && io.mode == 1 && (h->task == JACO_TASK_PICKING || h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PICKANDPLACE || h->task == JACO_TASK_PUSHING);
+  A.auto_reset = h->auto_reset && io.mode == JM_STEP && (h->task == JACO_TASK_PICKING || h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PICKANDPLACE || h->task == JACO_TASK_PUSHING);
   A.qpos0 = h->qpos0_dev;
-  const bool reorder = io.mode == 1 && h->schedule && nsub >= h->min_nsub_order && h->num_envs >= 4096;
+  const bool reorder = io.mode == JM_STEP && h->schedule && nsub >= h->min_nsub_order && h->num_envs >= 4096;
   std::pair<hipEvent_t, hipEvent_t>*ev = nullptr, *kev = nullptr;
-  if (h->timing && io.mode <= 1) {   // (the masked forward passes of resets are not the kernel being measured)
+  if (h->timing && JM_REAL_STEP(io.mode)) {   // (the masked forward passes of resets are not the kernel being measured)
     if (h->events_used == h->events.size()) {
       hipEvent_t a, b;
       HIPCHK(h, hipEventCreate(&a));
@@ -565,7 +565,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   }
   // Contact-free step (option disable_contact, or a model without a collidable pair): its own lean kernel, alone -- no capacity can
   // overflow (at most one limit row per joint), so there is nothing to route, order, serve or drain.
-  if (h->arm_kernel && (h->disable_contact || h->model_host.npair == 0) && io.mode <= 1) {
+  if (h->arm_kernel && (h->disable_contact || h->model_host.npair == 0) && JM_REAL_STEP(io.mode)) {
     A.disable_contact = 1; A.hint = nullptr;
     if (kev) HIPCHK(h, hipEventRecord(kev->first, st));
     JLAUNCHK(h, JK_ARM, (unsigned)h->num_envs, st, A);
@@ -585,8 +585,9 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   // frees and would otherwise starve behind the light grid, leaving serial tails of several ms per env step).  The drains that
   // follow in stream order serve whatever the workers did not (all of it when concurrency is off: full grids, which is also
   // what carries the load when most envs overflow).
-  // (the contact-free path above, take_action and terminal_inspection use no queue: they leave the buffers as they are)
-  const bool routes = A.hint && io.mode <= 1 && !(io.listed && io.mask);
+  // (the contact-free path above uses no queue and leaves the buffers as they are.  take_action and terminal_inspection alone prepare this
+  // launch's buffer like any launch that does not route -- which flips qsel -- and return before the drains: nothing of theirs is queued)
+  const bool routes = A.hint && JM_REAL_STEP(io.mode) && !(io.listed && io.mask);
   if (!h->q_ready || !routes) {   // this launch's buffer has not been prepared by the launch before
     JLAUNCH(h, jaco_prepare_kernel, dim3((unsigned)((6 * h->num_envs + 255) / 256)), dim3(256), 0, st, qctl, qctl_other, qlist, h->num_envs, h->workers, h->workers_heavy, h->workers_huge, h->order_ctl, io.mode, (int)light_grid);
     HIPCHK(h, hipGetLastError());
@@ -603,7 +604,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   // start its 10 ms of work when everything else is done.  Launched before the ordering pass, they have three small kernels of
   // head start on the light grid (and the event record below adds a barrier packet in front of it).
   // (short steps too: at frame_skip 4 the serial drains behind the light grid were 1.2 ms of a 5.1 ms step, profiles/r03_trace_fs4.txt)
-  const bool conc = h->concurrent && io.mode == 1 && nsub >= h->min_nsub_sched && h->num_envs >= 4096;
+  const bool conc = h->concurrent && io.mode == JM_STEP && nsub >= h->min_nsub_sched && h->num_envs >= 4096;
   if (conc) {
     HIPCHK(h, hipEventRecord(h->ev_fork, st));
     for (int t = 2; t >= 0; t--) HIPCHK(h, hipStreamWaitEvent(h->side[t], h->ev_fork, 0));
@@ -622,7 +623,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   }
   if (conc) HIPCHK(h, hipEventRecord(h->ev_pre, st));
   if (kev) HIPCHK(h, hipEventRecord(kev->first, st));
-  if (A.nslots || io.mode >= 2) JLAUNCHK(h, JK_LISTED, light_grid, st, A);   // (resets: forward passes, placing hold)
+  if (A.nslots || !JM_REAL_STEP(io.mode)) JLAUNCHK(h, JK_LISTED, light_grid, st, A);   // (resets, take_action / terminal_inspection alone)
   else JLAUNCHK(h, JK_STEP, light_grid, st, A);
   if (kev) HIPCHK(h, hipEventRecord(kev->second, st));
   HIPCHK(h, hipGetLastError());
@@ -630,10 +631,10 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   const unsigned ne = (unsigned)h->num_envs;
   // drain grids = the tiers' full occupancy on 256 CUs (8 / 4 / 2 workgroups per CU by LDS and registers); slots are claimed one at a time
   unsigned mg = ne < 2048 ? ne : 2048, hg = ne < JACO_HEAVY_GRID ? ne : JACO_HEAVY_GRID, gg = ne < 512 ? ne : 512;
-  if (io.mode == 2) { mg = mg < 64 ? mg : 64; hg = hg < 64 ? hg : 64; gg = gg < 256 ? gg : 256; }   // (reset-time forward passes: overflows of the light tier go straight to the last one)
-  if (io.mode == 4 || io.mode == 5) { if (ev) HIPCHK(h, hipEventRecord(ev->second, st)); return JACO_OK; }   // take_action / terminal_inspection run no substep: nothing can overflow
-  if (io.mode != 2) JLAUNCHK(h, JK_MEDIUM_DRAIN, mg, st, A);   // (mode 2 queues for the last tier only)
-  if (h->handdown && io.mode == 1 && nsub >= JACO_HANDDOWN_MIN) {   // (a hand-down needs JACO_HANDDOWN_MIN substeps left to pay: shorter steps never hand down, and skip the round)
+  if (io.mode == JM_FORWARD) { mg = mg < 64 ? mg : 64; hg = hg < 64 ? hg : 64; gg = gg < 256 ? gg : 256; }   // (reset-time forward passes: overflows of the light tier go straight to the last one)
+  if (JM_NO_SUBSTEP(io.mode)) { if (ev) HIPCHK(h, hipEventRecord(ev->second, st)); return JACO_OK; }   // take_action / terminal_inspection run no substep: nothing can overflow
+  if (io.mode != JM_FORWARD) JLAUNCHK(h, JK_MEDIUM_DRAIN, mg, st, A);   // (a forward pass queues for the last tier only)
+  if (h->handdown && io.mode == JM_STEP && nsub >= JACO_HANDDOWN_MIN) {   // (a hand-down needs JACO_HANDDOWN_MIN substeps left to pay: shorter steps never hand down, and skip the round)
     // the heavy tier holds 4 envs per CU: an env that needed it for a few substeps is passed back down to a second medium drain
     // (8 per CU) rather than kept there for the rest of its step; what overflows again is served by a second, final heavy drain
     A.handdown = 1;
@@ -642,7 +643,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
     JLAUNCH(h, jaco_drain_round2_kernel, dim3(1), dim3(1), 0, st, qctl, (int)mg, (int)hg);
     JLAUNCHK(h, JK_MEDIUM_DRAIN, mg, st, A);
   }
-  if (io.mode != 2) JLAUNCHK(h, JK_HEAVY_DRAIN, hg, st, A);
+  if (io.mode != JM_FORWARD) JLAUNCHK(h, JK_HEAVY_DRAIN, hg, st, A);
   JLAUNCHK(h, JK_HUGE_DRAIN, gg, st, A);
   HIPCHK(h, hipGetLastError());
   if (ev) HIPCHK(h, hipEventRecord(ev->second, st));
@@ -675,20 +676,20 @@ __global__ void jaco_reset_kernel(JacoResetArgs R) {
 
 extern "C" int jaco_forward(JacoHandle* h, float* obs_dev, void* stream) {
   if (!h || !obs_dev) return JACO_EINVAL;
-  EnvIO io; io.mode = 2; io.obs = obs_dev;
+  EnvIO io; io.mode = JM_FORWARD; io.obs = obs_dev;
   return launch_step(h, nullptr, 1, (hipStream_t)stream, nullptr, -1, io);
 }
 extern "C" int jaco_placing_hold(JacoHandle* h, const uint8_t* mask_dev, int nsub, void* stream) {
   if (!h || nsub <= 0) return JACO_EINVAL;
   if (h->model_host.eeobj_body < 0 || h->model_host.nq < 23) { h->err = "jaco_placing_hold: the model has no EE_obj frame / object body"; return JACO_EINVAL; }
-  EnvIO hold; hold.mode = 3; hold.mask = mask_dev; hold.listed = h->reset_listed;
+  EnvIO hold; hold.mode = JM_HOLD; hold.mask = mask_dev; hold.listed = h->reset_listed;
   return launch_step(h, nullptr, nsub, (hipStream_t)stream, nullptr, -1, hold);
 }
 #define JACO_PREREACH_MAX_SUBSTEPS 4000   // cap of the grasping reset's two `while True` loops (typically ~600-1500 substeps at 0.4 m/s)
 extern "C" int jaco_grasping_prereach(JacoHandle* h, const uint8_t* mask_dev, int max_substeps, float* obs_dev, void* stream) {
   if (!h || !obs_dev || max_substeps <= 0) return JACO_EINVAL;
   if (h->model_host.obj_body < 0 || h->model_host.nq < 23) { h->err = "jaco_grasping_prereach: the model has no object body"; return JACO_EINVAL; }
-  EnvIO pre; pre.mode = 6; pre.mask = mask_dev; pre.obs = obs_dev; pre.listed = h->reset_listed;
+  EnvIO pre; pre.mode = JM_PREREACH; pre.mask = mask_dev; pre.obs = obs_dev; pre.listed = h->reset_listed;
   return launch_step(h, nullptr, max_substeps, (hipStream_t)stream, nullptr, -1, pre);
 }
 extern "C" int jaco_reset(JacoHandle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
@@ -712,23 +713,23 @@ extern "C" int jaco_reset(JacoHandle* h, const uint8_t* mask_dev, float* obs_dev
     return rc;
   }
   // sim.forward() + _get_observation for the reset envs (the others keep their observation row and controller cache)
-  EnvIO io; io.mode = 2; io.obs = obs_dev; io.mask = mask_dev; io.listed = h->reset_listed;
+  EnvIO io; io.mode = JM_FORWARD; io.obs = obs_dev; io.mask = mask_dev; io.listed = h->reset_listed;
   h->reset_listed = false;
   return launch_step(h, nullptr, 1, st, nullptr, -1, io);
 }
 extern "C" int jaco_step(JacoHandle* h, const float* action_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream) {
   if (!h || !action_dev || !obs_dev || !reward_dev || !done_dev) return JACO_EINVAL;
-  EnvIO io; io.mode = 1; io.action = action_dev; io.obs = obs_dev; io.reward = reward_dev; io.done = done_dev;
+  EnvIO io; io.mode = JM_STEP; io.action = action_dev; io.obs = obs_dev; io.reward = reward_dev; io.done = done_dev;
   return launch_step(h, nullptr, h->frame_skip, (hipStream_t)stream, nullptr, -1, io);
 }
 extern "C" int jaco_take_action(JacoHandle* h, const float* action_dev, void* stream) {
   if (!h || !action_dev) return JACO_EINVAL;
-  EnvIO io; io.mode = 4; io.action = action_dev;
+  EnvIO io; io.mode = JM_TAKE_ACTION; io.action = action_dev;
   return launch_step(h, nullptr, 1, (hipStream_t)stream, nullptr, -1, io);
 }
 extern "C" int jaco_terminal_inspection(JacoHandle* h, uint8_t* done_dev, float* bonus_dev, void* stream) {
   if (!h || !done_dev || !bonus_dev) return JACO_EINVAL;
-  EnvIO io; io.mode = 5; io.reward = bonus_dev; io.done = done_dev;
+  EnvIO io; io.mode = JM_TERMINAL; io.reward = bonus_dev; io.done = done_dev;
   return launch_step(h, nullptr, 1, (hipStream_t)stream, nullptr, -1, io);
 }
 extern "C" int jaco_set_noise(JacoHandle* h, const float* noise_dev) {

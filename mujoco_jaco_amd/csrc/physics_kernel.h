@@ -124,6 +124,21 @@ struct JacoContactRec {
 };
 #define JCONREC_WORDS 24
 
+// Launch modes (JacoStepArgs::env_mode, described there), and the rules the kernels and the host apply to them.  The rules are macros on
+// purpose: a function call, even a forceinline one, reaches the optimiser as a different instruction stream than the same test written in
+// place, and that alone moved the register allocation of several kernels (up to 4 bytes of scratch per lane); an expansion compiles to
+// exactly the code of the test it names.  A mode is never negative.
+enum JacoMode { JM_CTRL = 0, JM_STEP = 1, JM_FORWARD = 2, JM_HOLD = 3, JM_TAKE_ACTION = 4, JM_TERMINAL = 5, JM_PREREACH = 6 };
+// a real step (JM_CTRL, JM_STEP): the launches that integrate every env and feed the tiers' demand, launch-order cost and contact record
+#define JM_REAL_STEP(m) ((m) <= JM_STEP)
+// a reset-time launch over the envs of `mask` only (JM_FORWARD, JM_HOLD, JM_PREREACH): the others are not touched
+#define JM_MASKED(m) ((m) == JM_FORWARD || (m) == JM_HOLD || (m) == JM_PREREACH)
+// the substep reached so far (JT_SUB) and an interrupted substep's ctrl (JT_PENDING) live in the task row, so a bigger tier resumes from
+// there (JM_STEP, JM_HOLD, JM_PREREACH)
+#define JM_TASK_SUBSTEPS(m) ((m) == JM_STEP || (m) == JM_HOLD || (m) == JM_PREREACH)
+// task-layer work alone (JM_TAKE_ACTION, JM_TERMINAL): no substep runs, nothing can overflow a tier
+#define JM_NO_SUBSTEP(m) ((m) == JM_TAKE_ACTION || (m) == JM_TERMINAL)
+
 struct JacoStepArgs {
   const JacoModelDev* model;
   const float* hull;   // float4 per hull vertex
@@ -159,12 +174,13 @@ struct JacoStepArgs {
                        //    medium / light code itself for the rest of the step (first heavy drain only: a second medium drain follows it)
   int hint_mode;       // 1: an env's next step starts in the biggest tier this step really needed; 2: in the tier its last substep needed
   int no_tier_return;  // 1: an env handed to the heavy tier stays there for the rest of the launch (option "tier_return" = 0)
-  // env-level mode (jaco_step / jaco_reset): nsub = frame_skip
-  int env_mode;              // 0 ctrl-level, 1 env step, 2 forward only (reset: fill cache + observation),
-                             // 3 placing reset: nsub controlled substeps with the object pinned in the hand (env_mujoco_util.py:106-117)
-                             // 4 take_action only (env_mujoco.py:158-159), 5 terminal_inspection only (env_mujoco.py:144-150): no physics
-                             // 6 grasping reset: the two pre-reach loops (env_mujoco_util.py:123-170), at most nsub substeps, then the observation
-  const unsigned char* mask; // modes 2 and 3: envs to run (nullptr = all)
+  // launch mode (JacoMode): JM_CTRL ctrl level (jaco_physics_step); JM_STEP env step (jaco_step, nsub = frame_skip);
+  // JM_FORWARD forward pass only (jaco_forward / jaco_reset: fill cache + observation);
+  // JM_HOLD placing reset: nsub controlled substeps with the object pinned in the hand (env_mujoco_util.py:106-117);
+  // JM_TAKE_ACTION take_action only (env_mujoco.py:158-159), JM_TERMINAL terminal_inspection only (env_mujoco.py:144-150): no substep;
+  // JM_PREREACH grasping reset: the two pre-reach loops (env_mujoco_util.py:123-170), at most nsub substeps, then the observation
+  int env_mode;
+  const unsigned char* mask; // masked-reset modes (JM_MASKED): envs to run (nullptr = all)
   float* marker;             // [nenv][2][12] poses (position, rotation) of the "hand" / "subgoal_reach" markers, or nullptr = XML rest pose
   int task_id, nact;
   unsigned long long seed;
@@ -173,7 +189,7 @@ struct JacoStepArgs {
   const float* action;       // [nenv][nact]
   const float* noise;        // optional [nenv][12] sub-goal noise draws (6 for the marker, 6 for the observation), else RNG
   int obs_mode;              // 0: rule-based sub-goal in obs[17:23] (what main.py selects), 1: the reaching goal (rulebased_subgoal = False, env_mujoco_util.py:255-270)
-  int auto_reset;            // mode 1, option "auto_reset": an env whose step ends its episode is reset (draws of _reset + sim.forward() + first
+  int auto_reset;            // JM_STEP, option "auto_reset": an env whose step ends its episode is reset (draws of _reset + sim.forward() + first
                              // observation) by the wave that finished it, instead of by a separate masked jaco_reset launch chain
   const float* qpos0;        // [nq] reset pose (auto_reset)
   const float* goal_buf;     // auto_reset, optional: recorded reaching goals (jaco_set_init_buffer), [goal_n][goal_stride]
@@ -190,7 +206,7 @@ struct JacoStepArgs {
   unsigned long long* prof;  // diagnostic build only: [nenv][JPROF_N] cycle sums, else nullptr
   float* dbg;          // optional stage dump of env dbg_env (see JDBG_* offsets), else nullptr
   int dbg_env;
-  // contact record (jaco_set_contact_record), modes 0 / 1 only: the contacts of the last integrating substep of the launch, or nullptr = off
+  // contact record (jaco_set_contact_record), real steps (JM_REAL_STEP) only: the contacts of the last integrating substep of the launch, or nullptr = off
   JacoContactRec* con_rec;   // [nenv][con_cap]
   int* con_n;                // [nenv] the true contact count (may exceed con_cap: the records past it are dropped)
   int con_cap;
@@ -1880,7 +1896,7 @@ JDEV void hint_raise(const JacoStepArgs& A, int env, int tier, int lane) {
 
 // ---------------------------------------------------------------- the kernels
 // ---------------------------------------------------------------- contact record (jaco_set_contact_record)
-// What data.contact and mj_contactForce give after mj_step, for the last substep of a mode 0 / 1 launch, written by run_env's epilogue:
+// What data.contact and mj_contactForce give after mj_step, for the last substep of a real step (JM_REAL_STEP), written by run_env's epilogue:
 // lane = contact (the first `cap`), each lane sums its own contact's rows -- rows in the light tier's side buffer are read there, as
 // stage_touch does -- and writes the 96-byte record as six 16-byte stores; lane 0 writes the true count.  (In the epilogue rather than
 // next to the stage dump inside the substep loop: there it cost the light kernel 8 bytes of scratch per lane.)
@@ -1919,8 +1935,8 @@ static_assert(sizeof(JacoContactRec) == 4 * JCONREC_WORDS && JCONREC_WORDS % 4 =
 // One substep loop for one env; returns the number of substeps NOT done (light tier bail-out) or 0.
 // TIER: 0 light, 1 medium, 2 heavy, 3 huge.  Tiers below 3 stop at a capacity overflow (*why = 1) and leave the env to the next
 // tier; tiers above 0 can give the env back to the tier below once it would fit again (handback; *why = 2).
-// FULL = false: the instantiation of the step kernel proper (jaco_physics_kernel), which is only ever launched in modes 0 (ctrl level)
-// and 1 (env step): the reset-time modes (forward pass, placing hold, grasping pre-reach, take_action / terminal_inspection on their own)
+// FULL = false: the instantiation of the step kernel proper (jaco_physics_kernel), which is only ever launched for real steps (JM_CTRL,
+// JM_STEP): the other modes (forward pass, placing hold, grasping pre-reach, take_action / terminal_inspection on their own)
 // fold away at compile time and stay out of the hot kernel's code and register budget; their launches use jaco_physics_kernel_listed.
 template <class C, int TIER, bool FULL = true>
 JDEV int run_env(const JacoStepArgs& A_, JacoLDS<C>& s, int env, int nsub, int lane, bool handback = false, int* why = nullptr) {
@@ -1930,22 +1946,22 @@ JDEV int run_env(const JacoStepArgs& A_, JacoLDS<C>& s, int env, int nsub, int l
   bool bailed = false;
   const JacoModelDev* m = opaque_ptr(A.model);
   const int nq = m->nq, nv = m->nv, nu = m->nu, ns = m->nsensor;
-  if (FULL && (A.env_mode == 3 || A.env_mode == 2 || A.env_mode == 6) && A.mask && !A.mask[env]) return 0;   // masked reset: the other envs are not touched
+  if (FULL && JM_MASKED(A.env_mode) && A.mask && !A.mask[env]) return 0;   // masked reset: the other envs are not touched
   if (lane < nq) { s.qpos[lane] = A.qpos[(size_t)env * nq + lane]; s.qpos_lo[lane] = A.qpos_lo ? A.qpos_lo[(size_t)env * nq + lane] : 0.f; }
   if (lane < nv) { s.qvel[lane] = A.qvel[(size_t)env * nv + lane]; s.qacc_ws[lane] = A.qacc_ws[(size_t)env * nv + lane]; s.qvel_lo[lane] = A.qvel_lo ? A.qvel_lo[(size_t)env * nv + lane] : 0.f; }
   // ctrl-level launches read the caller's controls.  Env-level launches compute theirs (controller + gripper ramp, or the interrupted substep's
-  // from the task row); a forward pass alone (mode 2: sim.forward() after sim.reset(), which zeroes data.ctrl) runs on ZERO controls -- A.ctrl is
+  // from the task row); a forward pass alone (JM_FORWARD: sim.forward() after sim.reset(), which zeroes data.ctrl) runs on ZERO controls -- A.ctrl is
   // only a readable placeholder there (the qvel buffer: reading it made a reset's first touch reading depend on other envs' velocities;
   // found by the auto-reset bit-identity test in round 5, 1 env of 8 192 x 6 steps)
-  if (lane < nu) s.ctrl[lane] = A.env_mode == 0 ? A.ctrl[(size_t)env * nu + lane] : 0.f;
+  if (lane < nu) s.ctrl[lane] = A.env_mode == JM_CTRL ? A.ctrl[(size_t)env * nu + lane] : 0.f;
   stage_model(m, s, lane);
   if (lane == 0) { s.ncon = 0; s.nefc = 0; s.ncand = 0; s.nlimit = 0; s.nsphere = 0; s.nside = 0; s.nside_cand = 0; }   // (LDS is not zeroed between workgroups)
   unsigned flags = LIGHT ? 0u : JFLAG_HEAVY_TIER;
   float sens = 0.f;
   int iters = 0, left = 0, sub0 = 0, nls_last = 0, calm = 0;
   bool tier_used = false;   // this tier's extra capacity was really needed in at least one substep
-  const int emode = FULL ? A.env_mode : (A.env_mode != 0 ? 1 : 0);
-  if (emode == 4 || emode == 5) nsub = 0;   // take_action / terminal_inspection on their own: no substep runs
+  const int emode = FULL ? A.env_mode : (A.env_mode != JM_CTRL ? JM_STEP : JM_CTRL);
+  if (JM_NO_SUBSTEP(emode)) nsub = 0;
   // poses of the two task-layer markers: LDS copy for this launch (their geoms are re-posed every substep)
   if (lane < 24) s.mk[lane] = A.marker ? A.marker[(size_t)env * 24 + lane] : m->marker_rest[lane / 12][lane % 12];
   if (emode) {   // task row + the one-substep-stale quantities the controller reads (env_logic.h)
@@ -1957,20 +1973,20 @@ JDEV int run_env(const JacoStepArgs& A_, JacoLDS<C>& s, int env, int nsub, int l
     if (lane < 9) s.xmat[m->ee_body][lane] = CR[JC_EEMAT + lane];
   }
   wave_sync();
-  if (emode == 1 || emode == 4 || emode == 5) {
+  if (emode == JM_STEP || JM_NO_SUBSTEP(emode)) {
     if (s.task[JT_DONE] != 0.f) {   // finished (or quarantined) and not yet reset: frozen (no auto-reset); counters untouched
-      if (lane == 0 && emode != 4) { A.reward[env] = 0.f; A.done[env] = 1; }
+      if (lane == 0 && emode != JM_TAKE_ACTION) { A.reward[env] = 0.f; A.done[env] = 1; }
       return 0;
     }
   }
   bool fwd = false;   // auto-reset: this pass is the reset env's sim.forward() + observation (one substep's derived quantities, no integration)
-  if (emode == 1 && s.task[JT_FWD] != 0.f) {   // ... resumed in a bigger tier after the forward pass overflowed the tier below
+  if (emode == JM_STEP && s.task[JT_FWD] != 0.f) {   // ... resumed in a bigger tier after the forward pass overflowed the tier below
     fwd = true; nsub = 1;
     if (lane < nu) s.ctrl[lane] = 0.f;
     if (lane == 0) { s.task[JT_SUB] = 0.f; s.task[JT_PENDING] = 0.f; }
     wave_sync();
   }
-  if ((emode == 1 && !fwd) || emode == 4) {
+  if ((emode == JM_STEP && !fwd) || emode == JM_TAKE_ACTION) {
     sub0 = wave_uniform_i((int)s.task[JT_SUB]);
     // (a step that overflowed this tier in its very first substep comes back with JT_SUB = 0 and the interrupted substep pending:
     // its action has been taken already -- taking it again would add the gripper increment twice and shift the draw counter)
@@ -2016,8 +2032,8 @@ JDEV int run_env(const JacoStepArgs& A_, JacoLDS<C>& s, int env, int nsub, int l
     osc_target_quat(s, lane);
     wave_sync();
   }
-  float pinv = 0.f;   // mode 3, lanes 9..15: the pinned object pose
-  if (emode == 3) {
+  float pinv = 0.f;   // JM_HOLD, lanes 9..15: the pinned object pose
+  if (emode == JM_HOLD) {
     // placing reset (env_mujoco_util.py:106-117): the object goes to the grasp frame EE_obj, 4 cm back along its x axis, and
     // is re-pinned there (zero velocity for every free body) after each of the nsub substeps, while the controller
     // holds the EE at its reset pose and the finger servos close onto the object (gripper command 0.6).
@@ -2051,7 +2067,7 @@ JDEV int run_env(const JacoStepArgs& A_, JacoLDS<C>& s, int env, int nsub, int l
     osc_target_quat(s, lane);
     wave_sync();
   }
-  if (emode == 6) {
+  if (emode == JM_PREREACH) {
     // grasping reset (env_mujoco_util.py:123-170): EE target = [object goal, orientation looking along EE -> object] (float16 angles,
     // yaw drawn), then loop 1: { stop_obj (free-body velocities zeroed, sim.forward), controller + sim.step } until the EE is within
     // 0.2 m of the object goal (the target then becomes the EE's own position) or its orientation within pi/6 of the sampled reaching
@@ -2100,23 +2116,23 @@ again:
     // instructions each; the kernel's remaining spills (156 B) all sit inside the MPR routine.
     lane = wave_opaque_i(lane);
     bool held_pending = false;
-    const int phase = emode == 6 ? wave_uniform_i((int)s.task[JT_PHASE]) : 0;
-    if ((emode == 3 || emode == 6) && s.task[JT_PENDING] != 0.f) {   // resume of an interrupted held substep: its ctrl was saved
+    const int phase = emode == JM_PREREACH ? wave_uniform_i((int)s.task[JT_PHASE]) : 0;
+    if ((emode == JM_HOLD || emode == JM_PREREACH) && s.task[JT_PENDING] != 0.f) {   // resume of an interrupted held substep: its ctrl was saved
       if (lane < nu) s.ctrl[lane] = s.task[JT_CTRL + lane];
       wave_sync();
       if (lane == 0) s.task[JT_PENDING] = 0.f;
       held_pending = true;
     }
-    if (emode == 6 && phase == 2 && !held_pending) {   // _step_simulation() with what mjData holds from the previous sim.step (one substep stale)
+    if (emode == JM_PREREACH && phase == 2 && !held_pending) {   // _step_simulation() with what mjData holds from the previous sim.step (one substep stale)
       stage_osc(m, s, lane, flags);
       if (lane >= 6 && lane < nu) s.ctrl[lane] = 0.6f;
       wave_sync();
     }
-    if (emode == 6 && phase == 1 && !held_pending) {   // stop_obj (mujoco.py:239-246): free-body velocities zeroed before the forward pass
+    if (emode == JM_PREREACH && phase == 1 && !held_pending) {   // stop_obj (mujoco.py:239-246): free-body velocities zeroed before the forward pass
       if (lane >= 9 && lane < nv) { s.qvel[lane] = 0.f; s.qvel_lo[lane] = 0.f; }
       wave_sync();
     }
-    if (emode == 1 && !fwd) {
+    if (emode == JM_STEP && !fwd) {
       if (s.task[JT_PENDING] != 0.f) {   // resume of a substep interrupted by the light tier: its ctrl was saved
         if (lane < nu) s.ctrl[lane] = s.task[JT_CTRL + lane];
         wave_sync();
@@ -2147,7 +2163,7 @@ again:
     wave_sync();
     stage_mass_bias(m, s, lane, pf);
     wave_sync();
-    if ((emode == 3 || (emode == 6 && phase == 1)) && !held_pending) {   // the substep follows a sim.forward(): the controller sees *this* state's M, J, bias
+    if ((emode == JM_HOLD || (emode == JM_PREREACH && phase == 1)) && !held_pending) {   // the substep follows a sim.forward(): the controller sees *this* state's M, J, bias
       stage_osc(m, s, lane, flags);
       if (lane >= 6 && lane < nu) s.ctrl[lane] = 0.6f;
       wave_sync();
@@ -2187,7 +2203,7 @@ again:
       left = nsub - sub;
       bailed = true;
       flags |= (cflags & 7u) << (JFLAG_BAIL_CAUSE_SHIFT + 3 * TIER);   // informational: which capacity of which tier sent the env on
-      if (emode == 1 || emode == 3 || emode == 6) {
+      if (JM_TASK_SUBSTEPS(emode)) {
         if (lane < nu) s.task[JT_CTRL + lane] = s.ctrl[lane];
         if (lane == 0) { s.task[JT_PENDING] = 1.f; s.task[JT_SUB] = (float)sub; }
         wave_sync();
@@ -2259,7 +2275,7 @@ again:
       if (lane < m->nsensor) D[JDBG_SENS + lane] = sens;
     }
     wave_sync();
-    if (emode == 2 || fwd) break;   // sim.forward(): derived quantities only, no integration
+    if (emode == JM_FORWARD || fwd) break;   // sim.forward(): derived quantities only, no integration
     if (lane < nv) {
       float v;
       if (m->compensated) {   // qvel += h qacc on the compensated pair
@@ -2302,12 +2318,12 @@ again:
       if (pv == 123.456f) s.smooth[40] = pv;
     }
 #endif
-    if (emode == 3) {   // set_obj_xyz (mujoco.py:217-227): object back to the pinned pose, all free-body velocities zeroed
+    if (emode == JM_HOLD) {   // set_obj_xyz (mujoco.py:217-227): object back to the pinned pose, all free-body velocities zeroed
       if (lane >= 9 && lane < 16) { s.qpos[lane] = pinv; s.qpos_lo[lane] = 0.f; }
       if (lane >= 9 && lane < nv) { s.qvel[lane] = 0.f; s.qvel_lo[lane] = 0.f; }
       wave_sync();
     }
-    if (emode == 6) {   // the loops' exit tests, on the poses of this substep's forward pass (what mjData holds after sim.step)
+    if (emode == JM_PREREACH) {   // the loops' exit tests, on the poses of this substep's forward pass (what mjData holds after sim.step)
       v3 pe; m3 Re;
       ee_frame(m, s, &pe, &Re);
       const v3 og = ld3(s.task + JT_OBJGOAL);
@@ -2333,25 +2349,25 @@ again:
     JSTAMP(8);
     // heavy tier: the burst that overflowed the light capacities is over (two substeps in a row would have fitted): give
     // the env back to the light code for the rest of the step (the caller alternates the two tiers)
-    if (!LIGHT && handback && calm >= 2 && sub + 1 < nsub && emode != 2) {
+    if (!LIGHT && handback && calm >= 2 && sub + 1 < nsub && emode != JM_FORWARD) {
       left = nsub - (sub + 1);
       flags |= JFLAG_TIER_RETURN;
-      if (emode == 1 || emode == 3 || emode == 6) { if (lane == 0) { s.task[JT_PENDING] = 0.f; s.task[JT_SUB] = (float)(sub + 1); } wave_sync(); }
+      if (JM_TASK_SUBSTEPS(emode)) { if (lane == 0) { s.task[JT_PENDING] = 0.f; s.task[JT_SUB] = (float)(sub + 1); } wave_sync(); }
       break;
     }
   }
   Ap = args_view(A_);   // (the epilogue reads the argument block afresh: nothing of it was carried through the substep loop)
   // contact record: the contacts of the substep this call ended with, still in LDS (Euler and the position update touch neither the contact
   // list nor the row forces).  Not of a forward pass, a reset or the auto-reset's forward pass (fwd); nothing when the env was handed on.
-  if (A.con_rec && left == 0 && !fwd && emode <= 1 && nsub > sub0) stage_record(m, s, A.con_rec, A.con_n, A.con_cap, env, lane);
+  if (A.con_rec && left == 0 && !fwd && JM_REAL_STEP(emode) && nsub > sub0) stage_record(m, s, A.con_rec, A.con_n, A.con_cap, env, lane);
   bool reset_now = false, term_now = false;
   // Write-through stores for everything another workgroup may read or REWRITE before this launch set is over: an env that is handed over
   // (bailed), and -- option auto_reset -- every normal step's outputs, because a step that ends its episode is followed by the in-kernel
   // reset, whose forward pass may overflow the tier and be finished by a resident worker on another XCD: that workgroup rewrites the
   // observation, sensor, cache and state rows, and two XCDs holding dirty copies of one line write back in an undefined order (the
   // GPU determinism test of the policy-driven regime caught this as one env in 8 192 differing from run to run).
-  const bool wt = bailed || (emode == 1 && A.auto_reset != 0 && !fwd);
-  if (emode != 2) {
+  const bool wt = bailed || (emode == JM_STEP && A.auto_reset != 0 && !fwd);
+  if (emode != JM_FORWARD) {
     if (wt) {   // handed over to another workgroup (possibly on another XCD): write-through stores
       if (lane < nq) { st_wt(&A.qpos[(size_t)env * nq + lane], s.qpos[lane]); if (A.qpos_lo) st_wt(&A.qpos_lo[(size_t)env * nq + lane], s.qpos_lo[lane]); }
       if (lane < nv) { st_wt(&A.qvel[(size_t)env * nv + lane], s.qvel[lane]); st_wt(&A.qacc_ws[(size_t)env * nv + lane], s.qacc_ws[lane]); if (A.qvel_lo) st_wt(&A.qvel_lo[(size_t)env * nv + lane], s.qvel_lo[lane]); }
@@ -2360,11 +2376,11 @@ again:
       if (lane < nv) { A.qvel[(size_t)env * nv + lane] = s.qvel[lane]; A.qacc_ws[(size_t)env * nv + lane] = s.qacc_ws[lane]; if (A.qvel_lo) A.qvel_lo[(size_t)env * nv + lane] = s.qvel_lo[lane]; }
     }
   }
-  if (left == 0 && lane < ns && A.sensordata && (emode < 4 || emode == 6)) { if (wt) st_wt(&A.sensordata[(size_t)env * ns + lane], sens); else A.sensordata[(size_t)env * ns + lane] = sens; }
-  if (emode == 6 && left == 0 && s.task[JT_PHASE] < 3.f) flags |= JFLAG_PREREACH_CAP;
-  if (emode == 5) sens = (lane < ns && A.sensordata) ? A.sensordata[(size_t)env * ns + lane] : 0.f;   // touch of the last forward pass
+  if (left == 0 && lane < ns && A.sensordata && (emode < JM_TAKE_ACTION || emode == JM_PREREACH)) { if (wt) st_wt(&A.sensordata[(size_t)env * ns + lane], sens); else A.sensordata[(size_t)env * ns + lane] = sens; }
+  if (emode == JM_PREREACH && left == 0 && s.task[JT_PHASE] < 3.f) flags |= JFLAG_PREREACH_CAP;
+  if (emode == JM_TERMINAL) sens = (lane < ns && A.sensordata) ? A.sensordata[(size_t)env * ns + lane] : 0.f;   // touch of the last forward pass
   if (emode) {
-    if ((left == 0 && emode != 3 && (emode < 4 || emode == 6)) || (!LIGHT && left > 0 && !bailed && (emode == 1 || emode == 6))) {
+    if ((left == 0 && emode != JM_HOLD && (emode < JM_TAKE_ACTION || emode == JM_PREREACH)) || (!LIGHT && left > 0 && !bailed && (emode == JM_STEP || emode == JM_PREREACH))) {
       // what the controller reads one substep late, for the next launch -- or, on a heavy -> light hand-back in the middle
       // of a step, for the light code's next substep
       float* CW = A.cache + (size_t)env * JCACHE_N;
@@ -2381,7 +2397,7 @@ again:
         if (lane < 9) CW[JC_EEMAT + lane] = s.xmat[m->ee_body][lane];
       }
     }
-    if (left == 0 && emode != 3 && emode != 4) {
+    if (left == 0 && emode != JM_HOLD && emode != JM_TAKE_ACTION) {
       // observation, reward, termination from the poses / sensors of the last forward pass (one substep stale, as in
       // the reference) -- make_observation, _get_reward, terminal_inspection (env_mujoco.py:122-126)
       int ob = m->obj_body >= 0 ? m->obj_body : 0;
@@ -2401,8 +2417,8 @@ again:
       int succ = 0;
       bool done = false;
       const float PI = 3.14159265358979323846f;
-      if ((emode == 1 && !fwd) || emode == 5) {
-        if (emode == 1) rew = A.task_id == JTASK_PICKING ? reward_picking(pe, eul, obj, touch)
+      if ((emode == JM_STEP && !fwd) || emode == JM_TERMINAL) {
+        if (emode == JM_STEP) rew = A.task_id == JTASK_PICKING ? reward_picking(pe, eul, obj, touch)
                             : (A.task_id == JTASK_REACHING ? reward_reaching(pe, eul, s.task + JT_REACHGOAL, ld3(m->base_pos))
                             : (A.task_id == JTASK_GRASPING ? reward_picking(pe, eul, obj, touch, 0.05f) : 0.f));   // (placing, pickAndplace: 0 in the reference)
         float trow[4] = {0.f, s.task[JT_STEPS], s.task[JT_EPISODES], 0.f};
@@ -2421,12 +2437,12 @@ again:
           A.done[env] = done ? 1 : 0;
           if (done && A.terminal) { A.terminal[2 * (size_t)env] = (float)succ; A.terminal[2 * (size_t)env + 1] = wb; }   // (survives the in-kernel reset)
         }
-        term_now = emode == 1 && wave_ballot(done) != 0ull;
+        term_now = emode == JM_STEP && wave_ballot(done) != 0ull;
         reset_now = term_now && A.auto_reset != 0;
       }
       if (fwd && lane == 0) { s.task[JT_FWD] = 0.f; s.task[JT_SUB] = 0.f; s.task[JT_PENDING] = 0.f; }
-      if (lane == 0 && emode != 5 && A.obs_mode == 0) s.task[JT_RNG] = rng_slot(cnt + 6u);
-      if (lane < 26 && emode != 5) {
+      if (lane == 0 && emode != JM_TERMINAL && A.obs_mode == 0) s.task[JT_RNG] = rng_slot(cnt + 6u);
+      if (lane < 26 && emode != JM_TERMINAL) {
         float o;
         if (lane == 0) o = (float)touch;
         else if (lane < 4) o = lane == 1 ? pe.x : (lane == 2 ? pe.y : pe.z);
@@ -2443,7 +2459,7 @@ again:
         if (term_now && A.terminal_obs) A.terminal_obs[(size_t)env * 26 + lane] = o;   // latched with (success, wb) by every terminal step, whoever resets the env (what the learner's value bootstrap wants after a time-out)
       }
     }
-    if (left == 0 && (emode == 3 || emode == 6) && lane == 0) { s.task[JT_SUB] = 0.f; s.task[JT_PENDING] = 0.f; }
+    if (left == 0 && (emode == JM_HOLD || emode == JM_PREREACH) && lane == 0) { s.task[JT_SUB] = 0.f; s.task[JT_PENDING] = 0.f; }
     wave_sync();
     if (lane < JTASK_N) { if (wt) st_wt(&A.task[(size_t)env * JTASK_N + lane], s.task[lane]); else A.task[(size_t)env * JTASK_N + lane] = s.task[lane]; }
   }
@@ -2515,26 +2531,26 @@ JDEV void light_grid(const JacoStepArgs& A, JacoLDS<C>& s) {
   const int env = A.order ? A.order[slot] : slot;
   // (envs whose previous step ended in a bigger tier were queued there before the launch: not this grid's, and not counted in light_left)
   if (A.routed_mark && A.routed_mark[env] == A.launch_id) return;
-  const bool masked_out = FULL && (A.env_mode == 2 || A.env_mode == 3 || A.env_mode == 6) && A.mask && !A.mask[env];
+  const bool masked_out = FULL && JM_MASKED(A.env_mode) && A.mask && !A.mask[env];
   int left = 0;
   if (!masked_out) {
-    if (FULL && A.hint && (A.env_mode == 2 || A.env_mode == 3 || A.env_mode == 6) && lane == 0) st_wt_i(&A.hint[env], 0);   // a reset env starts from scratch (its forward pass may raise it again)
+    if (FULL && A.hint && JM_MASKED(A.env_mode) && lane == 0) st_wt_i(&A.hint[env], 0);   // a reset env starts from scratch (its forward pass may raise it again)
     const unsigned long long t_start = wave_clock();
     left = run_env<C, 0, FULL>(A, s, env, A.nsub, lane);
     // (only real steps record their cost: the masked forward pass of a reset must not wipe the launch-order heuristic's input)
-    if (lane == 0 && A.cost && A.env_mode <= 1) { unsigned c = (unsigned)((wave_clock() - t_start) >> 4); if (left > 0) st_wt_u(&A.cost[env], c); else A.cost[env] = c; }
+    if (lane == 0 && A.cost && JM_REAL_STEP(A.env_mode)) { unsigned c = (unsigned)((wave_clock() - t_start) >> 4); if (left > 0) st_wt_u(&A.cost[env], c); else A.cost[env] = c; }
     // hand-off: the env's state went to memory with write-through stores (run_env); once they are acknowledged the env
     // is appended to the medium tier's queue.  Its workgroups run concurrently (jaco_env.hip) and poll the queue.
     // (a reset's forward pass goes straight to the last tier: one more launch in the chain instead of three, each of which would
     // redo the narrowphase of a hand-inside-the-pedestal pose up to its own capacity)
-    if (left > 0) queue_push(A, (FULL && A.env_mode == 2) ? 2 : 0, env, left, lane);
+    if (left > 0) queue_push(A, (FULL && A.env_mode == JM_FORWARD) ? 2 : 0, env, left, lane);
   }
   wave_sync();
   }
   if (lane == 0 && A.light_left) jaco_atomic_dec(A.light_left, false);
 }
 #if JACO_TU_HAS(0)
-__global__ __launch_bounds__(64, JACO_LIGHT_WAVES) void jaco_physics_kernel(JacoStepArgs A) {   // modes 0 and 1 only
+__global__ __launch_bounds__(64, JACO_LIGHT_WAVES) void jaco_physics_kernel(JacoStepArgs A) {   // real steps only (JM_REAL_STEP)
   __shared__ JacoLDS<JacoLight> s;
   JEMU_POISON(s);
   light_grid<false>(A, s);
@@ -2549,7 +2565,7 @@ __global__ __launch_bounds__(64, JACO_LIGHT_WAVES) void jaco_physics_kernel_list
   light_grid<true>(A, s);
 }
 #endif
-// The contact-free instantiation (modes 0 and 1): arm-only models / option disable_contact.  No collision, contact-row or touch code, LDS
+// The contact-free instantiation (real steps): arm-only models / option disable_contact.  No collision, contact-row or touch code, LDS
 // without the geom, candidate and contact arrays; 128 registers: BASELINE config 2's 4 096 envs are resident at once (16 per CU).  Nothing
 // can overflow a capacity here (at most one limit row per joint), so the host launches no tier workers or drains next to it.
 #if JACO_TU_HAS(8)
@@ -2565,7 +2581,7 @@ __global__ __launch_bounds__(64, 4) void jaco_physics_kernel_arm(JacoStepArgs A)
 template <class BIG, int TB, class U>
 JDEV int run_env_tiers(const JacoStepArgs& A, U& u, int env, int lane) {
   const unsigned long long t_start = wave_clock();
-  const bool stepmode = A.env_mode == 1 || A.env_mode == 3 || A.env_mode == 6;
+  const bool stepmode = JM_TASK_SUBSTEPS(A.env_mode);
   int left = stepmode ? A.nsub : A.remaining[env], why = 0;
   for (;;) {
     left = run_env<BIG, TB>(A, u.big, env, stepmode ? A.nsub : left, lane, !A.no_tier_return, &why);
@@ -2591,13 +2607,13 @@ union JacoAllLDS { JacoLDS<JacoHeavy> heavy; JacoMediumLDS ml; };
 #define JACO_HANDDOWN_MIN 8
 #endif                      // substeps that must be left for a hand-down to pay (it costs a queue round trip and a fresh model staging)
 JDEV int heavy_env_run(const JacoStepArgs& A, JacoAllLDS& u, int env, int lane, bool allow_down = false) {
-  const bool stepmode = A.env_mode == 1 || A.env_mode == 3 || A.env_mode == 6;
+  const bool stepmode = JM_TASK_SUBSTEPS(A.env_mode);
   int left = stepmode ? A.nsub : A.remaining[env], why = 0;
   for (;;) {
     left = run_env<JacoHeavy, 2>(A, u.heavy, env, stepmode ? A.nsub : left, lane, !A.no_tier_return, &why);
     if (left <= 0) return 0;
     if (why == 1) return left;
-    if (allow_down && A.handdown && A.env_mode == 1 && left >= JACO_HANDDOWN_MIN) return -left;   // calm again: the medium tier's turn (caller queues it)
+    if (allow_down && A.handdown && A.env_mode == JM_STEP && left >= JACO_HANDDOWN_MIN) return -left;   // calm again: the medium tier's turn (caller queues it)
     wave_sync();
     if (!stepmode && lane == 0) A.remaining[env] = left;   // (ctrl level: run_env_tiers reads the substeps left from here)
     wave_sync();
@@ -2619,7 +2635,7 @@ JDEV void heavy_env(const JacoStepArgs& A, JacoAllLDS& u, int env, int lane) {
 // down through heavy / medium / light like everything else
 union JacoHugeLDS { JacoLDS<JacoHuge> huge; JacoAllLDS rest; };
 JDEV void huge_env(const JacoStepArgs& A, JacoHugeLDS& u, int env, int lane) {
-  const bool stepmode = A.env_mode == 1 || A.env_mode == 3 || A.env_mode == 6;
+  const bool stepmode = JM_TASK_SUBSTEPS(A.env_mode);
   const unsigned long long t_start = wave_clock();
   int left = stepmode ? A.nsub : A.remaining[env], why = 0;
   for (;;) {

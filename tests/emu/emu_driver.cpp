@@ -76,22 +76,22 @@ static int emu_launch(JacoStepArgs A, int* heavy_envs) {
   if ((int)g_hint.size() != A.nenv) g_hint.assign(A.nenv, 0);
   A.hint = g_use_hints ? g_hint.data() : nullptr; A.hint_mode = g_use_hints;
   emu_grid = A.nenv;
-  // (as jaco_env.hip: the step kernel proper serves modes 0 / 1, every other mode the full-code twin)
+  // (as jaco_env.hip: the step kernel proper serves the real steps (JM_REAL_STEP), every other mode the full-code twin)
   // ... and contact-free steps (disable_contact, models without a collidable pair) the lean kernel, alone
-  if ((A.disable_contact || A.model->npair == 0) && A.env_mode <= 1) {
+  if ((A.disable_contact || A.model->npair == 0) && JM_REAL_STEP(A.env_mode)) {
     A.disable_contact = 1; A.hint = nullptr;
     for (int e = 0; e < A.nenv; e++) emu_run_wave(e, [&]() { jaco_physics_kernel_arm(A); });
     if (heavy_envs) *heavy_envs = 0;
     return 0;
   }
-  for (int e = 0; e < A.nenv; e++) emu_run_wave(e, [&]() { if (A.env_mode >= 2) jaco_physics_kernel_listed(A); else jaco_physics_kernel(A); });
+  for (int e = 0; e < A.nenv; e++) emu_run_wave(e, [&]() { if (!JM_REAL_STEP(A.env_mode)) jaco_physics_kernel_listed(A); else jaco_physics_kernel(A); });
   emu_grid = 1;
   // (the resident workers of the GPU build leave as soon as the light grid is done: here that is always the case, so the
   // drains serve every queue; they are the same serve functions).  Same launch sequence as jaco_env.hip, grids of one workgroup.
   if (count[0] > 0) emu_run_wave(0, [&]() { jaco_physics_kernel_medium(A); });
   emu_run_wave(0, [&]() { jaco_physics_kernel_medium_drain(A); });
   if (count[1] > 0) emu_run_wave(0, [&]() { jaco_physics_kernel_heavy_workers(A); });
-  if (g_handdown && A.env_mode == 1) {
+  if (g_handdown && A.env_mode == JM_STEP) {
     A.handdown = 1;
     emu_run_wave(0, [&]() { jaco_physics_kernel_heavy_drain(A); });
     A.handdown = 0;
@@ -105,7 +105,7 @@ static int emu_launch(JacoStepArgs A, int* heavy_envs) {
   if (heavy_envs) *heavy_envs = count[0];
   return 0;
 }
-// env-level call: mode 1 = step (nsub = frame_skip), mode 2 = forward only
+// env-level call (mode: JacoMode): JM_STEP = step (nsub = frame_skip), JM_FORWARD = forward only (nsub = 1), JM_HOLD / JM_PREREACH = resets
 static int g_auto_reset = 0;
 static std::vector<float> g_qpos0;
 extern "C" void emu_set_auto_reset(int on, const float* qpos0, int nq) { g_auto_reset = on; g_qpos0.assign(qpos0, qpos0 + nq); }
@@ -114,7 +114,7 @@ static int g_goal_n = 0, g_goal_stride = 0;
 extern "C" void emu_set_init_buffer(const float* rows, int nrows, int stride) {
   g_goal_buf.assign(rows, rows + (rows ? (size_t)nrows * stride : 0)); g_goal_n = rows ? nrows : 0; g_goal_stride = rows ? stride : 0;
 }
-// what jaco_reset_kernel does for one env (jaco_env.hip): sim.reset() + the draws; the forward pass is a mode-2 emu_env_call
+// what jaco_reset_kernel does for one env (jaco_env.hip): sim.reset() + the draws; the forward pass is a JM_FORWARD emu_env_call
 extern "C" void emu_reset_env(int task_id, unsigned long long seed, int env, int nq, int nv, const float* qpos0, const float* base, float* qpos, float* qvel,
                               float* qacc_ws, float* task, float* marker, const float* marker_rest) {
   for (int k = 0; k < nq; k++) qpos[(size_t)env * nq + k] = qpos0[k];
@@ -129,9 +129,9 @@ extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode
   if (load_model(blob, blob_size)) return -1;
   JacoStepArgs A{};
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = qvel; A.sensordata = sensordata;
-  A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = mode == 2 ? 1 : frame_skip; A.env_mode = mode; A.task_id = task_id; A.nact = nact;
+  A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = mode == JM_FORWARD ? 1 : frame_skip; A.env_mode = mode; A.task_id = task_id; A.nact = nact;
   A.seed = seed; A.task = task; A.cache = cache; A.action = action; A.noise = noise; A.obs = obs; A.reward = reward; A.done = done; A.marker = marker; A.dbg_env = -1;
-  A.auto_reset = g_auto_reset && mode == 1 && (task_id == 0 || task_id == 2 || task_id == 4 || task_id == 7); A.qpos0 = g_qpos0.empty() ? nullptr : g_qpos0.data();
+  A.auto_reset = g_auto_reset && mode == JM_STEP && (task_id == 0 || task_id == 2 || task_id == 4 || task_id == 7); A.qpos0 = g_qpos0.empty() ? nullptr : g_qpos0.data();
   A.goal_buf = g_goal_buf.empty() ? nullptr : g_goal_buf.data(); A.goal_n = g_goal_n; A.goal_stride = g_goal_stride;
   return emu_launch(A, heavy_envs);
 }

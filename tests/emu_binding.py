@@ -9,6 +9,7 @@ env-level calls and robot-configuration queries (tests/query_binding.py), and on
 import ctypes
 import sys
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -19,6 +20,10 @@ if ROOT not in sys.path:
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 ASSETS = os.path.join(ROOT, "mujoco_jaco_amd", "assets")
 _libs = {}
+# launch modes of emu_env_call, read from the kernel's own enum (physics_kernel.h JacoMode) so that the two cannot drift apart
+with open(os.path.join(ROOT, "mujoco_jaco_amd", "csrc", "physics_kernel.h")) as _f:
+    _MODES = {k: int(v) for k, v in re.findall(r"(JM_\w+) = (\d+)", re.search(r"enum JacoMode \{([^}]*)\}", _f.read()).group(1))}
+JM_STEP, JM_FORWARD, JM_HOLD, JM_TERMINAL, JM_PREREACH = (_MODES[k] for k in ("JM_STEP", "JM_FORWARD", "JM_HOLD", "JM_TERMINAL", "JM_PREREACH"))
 
 
 def lib(layout=""):
@@ -125,18 +130,18 @@ class EmuJacoEnv(EmuEnv):
         self.heavy_envs = hv.value
 
     def placing_hold(self, nsub=150):
-        """mode 3: the held part of the placing reset (jaco_reset runs it between the reset kernel and jaco_forward)."""
+        """JM_HOLD: the held part of the placing reset (jaco_reset runs it between the reset kernel and jaco_forward)."""
         fs, self.frame_skip = self.frame_skip, nsub
         try:
-            self._call(3, None, None)
+            self._call(JM_HOLD, None, None)
         finally:
             self.frame_skip = fs
 
     def grasping_prereach(self, cap=4000, noise=None):
-        """mode 6: the pre-reach loops of the grasping reset (jaco_reset runs them after the draws); returns the observation row."""
+        """JM_PREREACH: the pre-reach loops of the grasping reset (jaco_reset runs them after the draws); returns the observation row."""
         fs, self.frame_skip = self.frame_skip, cap
         try:
-            self._call(6, None, None if noise is None else np.ascontiguousarray(noise, np.float32))
+            self._call(JM_PREREACH, None, None if noise is None else np.ascontiguousarray(noise, np.float32))
         finally:
             self.frame_skip = fs
         return self.obs.copy()
@@ -155,7 +160,7 @@ class EmuJacoEnv(EmuEnv):
         self.L.emu_set_init_buffer(r.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r.shape[0], r.shape[1])
 
     def reset_env(self, env, noise=None):
-        """jaco_reset(mask = {env}): the reset kernel's work for one env, then the forward pass + observation (mode 2; here for all envs,
+        """jaco_reset(mask = {env}): the reset kernel's work for one env, then the forward pass + observation (JM_FORWARD; here for all envs,
         which is harmless for the others: a forward pass does not change state)."""
         fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         q0 = np.ascontiguousarray(self.M["qpos0"], np.float32)
@@ -166,10 +171,10 @@ class EmuJacoEnv(EmuEnv):
                              fp(self.marker), fp(rest))
 
     def forward(self, noise=None):
-        self._call(2, None, None if noise is None else np.ascontiguousarray(noise, np.float32))
+        self._call(JM_FORWARD, None, None if noise is None else np.ascontiguousarray(noise, np.float32))
         return self.obs.copy()
 
     def env_step(self, action, noise=None):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(action, np.float32), (self.nenv, 6 if self.task_id in (2, 7) else 7)))
-        self._call(1, a, None if noise is None else np.ascontiguousarray(noise, np.float32))
+        self._call(JM_STEP, a, None if noise is None else np.ascontiguousarray(noise, np.float32))
         return self.obs.copy(), self.reward.copy(), self.done.copy()

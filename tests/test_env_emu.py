@@ -3,7 +3,7 @@ env (tests/oracle_env.py = physics oracle + oracle/glue.py, the latter pinned by
 import numpy as np
 import pytest
 
-from emu_binding import EmuJacoEnv
+from emu_binding import JM_TERMINAL, EmuJacoEnv
 from mujoco_jaco_amd import workload
 from oracle_env import OracleEnv
 
@@ -262,7 +262,7 @@ def _inject_scene(e, model_arrays, ee, eeq, obj, q2, touch):
 
 def test_kernel_terminal_inspection_against_the_references_own_outputs(model_arrays):
     """The in-kernel termination rules of tasks grasping and pickAndplace (csrc/env_logic.h), driven through the terminal_inspection
-    entry (mode 5), against tests/golden/glue_vectors_grasping.npz = outputs of the reference's own _get_terminal_inspection
+    entry (JM_TERMINAL), against tests/golden/glue_vectors_grasping.npz = outputs of the reference's own _get_terminal_inspection
     (env_mujoco_util.py:521-536, 585-600): done flag exact, bonus to fp32 rounding, the `picked` flag carried in the task row."""
     import os
     GG = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "glue_vectors_grasping.npz"))
@@ -273,7 +273,7 @@ def test_kernel_terminal_inspection_against_the_references_own_outputs(model_arr
             _inject_scene(e, model_arrays, GG["g_ee"][k], GG["g_eeq"][k], GG["g_obj"][k], GG["g_q2"][k], int(GG["g_touch"][k]))
             e.task[0] = 0; e.task[0, 0] = 0.6; e.task[0, 16] = 0.6
             e.task[0, 2] = GG["g_nsteps"][k]; e.task[0, 7:10] = GG["g_dest_goal"][k]; e.task[0, 31] = GG["g_picked_in"][k]
-            e._call(5)
+            e._call(JM_TERMINAL)
             rd, rb, rwb = GG[key][k]
             assert bool(e.done[0]) == bool(rd), (task_id, k)
             assert abs(e.reward[0] - rb) < 2e-4 and abs(e.task[0, 30] - rwb) < 1e-5, (task_id, k, e.reward[0], rb)
@@ -289,7 +289,7 @@ def test_kernel_terminal_inspection_against_the_references_own_outputs(model_arr
 
 def test_grasping_prereach_and_steps_match_oracle_env(names, model_arrays):
     """Grasping reset (env_mujoco_util.py:123-170) from two arm poses of its init range (:181-185): the emulated kernel's pre-reach
-    (mode 6) must take the oracle env's path -- same loop exits, same EE target, observation and arm state -- and the env steps
+    (JM_PREREACH) must take the oracle env's path -- same loop exits, same EE target, observation and arm state -- and the env steps
     that follow must agree in observation, reward (:352-391) and termination."""
     for seed, expect_min in ((18, 50), (13, 1)):
         rng = np.random.default_rng(100 + seed)
@@ -336,31 +336,31 @@ def test_kernel_terminal_inspection_picking_placing_against_the_references_own_o
             _inject_scene(e, model_arrays, G["s_ee"][k], G["s_eeq"][k], G["s_obj"][k], G["s_q2"][k], int(G["s_touch"][k]))
             e.task[0] = 0; e.task[0, 0] = 0.6; e.task[0, 16] = 0.6
             e.task[0, 2] = G["s_nsteps"][k]; e.task[0, 7:10] = G["s_dest_goal"][k]
-            e._call(5)
+            e._call(JM_TERMINAL)
             rd, rb, rwb, rs = G[key][k]
             assert bool(e.done[0]) == bool(rd) and e.task[0, 29] == rs, (task_id, k)
             assert abs(e.reward[0] - rb) < 2e-4 and abs(e.task[0, 30] - rwb) < 1e-5
 
 
 def test_terminal_inspection_on_a_finished_env_is_frozen(names, model_arrays):
-    """jaco_terminal_inspection on its own (mode 5) freezes like jaco_step: a finished -- or NaN-quarantined -- env keeps done = 1,
+    """jaco_terminal_inspection on its own (JM_TERMINAL) freezes like jaco_step: a finished -- or NaN-quarantined -- env keeps done = 1,
     bonus 0 and its counters (it used to count another step and recompute done, un-quarantining an env with NaN poses)."""
     e, _ = _pair(names, model_arrays, 5, 1)
     e.forward()
     e.task[0, 1] = 699                                                   # one terminal_inspection away from the time-out
-    e._call(5)
+    e._call(JM_TERMINAL)
     assert e.done[0] == 1 and abs(e.reward[0] + 10.0) < 1e-6 and e.task[0, 3] == 1 and e.task[0, 1] == 700
     steps, episodes = e.task[0, 1], e.task[0, 2]
-    e._call(5)                                                           # again: frozen
+    e._call(JM_TERMINAL)                                                 # again: frozen
     assert e.done[0] == 1 and e.reward[0] == 0 and e.task[0, 1] == steps and e.task[0, 2] == episodes and e.task[0, 3] == 1
     e.cache[0, 78:93] = np.nan                                           # quarantined env: poses non-finite
-    e._call(5)
+    e._call(JM_TERMINAL)
     assert e.done[0] == 1 and e.reward[0] == 0 and e.task[0, 3] == 1
 
 
 def test_auto_reset_equals_the_explicit_reset_chain(names, model_arrays):
     """Option "auto_reset": the wave that finishes an episode does sim.reset(), the draws of _reset and sim.forward() + the first
-    observation itself.  Bit-for-bit what the explicit chain (reset kernel's work, then a mode-2 forward pass) leaves behind: state,
+    observation itself.  Bit-for-bit what the explicit chain (reset kernel's work, then a JM_FORWARD pass) leaves behind: state,
     task row (goals, draw counter, counters), controller cache, markers and the observation row; reward / done are the terminal step's."""
     def make():
         e, _ = _pair(names, model_arrays, 7, 2)
@@ -482,7 +482,7 @@ def test_pair_list_does_not_change_results(names, model_arrays):
 # ---------------------------------------------------------------- tasks releasing / carrying / pushing (round 4)
 def test_kernel_terminal_releasing_carrying_pushing_against_the_references_own_outputs(model_arrays):
     """The in-kernel termination rules of tasks releasing / carrying / pushing (csrc/env_logic.h) through the terminal_inspection entry
-    (mode 5) against tests/golden/glue_vectors_releasing.npz = outputs of the reference's own _get_terminal_inspection
+    (JM_TERMINAL) against tests/golden/glue_vectors_releasing.npz = outputs of the reference's own _get_terminal_inspection
     (env_mujoco_util.py:549-566,583-584): done flag exact, bonus to fp32 rounding; releasing reads the object's velocity (qvel[9:12])."""
     import os
     GR = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "glue_vectors_releasing.npz"))
@@ -495,7 +495,7 @@ def test_kernel_terminal_releasing_carrying_pushing_against_the_references_own_o
             e.qvel[0, 9:12] = GR["r_objvel"][k]
             e.task[0] = 0; e.task[0, 0] = 0.6; e.task[0, 16] = 0.6
             e.task[0, 2] = GR["r_nsteps"][k]; e.task[0, 7:10] = GR["r_dest_goal"][k]
-            e._call(5)
+            e._call(JM_TERMINAL)
             rd, rb, rwb, _ = GR[key][k]
             assert bool(e.done[0]) == bool(rd), (task_id, k)
             assert abs(e.reward[0] - rb) < 2e-4 and abs(e.task[0, 30] - rwb) < 1e-5, (task_id, k, e.reward[0], rb)
@@ -574,7 +574,7 @@ def test_reset_draws_the_reaching_goal_from_an_init_buffer(model_arrays):
 
 def test_forward_pass_runs_on_zero_controls_whatever_the_neighbours_do(model_arrays):
     """sim.forward() after sim.reset() sees data.ctrl = 0.  The env-level launches hand the kernel a placeholder ctrl pointer (the qvel buffer);
-    a forward pass alone (mode 2: jaco_forward, the explicit reset chain) used to READ it -- env e took qvel words [9 e, 9 e + 9) as its nine
+    a forward pass alone (JM_FORWARD: jaco_forward, the explicit reset chain) used to READ it -- env e took qvel words [9 e, 9 e + 9) as its nine
     controls, so a reset's first touch reading depended on other envs' velocities (found on MI355X by the auto-reset bit-identity test: 1 env of
     8 192 x 6 steps, a reset with the hand inside the pedestal).  Two envs in such a pose: env 1's readings must not move when env 0 spins."""
     q = workload.reset_states(model_arrays["qpos0"], 64, seed=7, f32_draws=True)[62]   # hand 10 cm inside the pedestal: pads and EE sensor loaded

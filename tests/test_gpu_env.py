@@ -176,7 +176,7 @@ def test_placing_reset_vs_oracle(model_arrays, names):
 
 
 def test_placing_hold_parity_150(model_arrays, names):
-    """The full 150-substep hold on the GPU against the oracle, from a given pre-hold state (mode 3 through jaco_reset is
+    """The full 150-substep hold on the GPU against the oracle, from a given pre-hold state (JM_HOLD through jaco_reset is
     covered above; here the kernel is driven through the same entry with a state injected before the hold)."""
     from mujoco_jaco_amd import workload
     from mujoco_jaco_amd.env import JacoBatchedEnv
