@@ -41,6 +41,7 @@ extern "C" {
 #define JACO_FLAG_BAIL_CAUSE_SHIFT 8  /* informational, bits 8..16: which capacity (bit 0 contacts, 1 rows, 2 candidates) made tier 0 / 1 / 2 (3 bits each) hand the env on */
 #define JACO_FLAG_OSC_SINGULAR 64u   /* informational: |det(J M^-1 J^T)| < 1e-3, the controller used its pseudo-inverse branch */
 #define JACO_FLAG_PREREACH_CAP 0x20000u /* the grasping reset's pre-reach loops (unbounded in the reference) stopped at the substep cap */
+#define JACO_FLAG_BAD_SNAPSHOT 0x40000u /* jaco_load_envs was given a row of another build, model, task or layout version for this env: the env was left as it was */
 
 /* task ids (env_script/env_mujoco.py:18-23; only picking/placing return the 4-tuple step() unpacks) */
 #define JACO_TASK_PICKING 0
@@ -172,6 +173,37 @@ int jaco_get_terminal_obs(JacoHandle* h, float* out_dev, void* stream);
 int jaco_get_markers(JacoHandle* h, float* out_dev, void* stream);
 int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream);
 int jaco_set_frame_skip(JacoHandle* h, int frame_skip);
+
+/* ---- env snapshots: sim.get_state() / sim.set_state() (mujoco.py:213-246,332-347) as a FULL-state pair, per env and by index.
+ * The reference's MjSimState is everything its sim.step() reads; here that is more than jaco_get_state / jaco_get_task_state /
+ * jaco_get_markers hand out (jaco_set_state rounds the compensated state to fp32 and zeroes the tier hints; the controller's cache, the
+ * touch values, flags, statistics and the terminal latches have no accessor), and those calls move whole batches.  A snapshot of one env
+ * is one ROW of W = jaco_snapshot_words(h) 32-bit words (W a multiple of 4: rows of a [n][W] buffer are 16-byte aligned; the buffer is the
+ * caller's, e.g. a torch int32 tensor, and must be 16-byte aligned).  The row holds every word a later launch reads of that env (table and
+ * layout: csrc/snapshot.h): both halves of the compensated qpos / qvel, qacc_warmstart, sensordata, flags, stats, tier hint, step cost,
+ * task row (draw counter, done flag, counters, goals, target, gripper ramp), controller cache, marker poses, terminal latches.  An env
+ * loaded from a row continues BIT FOR BIT as the env the row was saved from did, on any env index of the same handle or of another
+ * handle of the same build, model, task and layout version: word 0 of a row is a fingerprint of those.
+ * Not in a row: the separating-direction cache (its entries are re-validated before use and cannot change a result; a load leaves the
+ * destination's as they are), per-launch scratch, buffers the library only points to (jaco_set_noise / jaco_set_subgoal /
+ * jaco_set_contact_record / jaco_set_init_buffer) and handle-wide settings (seed, frame_skip, options).
+ * Random numbers: the stream is keyed by (seed, env index, counter) and only the counter is state.  A row loaded into the env index it
+ * came from (same seed) continues the same stream; loaded into another index it gives the same physical state on THAT index's stream,
+ * from the same counter.  With injected noise (jaco_set_noise) and no reset in the window a clone continues exactly as its source.
+ *
+ * jaco_save_envs: rows_dev[i] := state of env env_idx_dev[i], i < n.  env_idx_dev NULL: identity (then n must be num_envs).
+ * jaco_load_envs: env env_idx_dev[i] := rows_dev[row_idx_dev[i]], i < n.  env_idx_dev NULL: identity (n == num_envs); row_idx_dev NULL:
+ *   entry i reads row i (n <= nrows).  nrows = rows in the buffer.  The same row may be loaded into many envs (fan-out); an env index
+ *   listed twice is undefined.  "env e := env s" in place is a save into a scratch buffer followed by a load with row_idx_dev.
+ * Both: asynchronous on `stream`, ONE kernel launch (none for n == 0), no allocation, no synchronisation, no host copy.  JACO_EINVAL for
+ * n < 0, n > num_envs, NULL or misaligned rows, a NULL env index list with n != num_envs.  What only the device can see does not fault
+ * and does not stay silent: an env index outside [0, num_envs) or a row index outside [0, nrows) makes that entry a no-op; a row whose
+ * fingerprint is not this handle's leaves the env untouched and sets JACO_FLAG_BAD_SNAPSHOT in that env's flags.
+ * After a load the next launch prepares its tier queues itself (as after any launch that does not route): envs start in the tier their
+ * loaded hint names. */
+int jaco_snapshot_words(const JacoHandle* h);
+int jaco_save_envs(JacoHandle* h, const int32_t* env_idx_dev, int n, uint32_t* rows_dev, void* stream);
+int jaco_load_envs(JacoHandle* h, const int32_t* env_idx_dev, int n, const uint32_t* rows_dev, int nrows, const int32_t* row_idx_dev, void* stream);
 
 /* ---- robot-configuration queries: MujocoConfig.J / M / g / R / quaternion / Tx (mujoco_config.py:201-447) and Mujoco.get_xyz /
  * get_orientation (mujoco.py:148-215), batched.  The values are those of a sim.forward() on the given state: body poses, the

@@ -30,6 +30,7 @@ class JacoContact(ctypes.Structure):
 
 
 JACO_CONTACT_MAX_CAPACITY = 1024
+JACO_FLAG_BAD_SNAPSHOT = 0x40000   # jaco_load_envs: a row of another build / model / task / layout version was refused for this env
 CONTACT_WORDS = ctypes.sizeof(JacoContact) // 4        # 24 32-bit words per record
 CONTACT_FLOATS = JacoContact.geom.offset // 4          # the first 19 are floats (dist, pos, frame, force), then 5 int32 (geom, body, dim)
 assert ctypes.sizeof(JacoContact) == 96 and CONTACT_FLOATS == 19
@@ -86,6 +87,9 @@ SYMBOLS = {
     "jaco_stage_profile": (_ci, [_vp, ctypes.POINTER(ctypes.c_uint64), _ci]),
     "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
+    "jaco_snapshot_words": (_ci, [_vp]),
+    "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),
+    "jaco_load_envs": (_ci, [_vp, _vp, _ci, _vp, _ci, _vp, _vp]),
 }
 
 _libs = {}

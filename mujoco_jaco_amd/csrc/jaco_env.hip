@@ -13,6 +13,7 @@
 #include "../../include/jaco_env.h"
 #include "model_blob.h"
 #include "physics_kernel.h"
+#include "snapshot.h"
 
 // the physics kernels live in their own translation units (kernels.hip, one per kernel)
 #define JACO_DECLARE_LAUNCHER(n) void jaco_launch_kernel_##n(unsigned grid, hipStream_t st, const JacoStepArgs& A);
@@ -804,6 +805,74 @@ extern "C" int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream
   HIPCHK(h, hipMemcpyAsync(h->marker, in_dev, (size_t)h->num_envs * 24 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return JACO_OK;
 }
+// ---- env snapshots (snapshot.h: the row table and the two per-entry routines, shared with the CPU tests' host build) ------------------
+// One wavefront per entry, four entries per 256-thread block: the wave reads its env / row index once, makes it wave-uniform (the
+// addresses below are then scalar base + lane offset) and moves the row 16 bytes per lane on the snapshot side, dword by dword on the
+// side of the library's arrays.  Nothing is shared between waves: an entry that is out of range is skipped by its own wave.
+static_assert(JSNAP_FLAG_BAD == JACO_FLAG_BAD_SNAPSHOT, "flag bit of snapshot.h and the public header must agree");
+#define JSNAP_ENTRIES_PER_BLOCK 4
+__global__ __launch_bounds__(64 * JSNAP_ENTRIES_PER_BLOCK) void jaco_save_envs_kernel(JacoSnapTable T, const int32_t* env_idx, int n, uint32_t* rows) {
+  const int i = (int)blockIdx.x * JSNAP_ENTRIES_PER_BLOCK + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  if (i >= n) return;
+  int e, r;
+  if (!jaco_snap_entry(T, env_idx, nullptr, n, i, &e, &r)) return;
+  e = __builtin_amdgcn_readfirstlane(e);
+  jaco_snap_save_entry(T, e, rows + (size_t)i * T.W, lane, 64);
+}
+__global__ __launch_bounds__(64 * JSNAP_ENTRIES_PER_BLOCK) void jaco_load_envs_kernel(JacoSnapTable T, const int32_t* env_idx, int n, const uint32_t* rows, int nrows,
+                                                                                    const int32_t* row_idx) {
+  const int i = (int)blockIdx.x * JSNAP_ENTRIES_PER_BLOCK + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  if (i >= n) return;
+  int e, r;
+  if (!jaco_snap_entry(T, env_idx, row_idx, nrows, i, &e, &r)) return;
+  e = __builtin_amdgcn_readfirstlane(e);
+  r = __builtin_amdgcn_readfirstlane(r);
+  jaco_snap_load_entry(T, e, rows + (size_t)r * T.W, lane, 64);
+}
+static JacoSnapTable snapshot_table(const JacoHandle* h) {
+  JacoSnapSrc s;
+  s.qpos = h->qpos; s.qpos_lo = h->qpos_lo; s.qvel = h->qvel; s.qvel_lo = h->qvel_lo; s.qacc_ws = h->qacc_ws; s.sensordata = h->sensordata;
+  s.flags = h->flags; s.stats = h->stats; s.hint = h->hint; s.cost = h->cost; s.task = h->task_rows; s.cache = h->cache; s.marker = h->marker;
+  s.terminal = h->terminal; s.terminal_obs = h->terminal_obs;
+  const JacoModelDev& m = h->model_host;
+  return jaco_snapshot_table(s, m.nq, m.nv, m.nsensor, h->task, h->num_envs);
+}
+extern "C" int jaco_snapshot_words(const JacoHandle* h) { return h ? snapshot_table(h).W : JACO_EINVAL; }
+static int snapshot_args(JacoHandle* h, const char* who, const int32_t* env_idx, int n, const void* rows) {
+  if (n < 0 || n > h->num_envs || !rows || (!env_idx && n != h->num_envs)) {
+    h->err = std::string(who) + ": needs rows, 0 <= n <= num_envs, and n == num_envs when there is no env index list";
+    return JACO_EINVAL;
+  }
+  if ((reinterpret_cast<uintptr_t>(rows) & 15u) != 0) { h->err = std::string(who) + ": the row buffer must be 16-byte aligned"; return JACO_EINVAL; }
+  return JACO_OK;
+}
+extern "C" int jaco_save_envs(JacoHandle* h, const int32_t* env_idx_dev, int n, uint32_t* rows_dev, void* stream) {
+  if (!h) return JACO_EINVAL;
+  int rc = snapshot_args(h, "jaco_save_envs", env_idx_dev, n, rows_dev);
+  if (rc || n == 0) return rc;
+  ENTER(h);
+  JLAUNCH(h, jaco_save_envs_kernel, dim3((unsigned)((n + JSNAP_ENTRIES_PER_BLOCK - 1) / JSNAP_ENTRIES_PER_BLOCK)), dim3(64 * JSNAP_ENTRIES_PER_BLOCK), 0, (hipStream_t)stream,
+          snapshot_table(h), env_idx_dev, n, rows_dev);
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}
+extern "C" int jaco_load_envs(JacoHandle* h, const int32_t* env_idx_dev, int n, const uint32_t* rows_dev, int nrows, const int32_t* row_idx_dev, void* stream) {
+  if (!h) return JACO_EINVAL;
+  int rc = snapshot_args(h, "jaco_load_envs", env_idx_dev, n, rows_dev);
+  if (rc) return rc;
+  if (nrows < 0 || (!row_idx_dev && n > nrows)) { h->err = "jaco_load_envs: without a row index list entry i reads row i: needs n <= nrows"; return JACO_EINVAL; }
+  if (n == 0) return JACO_OK;
+  ENTER(h);
+  JLAUNCH(h, jaco_load_envs_kernel, dim3((unsigned)((n + JSNAP_ENTRIES_PER_BLOCK - 1) / JSNAP_ENTRIES_PER_BLOCK)), dim3(64 * JSNAP_ENTRIES_PER_BLOCK), 0, (hipStream_t)stream,
+          snapshot_table(h), env_idx_dev, n, rows_dev, nrows, row_idx_dev);
+  HIPCHK(h, hipGetLastError());
+  // The loaded envs carry the hints of their rows.  The routing kernel reads the hints when its launch starts, so no env is queued by a
+  // hint it no longer has; what the previous launch prepared ahead (option "merge_prepare") is only the cleared queue buffer.  The next
+  // launch prepares its buffer itself all the same: a load is a cut in the row of steps, like the launches that do not route.
+  h->q_ready = false;
+  return JACO_OK;
+}
+
 extern "C" int jaco_set_frame_skip(JacoHandle* h, int frame_skip) {
   if (!h || frame_skip <= 0) return JACO_EINVAL;
   h->frame_skip = frame_skip;

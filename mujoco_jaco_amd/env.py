@@ -40,6 +40,41 @@ class Box:
         return x.shape == self.shape and bool(np.all(x >= self.low) and np.all(x <= self.high))
 
 
+class EnvSnapshot:
+    """What JacoBatchedEnv.save_envs returns: `rows` [n, W] int32 (BatchedMujoco.save_envs: the complete library-side state of n envs) and
+    `obs` [n, 26] float32, the matching rows of the last observation the env returned -- the library does not own the observation, and
+    recomputing it with a forward pass would consume observation-noise draws the original run did not.  `current_steps` is the env's
+    host-side step mirror at save time.  Plain tensors: snap[i] / snap[idx] select rows, .to("cpu") moves them, and
+    torch.save(snap.tensors(), f) / EnvSnapshot.from_tensors(torch.load(f)) is the file format."""
+
+    def __init__(self, rows, obs, current_steps=0):
+        assert rows.dim() == 2 and obs.shape == (rows.shape[0], 26), (rows.shape, obs.shape)
+        self.rows, self.obs, self.current_steps = rows, obs, int(current_steps)
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def __getitem__(self, idx):
+        if isinstance(idx, int):
+            idx = [idx]
+        if not isinstance(idx, slice):
+            idx = torch.as_tensor(idx, device=self.rows.device)
+        return EnvSnapshot(self.rows[idx], self.obs[idx], self.current_steps)
+
+    def to(self, device):
+        return EnvSnapshot(self.rows.to(device), self.obs.to(device), self.current_steps)
+
+    def clone(self):
+        return EnvSnapshot(self.rows.clone(), self.obs.clone(), self.current_steps)
+
+    def tensors(self):
+        return {"rows": self.rows, "obs": self.obs, "current_steps": torch.tensor(self.current_steps)}
+
+    @classmethod
+    def from_tensors(cls, d):
+        return cls(d["rows"], d["obs"], int(d["current_steps"]))
+
+
 class JacoBatchedEnv:
     def __init__(self, num_envs=1, device=0, frame_skip=50, seed=0, **kwargs):
         self.task = kwargs.get("task", "picking")
@@ -107,7 +142,9 @@ class JacoBatchedEnv:
         self.action_space = Box(self.act_min, self.act_max, dtype=np.float32)
         self.wb = 0
         self.metadata = None
-        self._obs = torch.zeros(self.num_envs, 26, device=self.device)
+        # (one spare row behind the batch: load_envs / clone_envs park the observation rows of skipped entries there)
+        self._obs_buf = torch.zeros(self.num_envs + 1, 26, device=self.device)
+        self._obs = self._obs_buf[:self.num_envs]
         self._rew = torch.zeros(self.num_envs, device=self.device)
         self._done = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
         self._noise = None
@@ -169,6 +206,67 @@ class JacoBatchedEnv:
         m = self._mask(mask)
         self.sim._chk(self.L.jaco_reset(self.h, self._p(m) if m is not None else None, self._p(self._obs), self.sim._stream()))
         return self._out(self._obs)[0]
+
+    # ---- env snapshots (jaco_save_envs / jaco_load_envs): put an env back where it was, start many envs from one env's state
+    def save_envs(self, envs=None):
+        """EnvSnapshot of the listed envs (None: all, in order): their complete state rows and their rows of the last returned
+        observation.  One kernel launch and one gather; no synchronisation."""
+        rows = self.sim.save_envs(envs)
+        e = self.sim._index(envs)
+        obs = self._obs.clone() if e is None else self._obs_buf[self._safe(e, self.num_envs)].clone()
+        return EnvSnapshot(rows, obs, self.current_steps)
+
+    @staticmethod
+    def _safe(idx, n):
+        """int64 indices with everything outside [0, n) sent to n (the spare row): what the library skips must not fault in torch either."""
+        i = idx.long()
+        return torch.where((i >= 0) & (i < n), i, torch.full_like(i, n))
+
+    def _fingerprint(self):
+        if getattr(self, "_snap_fp", None) is None:
+            self._snap_fp = self.sim.save_envs([0])[0, 0].clone()   # word 0 of any row of this handle (a 0-dim device tensor)
+        return self._snap_fp
+
+    def _load(self, rows, obs, e, r):
+        """sim.load_envs + the observation rows of the entries the library accepts (in range, fingerprint of this handle)."""
+        B, nrows = self.num_envs, int(rows.shape[0])
+        fp = self._fingerprint()
+        self.sim.load_envs(rows, e, r)
+        ei = torch.arange(B, device=self.device) if e is None else e.long()
+        ri = torch.arange(ei.numel(), device=self.device) if r is None else r.long()
+        rsafe = self._safe(ri, nrows).clamp(max=max(nrows - 1, 0))
+        ok = (ri >= 0) & (ri < nrows) & (rows[rsafe, 0] == fp)
+        self._obs_buf[torch.where(ok, self._safe(ei, B), torch.full_like(ei, B))] = obs[rsafe]
+        return self._out(self._obs)[0]
+
+    def load_envs(self, snap, envs=None, row_index=None):
+        """env envs[i] := snap[row_index[i]] (envs None: all envs in order; row_index None: row i); returns the observation [B, 26] with the
+        loaded envs' rows replaced by the snapshot's.  The loaded envs continue bit for bit as the saved ones did: same physics, same
+        task state, same tier, same random draws when the env index and the seed are the same (another index continues on its own
+        stream from the same counter; with set_noise the draws are the caller's either way).  `current_steps`, the host-side mirror
+        that reset() zeroes whatever its mask, becomes the snapshot's.  The snapshot may come from another env of the same task and
+        model; one of another task or model is refused row by row (JACO_FLAG_BAD_SNAPSHOT in sim.flags(), env and observation untouched)."""
+        snap = snap.to(self.device)
+        e, r = self.sim._index(envs), self.sim._index(row_index)
+        self.current_steps = snap.current_steps
+        return self._load(snap.rows.contiguous(), snap.obs, e, r)
+
+    def clone_envs(self, src, mask=None):
+        """env e := env src[e] for every env (or those whose mask entry is set): a save of all envs into a scratch tensor kept on the env,
+        then a load by row index -- two launches, no read-after-write hazard between envs.  src: [num_envs] ints (a single int fans that
+        env out to all).  Returns the observation [B, 26].  A clone shares its source's physical and task state, draw counter included;
+        its later random draws are those of its OWN index (see load_envs)."""
+        B = self.num_envs
+        s = torch.full((B,), int(src), dtype=torch.int32, device=self.device) if isinstance(src, int) else self.sim._index(src)
+        if s.numel() != B:
+            raise ValueError("clone_envs: src must have one entry per env (%d), got %d" % (B, s.numel()))
+        if getattr(self, "_snap_scratch", None) is None:
+            self._snap_scratch = torch.empty(B, self.sim.snapshot_words, dtype=torch.int32, device=self.device)
+        rows = self.sim.save_envs(out=self._snap_scratch)
+        e = torch.arange(B, dtype=torch.int32, device=self.device)
+        if mask is not None:
+            e = torch.where(self._mask(mask).bool(), e, torch.full_like(e, -1))   # (an index outside the batch is a skipped entry: no host round trip)
+        return self._load(rows, self._obs.clone(), e, s)
 
     def markers(self):
         """[num_envs, 2, 12] poses (position, rotation matrix) of the "hand" and "subgoal_reach" markers that step() moves

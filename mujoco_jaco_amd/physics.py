@@ -122,6 +122,48 @@ class BatchedMujoco:
         self.state_version += 1
         self._chk(self.L.jaco_reset_state(self.h, self._stream()))
 
+    # ---- env snapshots (jaco_save_envs / jaco_load_envs: sim.get_state / set_state as a full-state pair, per env)
+    @property
+    def snapshot_words(self):
+        """W: 32-bit words of one snapshot row of this handle (a multiple of 4)."""
+        if getattr(self, "_snap_w", None) is None:
+            self._snap_w = int(self.L.jaco_snapshot_words(self.h))
+        return self._snap_w
+
+    def _index(self, idx):
+        """An env / row index list as an int32 device tensor (no synchronisation); None stays None."""
+        if idx is None:
+            return None
+        return torch.as_tensor(idx).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+
+    def save_envs(self, envs=None, out=None):
+        """rows [n, W] int32: row i = the complete state of env envs[i] (None: all envs in order) -- everything a later step reads of it
+        (include/jaco_env.h, "env snapshots").  Rows are plain tensors: index, concatenate, move to the host, torch.save them.  `out`: a
+        contiguous int32 device tensor [>= n, W] to write into (its first n rows are returned).  One kernel launch on the current stream."""
+        e = self._index(envs)
+        n = self.num_envs if e is None else e.numel()
+        W = self.snapshot_words
+        if out is None:
+            out = torch.empty(n, W, dtype=torch.int32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == W and out.shape[0] >= n, (out.shape, out.dtype)
+        self._chk(self.L.jaco_save_envs(self.h, ctypes.c_void_p(e.data_ptr()) if e is not None else None, n, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out[:n]
+
+    def load_envs(self, rows, envs=None, row_index=None):
+        """env envs[i] := rows[row_index[i]] (envs None: all envs in order; row_index None: row i).  The same row may go to many envs
+        (fan-out); an env listed twice is undefined.  Out-of-range indices are skipped; a row of another build / model / task leaves its
+        env untouched and sets JACO_FLAG_BAD_SNAPSHOT in flags().  The loaded envs continue bit for bit as the saved ones did (on another
+        env index: on that index's random stream).  One kernel launch on the current stream."""
+        rows = rows.to(device=self.device, dtype=torch.int32)
+        rows = rows.reshape(-1, self.snapshot_words).contiguous()
+        e, r = self._index(envs), self._index(row_index)
+        n = e.numel() if e is not None else (r.numel() if r is not None else self.num_envs)
+        if e is not None and r is not None and r.numel() != n:
+            raise ValueError("load_envs: %d envs but %d row indices" % (n, r.numel()))
+        self.state_version += 1
+        self._chk(self.L.jaco_load_envs(self.h, ctypes.c_void_p(e.data_ptr()) if e is not None else None, n, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]),
+                                        ctypes.c_void_p(r.data_ptr()) if r is not None else None, self._stream()))
+
     # ---- send_forces
     def send_forces(self, ctrl, nsub=1):
         self.state_version += 1

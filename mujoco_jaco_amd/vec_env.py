@@ -11,6 +11,9 @@ the finished episode is kept in `infos["terminal_observation"]` rows, as SB's Ve
 result size the host would have to wait for).  `infos` then holds full-size device tensors, rows / entries valid where `done` is set:
 `terminal_observation [B,26]`, `episode_return [B]`, `episode_length [B]`, `is_success [B]`, plus `quarantined` as a 0-dim device
 tensor; a learner masks them with `done` on the device.  The default (sparse rows gathered with `[done]`) synchronises once per step.
+
+Snapshots: `self.env.save_envs` / `load_envs` / `clone_envs` restore the env; the adapter's own Python-side episode accumulators
+(`episode_returns`, `episode_lengths`, the quarantine counts) are not part of a snapshot -- a caller who rewinds the env rewinds those itself.
 """
 import torch
 
