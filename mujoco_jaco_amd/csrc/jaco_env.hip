@@ -16,23 +16,13 @@
 #include "snapshot.h"
 
 // the physics kernels live in their own translation units (kernels.hip, one per kernel)
-#define JACO_DECLARE_LAUNCHER(n) void jaco_launch_kernel_##n(unsigned grid, hipStream_t st, const JacoStepArgs& A);
-JACO_DECLARE_LAUNCHER(0) JACO_DECLARE_LAUNCHER(1) JACO_DECLARE_LAUNCHER(2) JACO_DECLARE_LAUNCHER(3)
-JACO_DECLARE_LAUNCHER(4) JACO_DECLARE_LAUNCHER(5) JACO_DECLARE_LAUNCHER(6) JACO_DECLARE_LAUNCHER(7) JACO_DECLARE_LAUNCHER(8)
+typedef void JacoLauncher(unsigned grid, hipStream_t st, const JacoStepArgs& A);
+JacoLauncher jaco_launch_kernel_0, jaco_launch_kernel_1, jaco_launch_kernel_2, jaco_launch_kernel_3, jaco_launch_kernel_4, jaco_launch_kernel_5,
+    jaco_launch_kernel_6, jaco_launch_kernel_7, jaco_launch_kernel_8;
 enum { JK_STEP = 0, JK_LISTED = 1, JK_MEDIUM = 2, JK_MEDIUM_DRAIN = 3, JK_HEAVY = 4, JK_HEAVY_DRAIN = 5, JK_HUGE = 6, JK_HUGE_DRAIN = 7, JK_ARM = 8 };
-void jaco_launch_kernel(int k, unsigned grid, hipStream_t st, const JacoStepArgs& A) {
-  switch (k) {
-    case 0: jaco_launch_kernel_0(grid, st, A); break;
-    case 1: jaco_launch_kernel_1(grid, st, A); break;
-    case 2: jaco_launch_kernel_2(grid, st, A); break;
-    case 3: jaco_launch_kernel_3(grid, st, A); break;
-    case 4: jaco_launch_kernel_4(grid, st, A); break;
-    case 5: jaco_launch_kernel_5(grid, st, A); break;
-    case 6: jaco_launch_kernel_6(grid, st, A); break;
-    case 7: jaco_launch_kernel_7(grid, st, A); break;
-    default: jaco_launch_kernel_8(grid, st, A); break;
-  }
-}
+static JacoLauncher* const jaco_launchers[] = {jaco_launch_kernel_0, jaco_launch_kernel_1, jaco_launch_kernel_2, jaco_launch_kernel_3, jaco_launch_kernel_4,
+                                               jaco_launch_kernel_5, jaco_launch_kernel_6, jaco_launch_kernel_7, jaco_launch_kernel_8};   // indexed by JK_*
+void jaco_launch_kernel(int k, unsigned grid, hipStream_t st, const JacoStepArgs& A) { jaco_launchers[k](grid, st, A); }
 #define JLAUNCHK(h, k, grid, st, A) do { jaco_launch_kernel((k), (grid), (st), (A)); (h)->nlaunch++; } while (0)
 
 static_assert(JFLAG_CON_OVERFLOW == JACO_FLAG_CON_OVERFLOW && JFLAG_EFC_OVERFLOW == JACO_FLAG_EFC_OVERFLOW &&
@@ -50,40 +40,35 @@ enum { JQ_COUNT = 0, JQ_TAKEN = 3, JQ_LIMIT = 6, JQ_LIGHT = 9, JQ_RESERVE = 10, 
 
 struct JacoHandle {
   JacoModelDev model_host;
+  JacoEnvArrays env;    // every array with one row per env (env_arrays.h: the table they are generated from), widths in `words`
+  JacoEnvWords words;
+  // the device buffers the library owns that are NOT one row per env, and their release (the only hand-kept list: keep the two in step)
   JacoModelDev* model_dev = nullptr;
   float* hull_dev = nullptr;
   float* qpos0_dev = nullptr;   // [nq] reset pose, uploaded once (resets never touch host memory)
-  float *qpos = nullptr, *qvel = nullptr, *qacc_ws = nullptr, *sensordata = nullptr, *dbg = nullptr;
-  float *qpos_lo = nullptr, *qvel_lo = nullptr;   // low-order parts of the compensated state (physics_kernel.h, comp_add): zero after any state write from outside
-  unsigned* flags = nullptr;
-  int* stats = nullptr;
-  int* remaining = nullptr;
+  float* dbg = nullptr;
+  unsigned long long* prof = nullptr;
   // tier queues (medium, heavy, huge): lists [3][num_envs] and the control words JQ_* below
   int *qlist = nullptr, *qctl = nullptr;   // both double-buffered: launch N uses lists [qsel][6 B] and control words [qsel][JQ_WORDS]
+  unsigned* order_ctl = nullptr;   // histogram / cursors / cost sum / bucket reference of the ordering passes
+  float* sepdir = nullptr;         // [num_envs][JMAXPAIR][4] separating-direction cache of the hull narrowphase (collision.h)
+  float* goal_buf = nullptr;       // recorded reaching goals (jaco_set_init_buffer; library-owned copy), or nullptr
+  void free_buffers() {
+    for (void* p : {(void*)model_dev, (void*)hull_dev, (void*)qpos0_dev, (void*)dbg, (void*)prof, (void*)qlist, (void*)qctl, (void*)order_ctl, (void*)sepdir, (void*)goal_buf}) if (p) (void)hipFree(p);
+  }
   int qsel = 0;                               // buffer of the next launch
   bool q_ready = false;                       // ... already prepared by the previous launch's routing kernel
   int merge_prepare = 1;                      // option "merge_prepare": 0 = every launch prepares its own buffer with jaco_prepare_kernel (the launch set of rounds 1-4; comparison / regression tests)
-  int* hint = nullptr;                        // [num_envs] tier the env's last step needed
-  bool reset_listed = false;                  // jaco_reset in progress: h->order holds the list of the masked envs
-  int* routed_mark = nullptr;                 // [num_envs] id of the launch that queued the env for a bigger tier before it started
+  bool reset_listed = false;                  // jaco_reset in progress: env.order holds the list of the masked envs
   int launch_id = 0;
   hipStream_t side[3] = {nullptr, nullptr, nullptr};   // the tiers' resident workers run here, concurrently with the light grid
   hipEvent_t ev_pre = nullptr, ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   int pair_list = 1;   // option "pair_list"
-  float* sepdir = nullptr;   // [num_envs][JMAXPAIR][4] separating-direction cache of the hull narrowphase (collision.h)
   int sep_cache = 1;         // option "sep_cache"
   int mpr_pairs = JACO_MPR_PAIRS;   // option "mpr_pairs" (libraries built with -DJACO_MPR_PAIRS=1 only): hull candidates go through MPR two at a time, one per half wave (collision.h mpr_pair2); bit-identical results
   int arm_kernel = 1;        // option "arm_kernel": contact-free steps use the contact-free instantiation (0: the general kernel with its runtime flag, comparison)
   int concurrent = 1, workers = 1024, workers_heavy = 256, workers_huge = 32, tier_return = 1, use_hints = 2, handdown = 1;   // options "concurrent_heavy", "heavy_workers", "hints"
-  float *task_rows = nullptr, *cache = nullptr;
-  float* terminal = nullptr;   // [num_envs][2] (success flag, wb) latched by every terminal step
-  float* terminal_obs = nullptr;   // [num_envs][26] observation of the terminal step (auto_reset)
-  float* goal_buf = nullptr;       // recorded reaching goals (jaco_set_init_buffer; library-owned copy), or nullptr
   int goal_n = 0, goal_stride = 0;
-  float* marker = nullptr;    // [num_envs][2][12] poses of the "hand" / "subgoal_reach" markers (mocap bodies the task layer moves)
-  unsigned* cost = nullptr;   // per env: shader-clock ticks its last step took (>> 4)
-  int* order = nullptr;       // launch order of the env-level light kernel: expensive envs first
-  unsigned* order_ctl = nullptr;   // histogram / cursors / cost sum / bucket reference of the ordering passes
   int schedule = 1;           // option "schedule": 0 = launch envs in index order
   int auto_reset = 0;         // option "auto_reset"
   int min_nsub_sched = 2;     // option "min_nsub_sched": shortest step (substeps) that gets the resident tier workers
@@ -95,7 +80,6 @@ struct JacoHandle {
   int con_cap = 0;
   const float* subgoal = nullptr;   // obs_mode 1: the policy's sub-goal offsets for the "subgoal_reach" marker
   int obs_mode = 0;
-  unsigned long long* prof = nullptr;
   std::vector<float> qpos0;
   int num_envs = 0, device = 0, frame_skip = 50, task = 0, disable_contact = 0;
   uint64_t seed = 0;
@@ -160,28 +144,23 @@ extern "C" int jaco_create(const JacoConfig* cfg, JacoHandle** out) {
   CREATECHK(hipSetDevice(cfg->device));
   const JacoModelDev& m = h->model_host;
   size_t B = (size_t)cfg->num_envs;
+  h->words = jaco_env_words(m.nq, m.nv, m.nsensor);
+  // every per-env array of the table, zeroed, at least one word per env (a model without sensors still gets a sensordata pointer).  qpos, qvel, qacc_ws, marker
+  // (written by jaco_reset_state below) and order (by the scatter / reset kernel of the launch that reads it) were not zeroed before: no read sees the difference.
+#define JENV_X_ALLOC(f, T, w) { const size_t bytes = B * (h->words.f > 0 ? h->words.f : 1) * sizeof(T); CREATECHK(hipMalloc(&h->env.f, bytes)); CREATECHK(hipMemset(h->env.f, 0, bytes)); }
+  JACO_ENV_ARRAYS(JENV_X_ALLOC, 0, 0, 0)
+#undef JENV_X_ALLOC
   CREATECHK(hipMalloc(&h->model_dev, sizeof(JacoModelDev)));
+  CREATECHK(hipMemcpy(h->model_dev, &h->model_host, sizeof(JacoModelDev), hipMemcpyHostToDevice));
   CREATECHK(hipMalloc(&h->hull_dev, hull.size() * sizeof(float) + 16));
-  CREATECHK(hipMalloc(&h->qpos, B * m.nq * sizeof(float)));
-  CREATECHK(hipMalloc(&h->qvel, B * m.nv * sizeof(float)));
-  CREATECHK(hipMalloc(&h->qacc_ws, B * m.nv * sizeof(float)));
-  CREATECHK(hipMalloc(&h->qpos_lo, B * m.nq * sizeof(float)));
-  CREATECHK(hipMalloc(&h->qvel_lo, B * m.nv * sizeof(float)));
-  CREATECHK(hipMemset(h->qpos_lo, 0, B * m.nq * sizeof(float)));
-  CREATECHK(hipMemset(h->qvel_lo, 0, B * m.nv * sizeof(float)));
-  CREATECHK(hipMalloc(&h->sensordata, B * (m.nsensor > 0 ? m.nsensor : 1) * sizeof(float)));
-  CREATECHK(hipMalloc(&h->flags, B * sizeof(unsigned)));
-  CREATECHK(hipMalloc(&h->stats, B * 4 * sizeof(int)));
+  CREATECHK(hipMemcpy(h->hull_dev, hull.data(), hull.size() * sizeof(float), hipMemcpyHostToDevice));
   CREATECHK(hipMalloc(&h->dbg, JDBG_SIZE * sizeof(float)));
-  CREATECHK(hipMalloc(&h->remaining, B * sizeof(int)));
   CREATECHK(hipMalloc(&h->qlist, 2 * 6 * B * sizeof(int)));   // (per tier 2 B slots: an env can come by twice, see the second drain round)
   CREATECHK(hipMalloc(&h->qctl, 2 * JQ_WORDS * sizeof(int)));
   CREATECHK(hipMemset(h->qctl, 0, 2 * JQ_WORDS * sizeof(int)));
+  CREATECHK(hipMalloc(&h->order_ctl, 72 * sizeof(unsigned)));
+  CREATECHK(hipMemset(h->order_ctl, 0, 72 * sizeof(unsigned)));
   // (the separating-direction cache, 16 B x JMAXPAIR per env = 0.8 GB at 65 536 envs, is allocated by the first launch that uses it: launch_step)
-  CREATECHK(hipMalloc(&h->hint, B * sizeof(int)));
-  CREATECHK(hipMemset(h->hint, 0, B * sizeof(int)));
-  CREATECHK(hipMalloc(&h->routed_mark, B * sizeof(int)));
-  CREATECHK(hipMemset(h->routed_mark, 0, B * sizeof(int)));
   {
     int lo = 0, hi = 0;
     CREATECHK(hipDeviceGetStreamPriorityRange(&lo, &hi));   // (hi = numerically lowest = highest priority)
@@ -192,26 +171,6 @@ extern "C" int jaco_create(const JacoConfig* cfg, JacoHandle** out) {
       CREATECHK(hipEventCreateWithFlags(&h->ev_join[t], hipEventDisableTiming));
     }
   }
-  CREATECHK(hipMemset(h->remaining, 0, B * sizeof(int)));
-  CREATECHK(hipMalloc(&h->marker, B * 24 * sizeof(float)));
-  CREATECHK(hipMalloc(&h->cost, B * sizeof(unsigned)));
-  CREATECHK(hipMalloc(&h->order, B * sizeof(int)));
-  CREATECHK(hipMalloc(&h->order_ctl, 72 * sizeof(unsigned)));
-  CREATECHK(hipMemset(h->order_ctl, 0, 72 * sizeof(unsigned)));
-  CREATECHK(hipMemset(h->cost, 0, B * sizeof(unsigned)));
-  CREATECHK(hipMalloc(&h->task_rows, B * JTASK_N * sizeof(float)));
-  CREATECHK(hipMalloc(&h->cache, B * JCACHE_N * sizeof(float)));
-  CREATECHK(hipMalloc(&h->terminal, B * 2 * sizeof(float)));
-  CREATECHK(hipMemset(h->terminal, 0, B * 2 * sizeof(float)));
-  CREATECHK(hipMalloc(&h->terminal_obs, B * 26 * sizeof(float)));
-  CREATECHK(hipMemset(h->terminal_obs, 0, B * 26 * sizeof(float)));
-  CREATECHK(hipMemset(h->task_rows, 0, B * JTASK_N * sizeof(float)));
-  CREATECHK(hipMemset(h->cache, 0, B * JCACHE_N * sizeof(float)));
-  CREATECHK(hipMemcpy(h->model_dev, &h->model_host, sizeof(JacoModelDev), hipMemcpyHostToDevice));
-  CREATECHK(hipMemcpy(h->hull_dev, hull.data(), hull.size() * sizeof(float), hipMemcpyHostToDevice));
-  CREATECHK(hipMemset(h->flags, 0, B * sizeof(unsigned)));
-  CREATECHK(hipMemset(h->stats, 0, B * 4 * sizeof(int)));
-  CREATECHK(hipMemset(h->sensordata, 0, B * (m.nsensor > 0 ? m.nsensor : 1) * sizeof(float)));
   // qpos0 from the raw view of the blob (same joint order as the fused view)
   {
     const char* p = (const char*)cfg->model_blob;
@@ -250,8 +209,10 @@ extern "C" int jaco_destroy(JacoHandle* h) {
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_pre) (void)hipEventDestroy(h->ev_pre);
-  void* ptrs[] = {h->model_dev, h->hull_dev, h->qpos, h->qvel, h->qacc_ws, h->qpos_lo, h->qvel_lo, h->sensordata, h->flags, h->stats, h->dbg, h->prof, h->remaining, h->qlist, h->qctl, h->hint, h->routed_mark, h->task_rows, h->cache, h->cost, h->order, h->marker, h->order_ctl, h->qpos0_dev, h->sepdir, h->terminal, h->terminal_obs, h->goal_buf};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+#define JENV_X_FREE(f, T, w) if (h->env.f) (void)hipFree(h->env.f);
+  JACO_ENV_ARRAYS(JENV_X_FREE, 0, 0, 0)
+#undef JENV_X_FREE
+  h->free_buffers();
   delete h;
   return JACO_OK;
 }
@@ -262,64 +223,68 @@ extern "C" int jaco_dims(const JacoHandle* h, int* nq, int* nv, int* nu, int* ns
   if (nv) *nv = h->model_host.nv;
   if (nu) *nu = h->model_host.nu;
   if (nsensor) *nsensor = h->model_host.nsensor;
-  if (nobs) *nobs = 26;
-  if (nact) *nact = (h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PUSHING) ? 6 : 7;
+  if (nobs) *nobs = JSNAP_OBS_WORDS;
+  if (nact) *nact = jaco_task_nact(h->task);
   return JACO_OK;
 }
 extern "C" int jaco_num_envs(const JacoHandle* h) { return h ? h->num_envs : JACO_EINVAL; }
 
+static int copy_rows(JacoHandle* h, void* dst, const void* src, int words_per_env, hipStream_t st) {   // one per-env array in or out, device to device
+  ENTER(h);
+  HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)h->num_envs * words_per_env * 4, hipMemcpyDeviceToDevice, st));
+  return JACO_OK;
+}
+#define COPY_OUT(h, f, dst, stream) copy_rows((h), (dst), (h)->env.f, (h)->words.f, (hipStream_t)(stream))
+#define COPY_IN(h, f, src, stream) copy_rows((h), (h)->env.f, (src), (h)->words.f, (hipStream_t)(stream))
+#define ZERO_ROWS(h, f, stream) HIPCHK(h, hipMemsetAsync((h)->env.f, 0, (size_t)(h)->num_envs * (h)->words.f * 4, (hipStream_t)(stream)))
+// A state from outside is exactly the floats handed in, so the low halves of what was written are zero; and it starts in the light tier
+// (new positions: the hints go), so that results depend on the state alone.
+static int state_from_outside(JacoHandle* h, hipStream_t st, bool qpos_written, bool qvel_written) {
+  if (qpos_written) { ZERO_ROWS(h, hint, st); ZERO_ROWS(h, qpos_lo, st); }
+  if (qvel_written) ZERO_ROWS(h, qvel_lo, st);
+  return JACO_OK;
+}
 extern "C" int jaco_set_state(JacoHandle* h, const float* qpos, const float* qvel, const float* qacc_ws, void* stream) {
   if (!h) return JACO_EINVAL;
   ENTER(h);
-  hipStream_t st = (hipStream_t)stream;
-  size_t B = h->num_envs;
-  if (qpos) HIPCHK(h, hipMemcpyAsync(h->qpos, qpos, B * h->model_host.nq * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (qpos) HIPCHK(h, hipMemsetAsync(h->hint, 0, B * sizeof(int), st));
-  if (qpos) HIPCHK(h, hipMemsetAsync(h->qpos_lo, 0, B * h->model_host.nq * sizeof(float), st));   // the state handed in is exactly the floats
-  if (qvel) HIPCHK(h, hipMemsetAsync(h->qvel_lo, 0, B * h->model_host.nv * sizeof(float), st));   // a state from outside starts in the light tier: results depend on the state alone
-  if (qvel) HIPCHK(h, hipMemcpyAsync(h->qvel, qvel, B * h->model_host.nv * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (qacc_ws) HIPCHK(h, hipMemcpyAsync(h->qacc_ws, qacc_ws, B * h->model_host.nv * sizeof(float), hipMemcpyDeviceToDevice, st));
-  return JACO_OK;
+  int rc = qpos ? COPY_IN(h, qpos, qpos, stream) : JACO_OK;
+  if (!rc) rc = state_from_outside(h, (hipStream_t)stream, qpos != nullptr, qvel != nullptr);
+  if (qvel && !rc) rc = COPY_IN(h, qvel, qvel, stream);
+  if (qacc_ws && !rc) rc = COPY_IN(h, qacc_ws, qacc_ws, stream);
+  return rc;
 }
 extern "C" int jaco_get_state(JacoHandle* h, float* qpos, float* qvel, float* qacc_ws, void* stream) {
   if (!h) return JACO_EINVAL;
-  ENTER(h);
-  hipStream_t st = (hipStream_t)stream;
-  size_t B = h->num_envs;
-  if (qpos) HIPCHK(h, hipMemcpyAsync(qpos, h->qpos, B * h->model_host.nq * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (qvel) HIPCHK(h, hipMemcpyAsync(qvel, h->qvel, B * h->model_host.nv * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (qacc_ws) HIPCHK(h, hipMemcpyAsync(qacc_ws, h->qacc_ws, B * h->model_host.nv * sizeof(float), hipMemcpyDeviceToDevice, st));
-  return JACO_OK;
+  int rc = qpos ? COPY_OUT(h, qpos, qpos, stream) : JACO_OK;
+  if (qvel && !rc) rc = COPY_OUT(h, qvel, qvel, stream);
+  if (qacc_ws && !rc) rc = COPY_OUT(h, qacc_ws, qacc_ws, stream);
+  return rc;
 }
 
 __global__ void jaco_fill_rows_kernel(float* dst, const float* row, int n, int nenv) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < (size_t)n * nenv) dst[i] = row[i % n];
 }
+static const float* marker_rest_dev(const JacoHandle* h) { return (const float*)((const char*)h->model_dev + offsetof(JacoModelDev, marker_rest)); }   // [2][12], in the model's device copy
 extern "C" int jaco_reset_state(JacoHandle* h, void* stream) {
   if (!h) return JACO_EINVAL;
   ENTER(h);
   hipStream_t st = (hipStream_t)stream;
-  const JacoModelDev& m = h->model_host;
-  size_t B = h->num_envs;
-  size_t total = B * m.nq;
-  JLAUNCH(h, jaco_fill_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, h->qpos, h->qpos0_dev, m.nq, (int)B);
+  const int B = h->num_envs;
+  JLAUNCH(h, jaco_fill_rows_kernel, dim3((unsigned)(((size_t)B * h->words.qpos + 255) / 256)), dim3(256), 0, st, h->env.qpos, h->qpos0_dev, h->words.qpos, B);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemsetAsync(h->qvel, 0, B * m.nv * sizeof(float), st));
-  HIPCHK(h, hipMemsetAsync(h->qacc_ws, 0, B * m.nv * sizeof(float), st));
-  HIPCHK(h, hipMemsetAsync(h->qpos_lo, 0, B * m.nq * sizeof(float), st));
-  HIPCHK(h, hipMemsetAsync(h->qvel_lo, 0, B * m.nv * sizeof(float), st));
-  HIPCHK(h, hipMemsetAsync(h->hint, 0, B * sizeof(int), st));
+  ZERO_ROWS(h, qvel, st);
+  ZERO_ROWS(h, qacc_ws, st);
+  if (int rc = state_from_outside(h, st, true, true)) return rc;
   // markers back to their XML rest pose (sim.reset() restores mocap_pos / mocap_quat)
-  const float* rest = (const float*)((const char*)h->model_dev + offsetof(JacoModelDev, marker_rest));
-  JLAUNCH(h, jaco_fill_rows_kernel, dim3((unsigned)((B * 24 + 255) / 256)), dim3(256), 0, st, h->marker, rest, 24, (int)B);
+  JLAUNCH(h, jaco_fill_rows_kernel, dim3((unsigned)(((size_t)B * h->words.marker + 255) / 256)), dim3(256), 0, st, h->env.marker, marker_rest_dev(h), h->words.marker, B);
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
 
 #define JACO_PLACING_HOLD_SUBSTEPS 150   // reset_frame_skip (env_mujoco_util.py:114)
 struct EnvIO { int mode = JM_CTRL; const float* action = nullptr; float* obs = nullptr; float* reward = nullptr; unsigned char* done = nullptr; const unsigned char* mask = nullptr;
-               bool listed = false; };   // listed: h->order[0 .. order_ctl[67]) holds the envs of `mask` (written by jaco_reset_kernel): launch a small grid over that list
+               bool listed = false; };   // listed: env.order[0 .. order_ctl[67]) holds the envs of `mask` (written by jaco_reset_kernel): launch a small grid over that list
 
 // Launch order for the next env step: envs sorted by the cost of their previous step, most expensive first (32 buckets of
 // 1/8 of the mean cost).  An env step is ~1.5 ms of one wavefront and the expensive ones (hull-hull narrowphase, the
@@ -398,11 +363,6 @@ __global__ __launch_bounds__(1024) void jaco_order_scatter_kernel(const unsigned
     oc[68] = 0u;
   }
 }
-// ... and sizes this launch's workers from what the ordering pass has just counted: per tier, the envs that start there
-// (a medium worker serves ~8 of them in a third of a step, a heavy one ~4, a huge one ~2) plus a reserve for overflows that
-// only show up during the step (a tenth of the previous launch's total demand)
-// Envs whose previous step ended in a bigger tier go there at once: queued here, before the launch, so that the tier's workers
-// find them when they start; the hint is consumed (it is re-earned during the step by whichever tier is really needed).
 // Between the two drain rounds: every workgroup of a drain ends on one claim beyond the queue's end, so `taken` has overshot the
 // end of round one by exactly the grid size; the second round starts where the first one really stopped.
 __global__ void jaco_drain_round2_kernel(int* ctl, int medium_grid, int heavy_grid) {
@@ -513,6 +473,68 @@ __global__ void jaco_prepare_kernel(int* ctl, const int* prev_ctl, int* lists, i
   }
 }
 
+// The kernels' argument block for one launch set, in JacoStepArgs' order.  qlist / qctl: this launch's queue buffer.  What launch_step
+// changes between the launches of a set (routed_mark, order / nslots, handdown, the contact-free kernel's flags) starts out off.
+static JacoStepArgs step_args(const JacoHandle* h, const EnvIO& io, const float* ctrl, int nsub, float* dbg, int dbg_env, int* qlist, int* qctl) {
+  JacoStepArgs A{};
+  A.model = h->model_dev;
+  A.hull = h->hull_dev;
+  A.qpos = h->env.qpos;
+  A.qvel = h->env.qvel;
+  A.qpos_lo = h->env.qpos_lo;
+  A.qvel_lo = h->env.qvel_lo;
+  A.qacc_ws = h->env.qacc_ws;
+  A.ctrl = ctrl ? ctrl : h->env.qvel;   // env modes compute ctrl in-kernel; the pointer only has to be readable
+  A.sensordata = h->env.sensordata;
+  A.flags = h->env.flags;
+  A.stats = h->env.stats;
+  A.remaining = h->env.remaining;
+  for (int t = 0; t < 3; t++) A.q[t] = {qlist + (size_t)t * 2 * h->num_envs, qctl + JQ_COUNT + t, qctl + JQ_TAKEN + t, qctl + JQ_LIMIT + t, qctl + JQ_RESERVE + t};
+  A.launch_id = h->launch_id;
+  A.light_left = qctl + JQ_LIGHT;
+  A.hint = h->use_hints ? h->env.hint : nullptr;
+  A.nenv = h->num_envs;
+  A.nsub = nsub;
+  A.disable_contact = h->disable_contact;
+  A.no_pairlist = !h->pair_list;
+  A.mpr_pairs = h->mpr_pairs;
+  A.sepdir = h->sep_cache ? h->sepdir : nullptr;
+  A.hint_mode = h->use_hints;
+  A.no_tier_return = !h->tier_return;
+  A.env_mode = io.mode;
+  A.mask = io.mask;
+  A.marker = h->env.marker;
+  A.task_id = h->task;
+  A.nact = jaco_task_nact(h->task);
+  A.seed = h->seed;
+  A.task = h->env.task;
+  A.cache = h->env.cache;
+  A.action = io.action;
+  A.noise = h->noise;
+  A.obs_mode = h->obs_mode;
+  A.auto_reset = h->auto_reset && io.mode == JM_STEP && jaco_task_auto_resets(h->task);
+  A.qpos0 = h->qpos0_dev;
+  A.goal_buf = h->goal_buf;
+  A.goal_n = h->goal_n;
+  A.goal_stride = h->goal_stride;
+  A.subgoal = h->subgoal;
+  A.obs = io.obs;
+  A.reward = io.reward;
+  A.done = io.done;
+  A.terminal = h->env.terminal;
+  A.terminal_obs = h->env.terminal_obs;
+  A.cost = h->env.cost;
+  A.prof = h->prof;
+  A.dbg = dbg;
+  A.dbg_env = dbg_env;
+  if (JM_REAL_STEP(io.mode) && h->con_rec) {   // (forward passes and resets record nothing)
+    A.con_rec = h->con_rec;
+    A.con_n = h->con_n;
+    A.con_cap = h->con_cap;
+  }
+  return A;
+}
+
 static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t st, float* dbg, int dbg_env, const EnvIO& io = EnvIO()) {
   if ((!ctrl && io.mode == JM_CTRL) || nsub <= 0) { h->err = "jaco_physics_step: bad arguments"; return JACO_EINVAL; }
 #if JNV > 21
@@ -522,43 +544,28 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   if (io.mode != JM_CTRL) { h->err = "this build of the library (two-arm layout) steps models at the ctrl level only: jaco_physics_step / jaco_get_state / jaco_set_state"; return JACO_EINVAL; }
 #endif
   ENTER(h);
-  JacoStepArgs A{};
-  A.model = h->model_dev; A.hull = h->hull_dev; A.qpos = h->qpos; A.qvel = h->qvel; A.qacc_ws = h->qacc_ws; A.qpos_lo = h->qpos_lo; A.qvel_lo = h->qvel_lo;
-  A.ctrl = ctrl ? ctrl : h->qvel;   // env modes compute ctrl in-kernel; the pointer only has to be readable
-  A.sensordata = h->sensordata; A.flags = h->flags; A.stats = h->stats; A.nenv = h->num_envs; A.nsub = nsub;
   if (h->sep_cache && !h->disable_contact && h->model_host.npair > 0 && !h->sepdir) {   // first use: a handle that never runs contacts with the cache on never pays for it
     const size_t bytes = (size_t)h->num_envs * JMAXPAIR * 4 * sizeof(float);
     HIPCHK(h, hipMalloc(&h->sepdir, bytes));
     HIPCHK(h, hipMemsetAsync(h->sepdir, 0, bytes, st));   // (entries are re-validated by a support query before use: zeros are "no direction known")
   }
-  A.disable_contact = h->disable_contact; A.no_pairlist = !h->pair_list; A.mpr_pairs = h->mpr_pairs; A.sepdir = h->sep_cache ? h->sepdir : nullptr; A.no_tier_return = !h->tier_return; A.dbg = dbg; A.dbg_env = dbg_env; A.prof = h->prof;
   // this launch's queue buffer (lists + control words) and the other one: the previous launch's, and the next launch's
   int* const qctl = h->qctl + h->qsel * JQ_WORDS;
   int* const qctl_other = h->qctl + (h->qsel ^ 1) * JQ_WORDS;
   int* const qlist = h->qlist + (size_t)h->qsel * 6 * h->num_envs;
   int* const qlist_other = h->qlist + (size_t)(h->qsel ^ 1) * 6 * h->num_envs;
-  A.remaining = h->remaining; A.light_left = qctl + JQ_LIGHT; A.hint = h->use_hints ? h->hint : nullptr; A.hint_mode = h->use_hints;
-  for (int t = 0; t < 3; t++) { A.q[t].list = qlist + (size_t)t * 2 * h->num_envs; A.q[t].count = qctl + JQ_COUNT + t; A.q[t].taken = qctl + JQ_TAKEN + t; A.q[t].limit = qctl + JQ_LIMIT + t; A.q[t].reserve = qctl + JQ_RESERVE + t; }
-  A.routed_mark = nullptr; A.launch_id = ++h->launch_id;
-  A.env_mode = io.mode; A.task_id = h->task; A.nact = (h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PUSHING) ? 6 : 7; A.seed = h->seed;
-  A.task = h->task_rows; A.cache = h->cache; A.action = io.action; A.noise = h->noise; A.obs_mode = h->obs_mode; A.subgoal = h->subgoal; A.obs = io.obs; A.reward = io.reward; A.done = io.done; A.terminal = h->terminal; A.terminal_obs = h->terminal_obs; A.goal_buf = h->goal_buf; A.goal_n = h->goal_n; A.goal_stride = h->goal_stride; A.mask = io.mask; A.marker = h->marker;
-  A.cost = h->cost;
-  if (JM_REAL_STEP(io.mode) && h->con_rec) { A.con_rec = h->con_rec; A.con_n = h->con_n; A.con_cap = h->con_cap; }   // (forward passes and resets record nothing)
-  // auto-reset folds draws + sim.forward() + observation into the step wave: the tasks whose reset is nothing more (placing holds the
-  // object for 150 substeps, grasping pre-reaches: those keep the explicit jaco_reset)
-  A.auto_reset = h->auto_reset && io.mode == JM_STEP && (h->task == JACO_TASK_PICKING || h->task == JACO_TASK_REACHING || h->task == JACO_TASK_PICKANDPLACE || h->task == JACO_TASK_PUSHING);
-  A.qpos0 = h->qpos0_dev;
+  ++h->launch_id;
+  JacoStepArgs A = step_args(h, io, ctrl, nsub, dbg, dbg_env, qlist, qctl);
   const bool reorder = io.mode == JM_STEP && h->schedule && nsub >= h->min_nsub_order && h->num_envs >= 4096;
   std::pair<hipEvent_t, hipEvent_t>*ev = nullptr, *kev = nullptr;
   if (h->timing && JM_REAL_STEP(io.mode)) {   // (the masked forward passes of resets are not the kernel being measured)
     if (h->events_used == h->events.size()) {
-      hipEvent_t a, b;
-      HIPCHK(h, hipEventCreate(&a));
-      HIPCHK(h, hipEventCreate(&b));
-      h->events.emplace_back(a, b);
-      HIPCHK(h, hipEventCreate(&a));
-      HIPCHK(h, hipEventCreate(&b));
-      h->kevents.emplace_back(a, b);
+      for (auto* evs : {&h->events, &h->kevents}) {
+        hipEvent_t a, b;
+        HIPCHK(h, hipEventCreate(&a));
+        HIPCHK(h, hipEventCreate(&b));
+        evs->emplace_back(a, b);
+      }
     }
     kev = &h->kevents[h->events_used];
     ev = &h->events[h->events_used++];
@@ -578,7 +585,7 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   // masked reset: the reset kernel has listed its envs; a small grid walks that list instead of 65 536 workgroups finding out one by
   // one that they have nothing to do (0.9 ms per launch)
   unsigned light_grid = (unsigned)h->num_envs;
-  if (io.listed && io.mask) { A.order = h->order; A.nslots = reinterpret_cast<const int*>(h->order_ctl + 67); light_grid = light_grid < 1024u ? light_grid : 1024u; }
+  if (io.listed && io.mask) { A.order = h->env.order; A.nslots = reinterpret_cast<const int*>(h->order_ctl + 67); light_grid = light_grid < 1024u ? light_grid : 1024u; }
   // Light grid for every env.  An env that overflows the light capacities is handed over (queue) to the medium tier, and on
   // to the heavy / huge tiers if need be; an env whose previous step ended in a bigger tier is queued there straight away.
   // Each tier's persistent worker workgroups run concurrently on their own higher-priority stream: started just before the
@@ -594,9 +601,9 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
     HIPCHK(h, hipGetLastError());
   }
   if (routes) {   // queue the envs whose last step ended in a bigger tier, size the tiers' workers, prepare the next launch's buffer
-    JLAUNCH(h, jaco_route_kernel, dim3((unsigned)((h->num_envs + 255) / 256)), dim3(256), 0, st, h->hint, h->routed_mark, A.launch_id, qlist, qctl, h->remaining, h->cost, h->num_envs, nsub,
+    JLAUNCH(h, jaco_route_kernel, dim3((unsigned)((h->num_envs + 255) / 256)), dim3(256), 0, st, h->env.hint, h->env.routed_mark, A.launch_id, qlist, qctl, h->env.remaining, h->env.cost, h->num_envs, nsub,
             h->workers, h->workers_heavy, h->workers_huge, qlist_other, qctl_other, h->order_ctl, io.mode);
-    A.routed_mark = h->routed_mark;
+    A.routed_mark = h->env.routed_mark;
   }
   h->q_ready = routes && h->merge_prepare;   // (the routing kernel has prepared the other buffer either way; with the option off the next launch prepares it again)
   h->qsel ^= 1;
@@ -617,10 +624,10 @@ static int launch_step(JacoHandle* h, const float* ctrl, int nsub, hipStream_t s
   }
   if (reorder) {
     const unsigned ob = (unsigned)((h->num_envs + 1023) / 1024);
-    JLAUNCH(h, jaco_order_hist_kernel, dim3(ob), dim3(1024), 0, st, h->cost, h->order_ctl, h->num_envs, A.routed_mark, A.launch_id);
-    JLAUNCH(h, jaco_order_scatter_kernel, dim3(ob), dim3(1024), 0, st, h->cost, h->order_ctl, h->order, h->num_envs, A.routed_mark, A.launch_id);
+    JLAUNCH(h, jaco_order_hist_kernel, dim3(ob), dim3(1024), 0, st, h->env.cost, h->order_ctl, h->num_envs, A.routed_mark, A.launch_id);
+    JLAUNCH(h, jaco_order_scatter_kernel, dim3(ob), dim3(1024), 0, st, h->env.cost, h->order_ctl, h->env.order, h->num_envs, A.routed_mark, A.launch_id);
     HIPCHK(h, hipGetLastError());
-    A.order = h->order;
+    A.order = h->env.order;
   }
   if (conc) HIPCHK(h, hipEventRecord(h->ev_pre, st));
   if (kev) HIPCHK(h, hipEventRecord(kev->first, st));
@@ -698,8 +705,13 @@ extern "C" int jaco_reset(JacoHandle* h, const uint8_t* mask_dev, float* obs_dev
   ENTER(h);
   hipStream_t st = (hipStream_t)stream;
   const JacoModelDev& m = h->model_host;
-  const float* rest = (const float*)((const char*)h->model_dev + offsetof(JacoModelDev, marker_rest));
-  JacoResetArgs R{h->qpos0_dev, h->qpos, h->qvel, h->qacc_ws, h->qpos_lo, h->qvel_lo, h->task_rows, mask_dev, h->marker, rest, h->num_envs, m.nq, m.nv, h->task, m.nq >= 23, h->seed, {m.base_pos[0], m.base_pos[1], m.base_pos[2]}, h->order, h->order_ctl + 67, GoalBuffer{h->goal_buf, h->goal_n, h->goal_stride}};
+  JacoResetArgs R{};
+  R.qpos0 = h->qpos0_dev; R.qpos = h->env.qpos; R.qvel = h->env.qvel; R.qacc_ws = h->env.qacc_ws; R.qpos_lo = h->env.qpos_lo; R.qvel_lo = h->env.qvel_lo;
+  R.task = h->env.task; R.mask = mask_dev; R.marker = h->env.marker; R.marker_rest = marker_rest_dev(h);
+  R.nenv = h->num_envs; R.nq = m.nq; R.nv = m.nv; R.task_id = h->task; R.has_free = m.nq >= 23; R.seed = h->seed;
+  for (int k = 0; k < 3; k++) R.base[k] = m.base_pos[k];
+  R.list = h->env.order; R.list_count = h->order_ctl + 67;
+  R.goals = GoalBuffer{h->goal_buf, h->goal_n, h->goal_stride};
   if (mask_dev) HIPCHK(h, hipMemsetAsync(h->order_ctl + 67, 0, sizeof(unsigned), st));
   h->reset_listed = mask_dev != nullptr;
   JLAUNCH(h, jaco_reset_kernel, dim3((unsigned)((h->num_envs + 255) / 256)), dim3(256), 0, st, R);
@@ -768,43 +780,13 @@ extern "C" int jaco_set_init_buffer(JacoHandle* h, const float* rows_dev, int nr
   h->goal_n = nrows; h->goal_stride = row_floats;
   return JACO_OK;
 }
-extern "C" int jaco_get_task_state(JacoHandle* h, float* out_dev, void* stream) {
-  if (!h || !out_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out_dev, h->task_rows, (size_t)h->num_envs * JTASK_N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
-extern "C" int jaco_set_task_state(JacoHandle* h, const float* in_dev, void* stream) {
-  if (!h || !in_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(h->task_rows, in_dev, (size_t)h->num_envs * JTASK_N * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
+extern "C" int jaco_get_task_state(JacoHandle* h, float* out_dev, void* stream) { return h && out_dev ? COPY_OUT(h, task, out_dev, stream) : JACO_EINVAL; }
+extern "C" int jaco_set_task_state(JacoHandle* h, const float* in_dev, void* stream) { return h && in_dev ? COPY_IN(h, task, in_dev, stream) : JACO_EINVAL; }
 extern "C" int jaco_task_row_floats(void) { return JTASK_N; }
-extern "C" int jaco_get_terminal_obs(JacoHandle* h, float* out_dev, void* stream) {
-  if (!h || !out_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out_dev, h->terminal_obs, (size_t)h->num_envs * 26 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
-extern "C" int jaco_get_last_terminal(JacoHandle* h, float* out_dev, void* stream) {
-  if (!h || !out_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out_dev, h->terminal, (size_t)h->num_envs * 2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
-extern "C" int jaco_get_markers(JacoHandle* h, float* out_dev, void* stream) {
-  if (!h || !out_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out_dev, h->marker, (size_t)h->num_envs * 24 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
-extern "C" int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream) {
-  if (!h || !in_dev) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(h->marker, in_dev, (size_t)h->num_envs * 24 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
+extern "C" int jaco_get_terminal_obs(JacoHandle* h, float* out_dev, void* stream) { return h && out_dev ? COPY_OUT(h, terminal_obs, out_dev, stream) : JACO_EINVAL; }
+extern "C" int jaco_get_last_terminal(JacoHandle* h, float* out_dev, void* stream) { return h && out_dev ? COPY_OUT(h, terminal, out_dev, stream) : JACO_EINVAL; }
+extern "C" int jaco_get_markers(JacoHandle* h, float* out_dev, void* stream) { return h && out_dev ? COPY_OUT(h, marker, out_dev, stream) : JACO_EINVAL; }
+extern "C" int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream) { return h && in_dev ? COPY_IN(h, marker, in_dev, stream) : JACO_EINVAL; }
 // ---- env snapshots (snapshot.h: the row table and the two per-entry routines, shared with the CPU tests' host build) ------------------
 // One wavefront per entry, four entries per 256-thread block: the wave reads its env / row index once, makes it wave-uniform (the
 // addresses below are then scalar base + lane offset) and moves the row 16 bytes per lane on the snapshot side, dword by dword on the
@@ -829,14 +811,7 @@ __global__ __launch_bounds__(64 * JSNAP_ENTRIES_PER_BLOCK) void jaco_load_envs_k
   r = __builtin_amdgcn_readfirstlane(r);
   jaco_snap_load_entry(T, e, rows + (size_t)r * T.W, lane, 64);
 }
-static JacoSnapTable snapshot_table(const JacoHandle* h) {
-  JacoSnapSrc s;
-  s.qpos = h->qpos; s.qpos_lo = h->qpos_lo; s.qvel = h->qvel; s.qvel_lo = h->qvel_lo; s.qacc_ws = h->qacc_ws; s.sensordata = h->sensordata;
-  s.flags = h->flags; s.stats = h->stats; s.hint = h->hint; s.cost = h->cost; s.task = h->task_rows; s.cache = h->cache; s.marker = h->marker;
-  s.terminal = h->terminal; s.terminal_obs = h->terminal_obs;
-  const JacoModelDev& m = h->model_host;
-  return jaco_snapshot_table(s, m.nq, m.nv, m.nsensor, h->task, h->num_envs);
-}
+static JacoSnapTable snapshot_table(const JacoHandle* h) { return jaco_snapshot_table(jaco_snap_src(h->env), h->words.qpos, h->words.qvel, h->words.sensordata, h->task, h->num_envs); }
 extern "C" int jaco_snapshot_words(const JacoHandle* h) { return h ? snapshot_table(h).W : JACO_EINVAL; }
 static int snapshot_args(JacoHandle* h, const char* who, const int32_t* env_idx, int n, const void* rows) {
   if (n < 0 || n > h->num_envs || !rows || (!env_idx && n != h->num_envs)) {
@@ -905,30 +880,15 @@ extern "C" int jaco_physics_step_debug(JacoHandle* h, const float* ctrl_dev, int
   return JACO_OK;
 }
 
-extern "C" int jaco_get_sensordata(JacoHandle* h, float* out, void* stream) {
-  if (!h || !out) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out, h->sensordata, (size_t)h->num_envs * h->model_host.nsensor * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
-extern "C" int jaco_get_flags(JacoHandle* h, uint32_t* out, void* stream) {
-  if (!h || !out) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out, h->flags, (size_t)h->num_envs * sizeof(unsigned), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
+extern "C" int jaco_get_sensordata(JacoHandle* h, float* out, void* stream) { return h && out ? COPY_OUT(h, sensordata, out, stream) : JACO_EINVAL; }
+extern "C" int jaco_get_flags(JacoHandle* h, uint32_t* out, void* stream) { return h && out ? COPY_OUT(h, flags, out, stream) : JACO_EINVAL; }
 extern "C" int jaco_clear_flags(JacoHandle* h, void* stream) {
   if (!h) return JACO_EINVAL;
   ENTER(h);
-  HIPCHK(h, hipMemsetAsync(h->flags, 0, (size_t)h->num_envs * sizeof(unsigned), (hipStream_t)stream));
+  ZERO_ROWS(h, flags, stream);
   return JACO_OK;
 }
-extern "C" int jaco_get_stats(JacoHandle* h, int32_t* out, void* stream) {
-  if (!h || !out) return JACO_EINVAL;
-  ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out, h->stats, (size_t)h->num_envs * 4 * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return JACO_OK;
-}
+extern "C" int jaco_get_stats(JacoHandle* h, int32_t* out, void* stream) { return h && out ? COPY_OUT(h, stats, out, stream) : JACO_EINVAL; }
 
 extern "C" int jaco_set_option(JacoHandle* h, const char* name, double v) {
   if (!h || !name) return JACO_EINVAL;
@@ -1038,8 +998,8 @@ extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nfram
   }
   ENTER(h);
   Q.model = h->model_dev;
-  Q.qpos = qpos_dev ? qpos_dev : h->qpos;
-  Q.qvel = qvel_dev ? qvel_dev : h->qvel;
+  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
+  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
   if (out) { Q.xpos = out->xpos; Q.xmat = out->xmat; Q.jac = out->jac; Q.qM = out->qM; Q.bias = out->qfrc_bias; }
   Q.nenv = h->num_envs;
   Q.nframes = nframes;

@@ -1,9 +1,9 @@
 // Env snapshots (jaco_save_envs / jaco_load_envs, include/jaco_env.h): the complete per-env state as one row of 32-bit words.
 //
-// ONE table, JACO_SNAPSHOT_FIELDS below, lists every per-env array a row carries.  The field enum, the pointer record the handle fills in,
-// the offsets, the row width W, the save and the load routine (the GPU kernels in jaco_env.hip and the host build of the CPU tests,
-// tests/emu/snapshot_driver.cpp, run the same two functions) are all generated from it: a per-env array added to the library later is
-// added here, in one line, and bumps JSNAP_LAYOUT_VERSION.
+// JACO_SNAPSHOT_FIELDS is the snapshot part of the ONE table of the handle's per-env arrays (env_arrays.h).  The handle's members, their
+// allocation and release are generated from that table; so are the field enum, the offsets, the row width W, the save and the load routine
+// here (the GPU kernels in jaco_env.hip and the CPU tests' host build, tests/emu/emu_driver.cpp, run the same two functions).  Every array of
+// the table is in the row or carries, in the table, the reason why not; a new one is one line there (+ JSNAP_LAYOUT_VERSION if it is state).
 //
 // Row layout: word 0 = fingerprint (layout version, nq, nv, nsensor, JTASK_N, JCACHE_N, task id hashed into one word), words 1-3 zero, then
 // the fields in table order, dword-packed, padded with zeros to a multiple of 4 words (rows of a [n][W] buffer are 16-byte aligned).
@@ -16,9 +16,9 @@
 //    support query along it still shows the gap; otherwise the pair goes through MPR as without the cache -- "any stale or foreign value
 //    is harmless"), which is why option "sep_cache" is bit-neutral.
 //    Its content cannot change a result; a load leaves the destination's entries as they are.
-//  * per-launch scratch: remaining, routed_mark, the tier queues (qlist / qctl), order, order_ctl.  They are rebuilt by every launch;
-//    qctl / order_ctl carry demand and cost figures of the previous launch that size worker grids and bucket the launch order, nothing
-//    a result depends on.
+//  * per-launch scratch: remaining, routed_mark, order (one row per env: JACO_SCRATCH_ARRAYS of the table, each with its reason), the tier
+//    queues (qlist / qctl) and order_ctl.  They are rebuilt by every launch; qctl / order_ctl carry demand and cost figures of the previous
+//    launch that size worker grids and bucket the launch order, nothing a result depends on.
 //  * what the library only points to (noise, sub-goal and contact-record buffers of the caller), the recorded-goal buffer, and the
 //    handle-wide settings (seed, frame_skip, options).
 //  * the random STREAM: it is keyed by (seed, env index, counter) and only the counter (task row, JT_RNG) is state.  A row restored into
@@ -31,39 +31,27 @@
 #ifndef JTASK_N
 #error "snapshot.h needs JTASK_N / JCACHE_N: include physics_kernel.h (env_logic.h) first"
 #endif
+#include "env_arrays.h"
 
 #define JSNAP_LAYOUT_VERSION 1u
 #define JSNAP_HEADER_WORDS 4
-#define JSNAP_OBS_WORDS 26            // width of an observation row (terminal_obs)
 #define JSNAP_FLAG_BAD 0x40000u       // JACO_FLAG_BAD_SNAPSHOT of the public header (bit 18: bits 0-7 and 17 are the step kernels', 8-16 the bail causes)
-
-// field (= member of JacoSnapSrc), words per env.  nq / nv / nsensor are the MODEL's widths (rows of the library's arrays are that wide).
-//   qpos .. qvel_lo   compensated state, both halves (jaco_set_state clears the low halves: this is what it loses)
-//   qacc_ws           solver warm start
-//   sensordata        touch values of the last substep (observation, termination rule)
-//   flags, stats      sticky bits and last-substep statistics travel with the env
-//   hint              tier the env starts its next step in (tiers agree to fp32 rounding only)
-//   cost              ticks of the last step: launch order only (bit-neutral), keeps the schedule of a resumed run
-//   task              task row: JT_RNG draw counter, JT_DONE, step / episode counters, goals, target, gripper ramp
-//   cache             what the controller reads one substep late (JC_*), placing pin
-//   marker            mocap poses of "hand" / "subgoal_reach"
-//   terminal, terminal_obs   latches of the last terminal step
-#define JACO_SNAPSHOT_FIELDS(X, nq, nv, nsensor)                                                                         \
-  X(qpos, nq) X(qpos_lo, nq) X(qvel, nv) X(qvel_lo, nv) X(qacc_ws, nv) X(sensordata, nsensor) X(flags, 1) X(stats, 4)    \
-  X(hint, 1) X(cost, 1) X(task, JTASK_N) X(cache, JCACHE_N) X(marker, 24) X(terminal, 2) X(terminal_obs, JSNAP_OBS_WORDS)
 
 #define JSNAP_X_ENUM(f, w) JSNAP_##f,
 enum JacoSnapFieldId { JACO_SNAPSHOT_FIELDS(JSNAP_X_ENUM, 0, 0, 0) JSNAP_NFIELD };
 #undef JSNAP_X_ENUM
 
-// the arrays themselves ([nenv][words], any 32-bit element type); NULL = this build keeps no such array
-#define JSNAP_X_MEMBER(f, w) void* f = nullptr;
-struct JacoSnapSrc { JACO_SNAPSHOT_FIELDS(JSNAP_X_MEMBER, 0, 0, 0) };
-#undef JSNAP_X_MEMBER
-
 #define JSNAP_X_NAME(f, w) #f,
 static const char* const jaco_snap_field_names[JSNAP_NFIELD] = {JACO_SNAPSHOT_FIELDS(JSNAP_X_NAME, 0, 0, 0)};
 #undef JSNAP_X_NAME
+
+// the fields' arrays ([nenv][words], 32-bit elements): the handle's own (jaco_snap_src) or the CPU emulator's; NULL = this build keeps no such array
+#define JSNAP_X_MEMBER(f, w) void* f = nullptr;
+struct JacoSnapSrc { JACO_SNAPSHOT_FIELDS(JSNAP_X_MEMBER, 0, 0, 0) };
+#undef JSNAP_X_MEMBER
+#define JSNAP_X_SRC(f, w) s.f = a.f;
+static inline JacoSnapSrc jaco_snap_src(const JacoEnvArrays& a) { JacoSnapSrc s; JACO_SNAPSHOT_FIELDS(JSNAP_X_SRC, 0, 0, 0) return s; }
+#undef JSNAP_X_SRC
 
 struct JacoSnapField { uint32_t* base; int words, off; };
 struct JacoSnapTable {

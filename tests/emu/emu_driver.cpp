@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE: runs the unmodified kernel source under the lockstep wavefront emulator.
 // Built by tests/emu/Makefile into every libjaco_emu*.so; used by CPU-side (-m "not gpu") kernel checks: ctrl-level steps (with the
-// contact record of jaco_set_contact_record), env-level calls and robot-configuration queries (jaco_query).
+// contact record of jaco_set_contact_record), env-level calls, robot-configuration queries (jaco_query) and the host build of the env
+// snapshots (jaco_save_envs / jaco_load_envs).
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -10,10 +11,12 @@
 #include "../../include/jaco_env.h"
 #include "../../mujoco_jaco_amd/csrc/model_blob.h"
 #include "../../mujoco_jaco_amd/csrc/physics_kernel.h"
+#include "../../mujoco_jaco_amd/csrc/snapshot.h"
 
 void emu_run_wave(int block, std::function<void()> body);
 
 static_assert(sizeof(JacoContact) == sizeof(JacoContactRec), "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
+static_assert(JSNAP_FLAG_BAD == JACO_FLAG_BAD_SNAPSHOT, "flag bit of snapshot.h and the public header must agree");
 
 extern "C" int emu_dbg_size() { return JDBG_SIZE; }
 extern "C" int emu_lds_bytes() { return (int)sizeof(JacoLDS<JacoLight>); }
@@ -24,6 +27,7 @@ extern "C" int emu_query_lds_bytes() { return (int)sizeof(JacoLDS<JacoArm>); }
 extern "C" int emu_contact_words() { return (int)(sizeof(JacoContact) / 4); }
 extern "C" int emu_task_floats() { return JTASK_N; }
 extern "C" int emu_cache_floats() { return JCACHE_N; }
+extern "C" int emu_task_nact(int task_id) { return jaco_task_nact(task_id); }   // width of the task's action row (jaco_dims)
 
 // the model of the last call: every entry loads its blob into it (the loader starts from a zeroed model and a fresh hull table)
 static JacoModelDev g_model;
@@ -131,7 +135,7 @@ extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = qvel; A.sensordata = sensordata;
   A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = mode == JM_FORWARD ? 1 : frame_skip; A.env_mode = mode; A.task_id = task_id; A.nact = nact;
   A.seed = seed; A.task = task; A.cache = cache; A.action = action; A.noise = noise; A.obs = obs; A.reward = reward; A.done = done; A.marker = marker; A.dbg_env = -1;
-  A.auto_reset = g_auto_reset && mode == JM_STEP && (task_id == 0 || task_id == 2 || task_id == 4 || task_id == 7); A.qpos0 = g_qpos0.empty() ? nullptr : g_qpos0.data();
+  A.auto_reset = g_auto_reset && mode == JM_STEP && jaco_task_auto_resets(task_id); A.qpos0 = g_qpos0.empty() ? nullptr : g_qpos0.data();
   A.goal_buf = g_goal_buf.empty() ? nullptr : g_goal_buf.data(); A.goal_n = g_goal_n; A.goal_stride = g_goal_stride;
   return emu_launch(A, heavy_envs);
 }
@@ -171,4 +175,43 @@ extern "C" int emu_query(const void* blob, long blob_size, int nenv, const float
   emu_grid = nenv;   // (the kernel reads only blockIdx; the grid jaco_query launches)
   for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_query_kernel(Q); });
   return 0;
+}
+
+// ---- env snapshots: the table and the save / load routines of snapshot.h -- the very header the GPU kernels jaco_save_envs_kernel /
+// jaco_load_envs_kernel are compiled from; here one "lane" walks a whole row ------------------------------------------------------------
+extern "C" int snap_nfield() { return JSNAP_NFIELD; }
+extern "C" const char* snap_field_name(int i) { return i >= 0 && i < JSNAP_NFIELD ? jaco_snap_field_names[i] : nullptr; }
+extern "C" int snap_header_words() { return JSNAP_HEADER_WORDS; }
+extern "C" unsigned snap_bad_flag() { return JSNAP_FLAG_BAD; }
+// ptrs[JSNAP_NFIELD]: the arrays in table order (NULL = the caller keeps no such array)
+static JacoSnapTable table_of(void* const* ptrs, int nq, int nv, int nsensor, int task_id, int nenv) {
+  JacoSnapSrc s;
+  int i = 0;
+#define SNAP_X_PTR(f, w) s.f = ptrs ? ptrs[i] : nullptr; i++;
+  JACO_SNAPSHOT_FIELDS(SNAP_X_PTR, 0, 0, 0)
+#undef SNAP_X_PTR
+  return jaco_snapshot_table(s, nq, nv, nsensor, task_id, nenv);
+}
+// words[i], off[i] of every field; returns W
+extern "C" int snap_table(int nq, int nv, int nsensor, int task_id, int* words, int* off, unsigned* fingerprint) {
+  const JacoSnapTable T = table_of(nullptr, nq, nv, nsensor, task_id, 0);
+  for (int i = 0; i < JSNAP_NFIELD; i++) { words[i] = T.f[i].words; off[i] = T.f[i].off; }
+  if (fingerprint) *fingerprint = T.fingerprint;
+  return T.W;
+}
+// the grids of the two kernels, entry by entry (jaco_env.hip: one wavefront per entry)
+extern "C" void snap_save(void* const* ptrs, int nq, int nv, int nsensor, int task_id, int nenv, const int32_t* env_idx, int n, uint32_t* rows) {
+  const JacoSnapTable T = table_of(ptrs, nq, nv, nsensor, task_id, nenv);
+  for (int i = 0; i < n; i++) {
+    int e, r;
+    if (jaco_snap_entry(T, env_idx, nullptr, n, i, &e, &r)) jaco_snap_save_entry(T, e, rows + (size_t)i * T.W, 0, 1);
+  }
+}
+extern "C" void snap_load(void* const* ptrs, int nq, int nv, int nsensor, int task_id, int nenv, const int32_t* env_idx, int n, const uint32_t* rows, int nrows,
+                          const int32_t* row_idx) {
+  const JacoSnapTable T = table_of(ptrs, nq, nv, nsensor, task_id, nenv);
+  for (int i = 0; i < n; i++) {
+    int e, r;
+    if (jaco_snap_entry(T, env_idx, row_idx, nrows, i, &e, &r)) jaco_snap_load_entry(T, e, rows + (size_t)r * T.W, 0, 1);
+  }
 }

@@ -48,6 +48,7 @@ def lib(layout=""):
             getattr(L, "emu_set_" + switch).argtypes = [ctypes.c_int]
         L.emu_get_counter.argtypes = [ctypes.c_int, ctypes.c_int]; L.emu_get_counter.restype = ctypes.c_long
         L.emu_last_terminal.argtypes = []; L.emu_last_terminal.restype = fp
+        L.emu_task_nact.argtypes = [ctypes.c_int]
         _libs[layout] = L
     return _libs[layout]
 
@@ -107,6 +108,7 @@ class EmuJacoEnv(EmuEnv):
     def __init__(self, model="jaco2_curtain_torque", nenv=1, task_id=0, frame_skip=50, seed=0):
         super().__init__(model, nenv)
         self.task_id, self.frame_skip, self.seed = task_id, frame_skip, seed
+        self.nact = self.L.emu_task_nact(task_id)   # (the library's own rule: env_arrays.h jaco_task_nact)
         self.task = np.zeros((nenv, self.L.emu_task_floats()), np.float32)
         self.cache = np.zeros((nenv, self.L.emu_cache_floats()), np.float32)
         self.obs = np.zeros((nenv, 26), np.float32)
@@ -121,7 +123,7 @@ class EmuJacoEnv(EmuEnv):
         fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if a is not None else None
         hv = ctypes.c_int(0)
         self.L.emu_set_obs_mode(int(getattr(self, "obs_mode", 0)))
-        rc = self.L.emu_env_call(self.blob, len(self.blob), self.nenv, mode, self.frame_skip, self.task_id, 6 if self.task_id in (2, 7) else 7, self.seed,
+        rc = self.L.emu_env_call(self.blob, len(self.blob), self.nenv, mode, self.frame_skip, self.task_id, self.nact, self.seed,
                                  fp(self.qpos), fp(self.qvel), fp(self.qacc_ws), fp(self.sensordata),
                                  self.flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), self.stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                                  fp(self.task), fp(self.cache), fp(action), fp(noise), fp(self.obs), fp(self.reward),
@@ -175,6 +177,6 @@ class EmuJacoEnv(EmuEnv):
         return self.obs.copy()
 
     def env_step(self, action, noise=None):
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(action, np.float32), (self.nenv, 6 if self.task_id in (2, 7) else 7)))
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(action, np.float32), (self.nenv, self.nact)))
         self._call(JM_STEP, a, None if noise is None else np.ascontiguousarray(noise, np.float32))
         return self.obs.copy(), self.reward.copy(), self.done.copy()

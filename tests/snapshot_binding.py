@@ -1,38 +1,21 @@
-"""ctypes binding of tests/emu/libjaco_snap*.so -- TEST INFRASTRUCTURE ONLY.
+"""Binding of the env-snapshot entries (snap_*) of tests/emu/libjaco_emu*.so -- TEST INFRASTRUCTURE ONLY.
 
-The host build of the env-snapshot table and its save / load routines (tests/emu/snapshot_driver.cpp over mujoco_jaco_amd/csrc/snapshot.h,
-the header the GPU kernels of jaco_save_envs / jaco_load_envs are compiled from), one library per layout with the layout flags of
-tests/emu/Makefile.  SnapHost wraps a set of per-env numpy arrays (an EmuJacoEnv's, or synthetic ones) as the "handle".
+The host build of the env-snapshot table and its save / load routines (tests/emu/emu_driver.cpp over mujoco_jaco_amd/csrc/snapshot.h, the
+header the GPU kernels of jaco_save_envs / jaco_load_envs are compiled from), in the emulator library of each layout (emu_binding.lib).
+SnapHost wraps a set of per-env numpy arrays (an EmuJacoEnv's, or synthetic ones) as the "handle".
 """
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "mujoco_jaco_amd", "csrc")
-_libs = {}
+import emu_binding
 
-
-def _makefile_var(name):
-    """A variable of tests/emu/Makefile (the layouts' -D flags, the compiler flags): read, not copied, so that the two cannot drift apart."""
-    m = re.search(r"^%s \??= (.*)$" % re.escape(name), open(os.path.join(EMU_DIR, "Makefile")).read(), re.M)
-    return m.group(1).replace("$(CSRC)", CSRC).split() if m else []
+_typed = set()
 
 
 def lib(layout=""):
-    if layout not in _libs:
-        out = os.path.join(EMU_DIR, "libjaco_snap%s.so" % layout)
-        deps = [os.path.join(EMU_DIR, "snapshot_driver.cpp"), os.path.join(EMU_DIR, "Makefile"), os.path.join(ROOT, "include", "jaco_env.h")]
-        deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-        if not os.path.exists(out) or any(os.path.getmtime(d) >= os.path.getmtime(out) for d in deps):
-            # -DJACO_TU=-1: physics_kernel.h defines no kernel (what jaco_env.hip is compiled with); only the row sizes are wanted
-            subprocess.check_call(["g++", *_makefile_var("CXXFLAGS"), *_makefile_var("FLAGS" + layout), "-DJACO_TU=-1", "-shared", "-o", out, "snapshot_driver.cpp"],
-                                  cwd=EMU_DIR)
-        L = ctypes.CDLL(out)
+    L = emu_binding.lib(layout)
+    if layout not in _typed:
         ip, up, vpp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_void_p)
         L.snap_field_name.restype = ctypes.c_char_p
         L.snap_field_name.argtypes = [ctypes.c_int]
@@ -41,8 +24,9 @@ def lib(layout=""):
         L.snap_save.argtypes = [vpp] + [ctypes.c_int] * 5 + [ip, ctypes.c_int, up]
         L.snap_load.argtypes = [vpp] + [ctypes.c_int] * 5 + [ip, ctypes.c_int, up, ctypes.c_int, ip]
         L.snap_save.restype = L.snap_load.restype = None
-        _libs[layout] = L
-    return _libs[layout]
+        L.snap_task_floats, L.snap_cache_floats = L.emu_task_floats, L.emu_cache_floats   # (JTASK_N / JCACHE_N: one entry each in the library)
+        _typed.add(layout)
+    return L
 
 
 def fields(layout=""):
