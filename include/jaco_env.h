@@ -226,6 +226,34 @@ typedef struct JacoQueryOut { float* xpos; float* xmat; float* jac; float* qM; f
 int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nframes, const float* qpos_dev, const float* qvel_dev,
                const JacoQueryOut* out, void* stream);
 
+/* ---- inverse kinematics: which arm configuration puts this frame at this pose?  A damped least-squares iteration per env, all of it
+ * in one kernel launch (mujoco_jaco_amd/csrc/ik.h).  Per env: a seed qpos, a target position and, optionally, a target orientation (unit
+ * quaternion, w first).  Per call: one frame -- `point` is the controlled point in the frame's coordinates, the orientation is the
+ * frame's -- and the options.  Active dofs: the hinge dofs on the chain of the frame's body, intersected with dof_mask (bit d = dof d)
+ * when that is non-zero.  Iteration: p = frame point, e_p = target - p, e_r = rotation vector of R* R^T (0 without an orientation);
+ * converged when |e_p| < tol_pos and (no orientation or |e_r| < tol_rot); dq = J^T (J J^T + damping^2 I)^-1 [e_p; e_r] with J the 6 x
+ * n_active Jacobian at p (rows 3-5 zero without an orientation); dq scaled uniformly so that max|dq| <= max_step; q += dq; limited joints
+ * clamped to their range.  At most max_iters iterations (<= JACO_IK_MAX_ITERS).
+ * Inputs (device): qpos_seed_dev [num_envs][nq] (NULL = the handle's current state), target_pos_dev [num_envs][3], target_quat_dev
+ * [num_envs][4] (NULL = position only).  Outputs (device): qpos_out_dev [num_envs][nq] = the seed row with the active dofs replaced,
+ * every other word copied bit for bit (it may be the seed buffer itself); resid_dev [num_envs][2] = |e_p|, |e_r| of the last evaluation
+ * (or NULL); status_dev [num_envs][2] int32 = iterations taken, converged 0 / 1 (or NULL).  opt_host NULL = the defaults of
+ * JACO_IK_DEFAULTS.  Nothing of the handle is written: the caller applies the result with jaco_set_state.
+ * Asynchronous on `stream` (the handle owns no stream: as every launching call it takes the caller's): one kernel launch, no allocation,
+ * no synchronisation, no host copy (frame and options travel in the kernel arguments).
+ * JACO_EINVAL for a frame body outside [-1, fused bodies), max_iters outside [0, JACO_IK_MAX_ITERS], a non-positive tolerance, damping
+ * or max_step, an empty active set (a world-fixed frame, a free body's frame) and a NULL target position or output. */
+#define JACO_IK_MAX_ITERS 256
+typedef struct JacoIkOptions {
+  float tol_pos, tol_rot;   /* m, rad */
+  float damping, max_step;  /* lambda; rad */
+  int32_t max_iters, reserved;
+  uint64_t dof_mask;        /* 0 = every hinge dof on the frame's chain */
+} JacoIkOptions;
+#define JACO_IK_DEFAULTS {1e-5f, 1e-4f, 0.02f, 0.3f, 60, 0, 0}
+int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt_host, const float* qpos_seed_dev,
+            const float* target_pos_dev, const float* target_quat_dev, float* qpos_out_dev, float* resid_dev, int32_t* status_dev, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

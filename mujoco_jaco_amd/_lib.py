@@ -23,6 +23,22 @@ class JacoQueryOut(ctypes.Structure):
     _fields_ = [("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("jac", ctypes.c_void_p), ("qM", ctypes.c_void_p), ("qfrc_bias", ctypes.c_void_p)]
 
 
+JACO_IK_MAX_ITERS = 256
+
+
+class JacoIkOptions(ctypes.Structure):
+    """JacoIkOptions of include/jaco_env.h; a fresh instance holds the API defaults (JACO_IK_DEFAULTS)."""
+    _fields_ = [("tol_pos", ctypes.c_float), ("tol_rot", ctypes.c_float), ("damping", ctypes.c_float), ("max_step", ctypes.c_float),
+                ("max_iters", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dof_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(tol_pos=1e-5, tol_rot=1e-4, damping=0.02, max_step=0.3, max_iters=60, dof_mask=0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown IK option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
 class JacoContact(ctypes.Structure):
     """JacoContact of include/jaco_env.h: one record of the contact record (jaco_set_contact_record), 96 bytes."""
     _fields_ = [("dist", ctypes.c_float), ("pos", ctypes.c_float * 3), ("frame", ctypes.c_float * 9), ("force", ctypes.c_float * 6),
@@ -86,6 +102,7 @@ SYMBOLS = {
     "jaco_step_time_ms": (_ci, [_vp, ctypes.POINTER(_cd)]),
     "jaco_stage_profile": (_ci, [_vp, ctypes.POINTER(ctypes.c_uint64), _ci]),
     "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "jaco_ik": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1008,3 +1008,30 @@ extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nfram
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- inverse kinematics (ik.h): one wavefront per env, nothing of the handle written ---------------------------------------------
+static_assert(sizeof(JacoIkOptions) == sizeof(JacoIkOpts) && offsetof(JacoIkOptions, tol_pos) == offsetof(JacoIkOpts, tol_pos) &&
+                  offsetof(JacoIkOptions, tol_rot) == offsetof(JacoIkOpts, tol_rot) && offsetof(JacoIkOptions, damping) == offsetof(JacoIkOpts, damping) &&
+                  offsetof(JacoIkOptions, max_step) == offsetof(JacoIkOpts, max_step) && offsetof(JacoIkOptions, max_iters) == offsetof(JacoIkOpts, max_iters) &&
+                  offsetof(JacoIkOptions, dof_mask) == offsetof(JacoIkOpts, dof_mask) && JACO_IK_MAX_ITERS == JIK_MAX_ITERS,
+              "JacoIkOptions of the public header and the kernel's option record must agree");
+extern "C" int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt_host, const float* qpos_seed_dev,
+                       const float* target_pos_dev, const float* target_quat_dev, float* qpos_out_dev, float* resid_dev, int32_t* status_dev, void* stream) {
+  if (!h) return JACO_EINVAL;
+  if (!frame_host || !target_pos_dev || !qpos_out_dev) { h->err = "jaco_ik: the frame, the target positions and the output qpos are required"; return JACO_EINVAL; }
+  const JacoIkOptions defaults = JACO_IK_DEFAULTS;
+  JacoIkArgs Q{};
+  memcpy(&Q.fr, frame_host, sizeof(JacoFrame));
+  memcpy(&Q.opt, opt_host ? opt_host : &defaults, sizeof(JacoIkOptions));
+  if (const char* why = jaco_ik_resolve(h->model_host, Q.fr, Q.opt, &Q.active)) { h->err = std::string("jaco_ik: ") + why; return JACO_EINVAL; }
+  ENTER(h);
+  Q.model = h->model_dev;
+  Q.qpos = qpos_seed_dev ? qpos_seed_dev : h->env.qpos;
+  Q.target_pos = target_pos_dev; Q.target_quat = target_quat_dev;
+  Q.qpos_out = qpos_out_dev; Q.resid = resid_dev; Q.status = status_dev;
+  Q.nenv = h->num_envs;
+  jaco_launch_ik((unsigned)h->num_envs, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

@@ -2803,3 +2803,5 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 
 // the robot-configuration query kernel (jaco_query): translation unit 9
 #include "query.h"
+// the inverse-kinematics kernel (jaco_ik): translation unit 10
+#include "ik.h"

@@ -194,6 +194,27 @@ class BatchedMujoco:
                                     ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
         return res
 
+    # ---- inverse kinematics (jaco_ik: a damped least-squares solve per env, one launch)
+    def ik(self, frame, target_pos, target_quat=None, qpos=None, **options):
+        """Which arm configuration puts `frame` (_lib.JacoFrame; FrameTable.jaco_frame(name, point=...): `point` is the controlled point)
+        at target_pos [B, 3] and, if given, at the orientation target_quat [B, 4] (unit quaternions, w first)?  Seed: qpos [B, nq], default
+        the current state.  options: tol_pos, tol_rot, damping, max_step, max_iters, dof_mask (include/jaco_env.h).  One launch on the
+        current stream; {"qpos": [B, nq] the seed with the active dofs replaced, "converged": [B] bool, "iters": [B] int32, "err_pos" /
+        "err_rot": [B] the last |e_p| / |e_r|}.  The sim's state is not touched: apply the result with set_state."""
+        B, dev = self.num_envs, self.device
+        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
+        tp, tq, seed = prep(target_pos, 3), prep(target_quat, 4), prep(qpos, self.nq)
+        if tp is None:
+            raise ValueError("ik: target_pos is required")
+        out = torch.empty(B, self.nq, device=dev)
+        resid = torch.empty(B, 2, device=dev)
+        status = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        opt = _lib.JacoIkOptions(**options)
+        self._chk(self.L.jaco_ik(self.h, ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
+                                 self._dev(seed, self.nq), self._dev(tp, 3), self._dev(tq, 4), ctypes.c_void_p(out.data_ptr()),
+                                 ctypes.c_void_p(resid.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream()))
+        return {"qpos": out, "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

@@ -222,6 +222,22 @@ class BatchedMujocoConfig:
         i = self._register(name)
         return mat2quat(self._result(q)["xmat"][:, i])
 
+    def ik(self, name, pos, quat=None, q=None, x=None, **options):
+        """([num_envs, n_arm] arm angles, [num_envs] converged): the configuration that puts the point x (3-vector in the body frame,
+        default the body origin) of body `name` at pos [num_envs, 3] -- Tx(name, q=result, x=x) ~ pos -- and, with quat [num_envs, 4]
+        (w first), the body at that orientation.  Seed: q ([num_envs, n_arm] arm angles spliced into the current qpos, as every
+        accessor's q), default the current state.  options: tol_pos, tol_rot, damping, max_step, max_iters, dof_mask (BatchedMujoco.ik).
+        One jaco_ik launch; the sim's state is not touched."""
+        seed = None
+        if q is not None:
+            import torch
+            seed = self.sim.get_state()[0]
+            seed[:, self.arm_qadr] = torch.as_tensor(q, dtype=seed.dtype, device=seed.device).reshape(seed.shape[0], self.n_arm)
+            seed = seed.contiguous()
+        frame = self.table.jaco_frame(name, point=np.zeros(3) if x is None else np.asarray(x, np.float64).reshape(3))
+        r = self.sim.ik(frame, pos, quat, seed, **options)
+        return r["qpos"][:, self.arm_qadr], r["converged"]
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
