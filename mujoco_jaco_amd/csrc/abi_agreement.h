@@ -1,0 +1,23 @@
+// The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h and ik.h) and snapshot.h.  The library's host unit
+// (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
+#pragma once
+#include <cstddef>
+
+static_assert(JFLAG_CON_OVERFLOW == JACO_FLAG_CON_OVERFLOW && JFLAG_EFC_OVERFLOW == JACO_FLAG_EFC_OVERFLOW &&
+                  JFLAG_CAND_OVERFLOW == JACO_FLAG_CAND_OVERFLOW && JFLAG_NAN == JACO_FLAG_NAN &&
+                  JFLAG_SOLVER_MAXITER == JACO_FLAG_SOLVER_MAXITER && JFLAG_HEAVY_TIER == JACO_FLAG_HEAVY_TIER,
+              "flag bits of the kernel and the public header must agree");
+static_assert(JSNAP_FLAG_BAD == JACO_FLAG_BAD_SNAPSHOT, "flag bit of snapshot.h and the public header must agree");
+static_assert(sizeof(JacoContact) == sizeof(JacoContactRec) && offsetof(JacoContact, force) == offsetof(JacoContactRec, force) &&
+                  offsetof(JacoContact, geom) == offsetof(JacoContactRec, geom) && offsetof(JacoContact, dim) == offsetof(JacoContactRec, dim) &&
+                  JACO_CONTACT_MAX_CAPACITY == JCONREC_MAX_CAPACITY,
+              "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
+static_assert(sizeof(JacoFrame) == sizeof(JacoQueryFrame) && offsetof(JacoFrame, pos) == offsetof(JacoQueryFrame, pos) &&
+                  offsetof(JacoFrame, mat) == offsetof(JacoQueryFrame, mat) && offsetof(JacoFrame, point) == offsetof(JacoQueryFrame, point) &&
+                  JACO_QUERY_MAX_FRAMES == JQ_MAXFRAMES, "JacoFrame of the public header and the kernel's frame record must agree");
+static_assert(sizeof(JacoIkOptions) == sizeof(JacoIkOpts) && offsetof(JacoIkOptions, tol_pos) == offsetof(JacoIkOpts, tol_pos) &&
+                  offsetof(JacoIkOptions, tol_rot) == offsetof(JacoIkOpts, tol_rot) && offsetof(JacoIkOptions, damping) == offsetof(JacoIkOpts, damping) &&
+                  offsetof(JacoIkOptions, max_step) == offsetof(JacoIkOpts, max_step) && offsetof(JacoIkOptions, max_iters) == offsetof(JacoIkOpts, max_iters) &&
+                  offsetof(JacoIkOptions, dof_mask) == offsetof(JacoIkOpts, dof_mask) && JACO_IK_MAX_ITERS == JIK_MAX_ITERS,
+              "JacoIkOptions of the public header and the kernel's option record must agree");

@@ -359,6 +359,23 @@ JDEV void reset_draws(int task_id, unsigned long long seed, unsigned env, int ha
 #undef JRU
   t[JT_RNG] = rng_slot(c);
 }
+// One env's reset, sim.reset() + the draws above: what jaco_reset_kernel does for each env of its mask (jaco_env.hip: one thread per env)
+// and what the CPU tests' host build calls for one env.  The forward pass and the observation are launches of their own.
+struct JacoResetArgs {
+  const float* qpos0; float* qpos; float* qvel; float* qacc_ws; float* qpos_lo; float* qvel_lo; float* task; const unsigned char* mask; float* marker; const float* marker_rest;
+  int nenv, nq, nv, task_id, has_free; unsigned long long seed;
+  float base[3];   // link1 position: the reaching goal's orientation looks along base -> goal (env_mujoco_util.py:201-205)
+  int* list; unsigned* list_count;   // the reset envs, for the launches that follow (forward pass, placing hold)
+  GoalBuffer goals;
+};
+JDEV void jaco_reset_env(const JacoResetArgs& R, int e) {
+  float* t = R.task + (size_t)e * JTASK_N;
+  float* q = R.qpos + (size_t)e * R.nq;
+  for (int k = 0; k < R.nq; k++) { q[k] = R.qpos0[k]; if (R.qpos_lo) R.qpos_lo[(size_t)e * R.nq + k] = 0.f; }   // (low halves: nullptr = the caller keeps none, as JacoStepArgs)
+  for (int k = 0; k < R.nv; k++) { R.qvel[(size_t)e * R.nv + k] = 0.f; R.qacc_ws[(size_t)e * R.nv + k] = 0.f; if (R.qvel_lo) R.qvel_lo[(size_t)e * R.nv + k] = 0.f; }
+  for (int k = 0; k < 24; k++) R.marker[(size_t)e * 24 + k] = R.marker_rest[k];   // sim.reset(): markers back to their XML pose
+  reset_draws(R.task_id, R.seed, (unsigned)e, R.has_free, R.base, q, t, R.goals);   // (shared with the in-kernel auto-reset)
+}
 
 // ---------------------------------------------------------------- a4/a5: operational-space controller on the wave
 // 6x6 Gauss-Jordan, one matrix row per lane (lanes 0..5), no pivoting (SPD input). B in: identity row; out: inverse row.

@@ -21,7 +21,7 @@
 #pragma once
 
 #define JIK_MAX_ITERS 256   // = JACO_IK_MAX_ITERS
-struct JacoIkOpts {         // = JacoIkOptions of include/jaco_env.h (static_assert in jaco_env.hip)
+struct JacoIkOpts {         // = JacoIkOptions of include/jaco_env.h (static_assert in abi_agreement.h)
   float tol_pos, tol_rot, damping, max_step;
   int max_iters, reserved;
   unsigned long long dof_mask;   // 0: every hinge dof on the frame's chain

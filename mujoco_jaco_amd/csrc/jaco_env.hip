@@ -14,6 +14,7 @@
 #include "model_blob.h"
 #include "physics_kernel.h"
 #include "snapshot.h"
+#include "abi_agreement.h"
 
 // the physics kernels live in their own translation units (kernels.hip, one per kernel)
 typedef void JacoLauncher(unsigned grid, hipStream_t st, const JacoStepArgs& A);
@@ -24,11 +25,6 @@ static JacoLauncher* const jaco_launchers[] = {jaco_launch_kernel_0, jaco_launch
                                                jaco_launch_kernel_5, jaco_launch_kernel_6, jaco_launch_kernel_7, jaco_launch_kernel_8};   // indexed by JK_*
 void jaco_launch_kernel(int k, unsigned grid, hipStream_t st, const JacoStepArgs& A) { jaco_launchers[k](grid, st, A); }
 #define JLAUNCHK(h, k, grid, st, A) do { jaco_launch_kernel((k), (grid), (st), (A)); (h)->nlaunch++; } while (0)
-
-static_assert(JFLAG_CON_OVERFLOW == JACO_FLAG_CON_OVERFLOW && JFLAG_EFC_OVERFLOW == JACO_FLAG_EFC_OVERFLOW &&
-                  JFLAG_CAND_OVERFLOW == JACO_FLAG_CAND_OVERFLOW && JFLAG_NAN == JACO_FLAG_NAN &&
-                  JFLAG_SOLVER_MAXITER == JACO_FLAG_SOLVER_MAXITER && JFLAG_HEAVY_TIER == JACO_FLAG_HEAVY_TIER,
-              "flag bits of the kernel and the public header must agree");
 
 // Queue control words (ints): per tier t (0 medium, 1 heavy, 2 huge) JQ_COUNT + t appended, JQ_TAKEN + t claimed, JQ_LIMIT + t workers
 // that start, JQ_RESERVE + t workers that stay when the queue runs dry; JQ_LIGHT light workgroups still running; JQ_ROUTED envs
@@ -125,7 +121,7 @@ extern "C" int jaco_create(const JacoConfig* cfg, JacoHandle** out) {
   JacoHandle* h = new JacoHandle();
   std::vector<float> hull;
   std::string err;
-  if (jaco_model_from_blob(cfg->model_blob, cfg->model_blob_size, &h->model_host, &hull, &err)) {
+  if (jaco_model_from_blob(cfg->model_blob, cfg->model_blob_size, &h->model_host, &hull, &err, &h->qpos0)) {
     g_create_error = "jaco_create: " + err;
     delete h;
     return JACO_EINVAL;
@@ -171,26 +167,8 @@ extern "C" int jaco_create(const JacoConfig* cfg, JacoHandle** out) {
       CREATECHK(hipEventCreateWithFlags(&h->ev_join[t], hipEventDisableTiming));
     }
   }
-  // qpos0 from the raw view of the blob (same joint order as the fused view)
-  {
-    const char* p = (const char*)cfg->model_blob;
-    int n = *(const int32_t*)(p + 8);
-    size_t off = 16;
-    for (int i = 0; i < n; i++) {
-      std::string name(p + off, strnlen(p + off, 32));
-      int code = *(const int32_t*)(p + off + 32), count = *(const int32_t*)(p + off + 36);
-      off += 40;
-      size_t nb = (size_t)count * (code == 0 ? 8 : 4);
-      if (name == "qpos0" && code == 0) {
-        h->qpos0.resize(count);
-        for (int k = 0; k < count; k++) h->qpos0[k] = (float)((const double*)(p + off))[k];
-      }
-      off += nb + ((8 - nb % 8) % 8);
-    }
-    if ((int)h->qpos0.size() != m.nq) { g_create_error = "jaco_create: qpos0 missing"; jaco_destroy(h); return JACO_EINVAL; }
-    CREATECHK(hipMalloc(&h->qpos0_dev, m.nq * sizeof(float)));
-    CREATECHK(hipMemcpy(h->qpos0_dev, h->qpos0.data(), m.nq * sizeof(float), hipMemcpyHostToDevice));
-  }
+  CREATECHK(hipMalloc(&h->qpos0_dev, m.nq * sizeof(float)));
+  CREATECHK(hipMemcpy(h->qpos0_dev, h->qpos0.data(), m.nq * sizeof(float), hipMemcpyHostToDevice));
   *out = h;
   int rc = jaco_reset_state(h, nullptr);
   if (rc) { g_create_error = h->err; jaco_destroy(h); *out = nullptr; return rc; }
@@ -663,23 +641,11 @@ extern "C" int jaco_physics_step(JacoHandle* h, const float* ctrl_dev, int nsub,
   return launch_step(h, ctrl_dev, nsub, (hipStream_t)stream, nullptr, -1);
 }
 // ---- env level: reset / step with the reference's Gym-style semantics, batched -------------------------
-struct JacoResetArgs {
-  const float* qpos0; float* qpos; float* qvel; float* qacc_ws; float* qpos_lo; float* qvel_lo; float* task; const unsigned char* mask; float* marker; const float* marker_rest;
-  int nenv, nq, nv, task_id, has_free; unsigned long long seed;
-  float base[3];   // link1 position: the reaching goal's orientation looks along base -> goal (env_mujoco_util.py:201-205)
-  int* list; unsigned* list_count;   // the reset envs, for the launches that follow (forward pass, placing hold)
-  GoalBuffer goals;
-};
 __global__ void jaco_reset_kernel(JacoResetArgs R) {
   int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (e >= R.nenv || (R.mask && !R.mask[e])) return;
   if (R.mask) R.list[atomicAdd(R.list_count, 1u)] = e;
-  float* t = R.task + (size_t)e * JTASK_N;
-  float* q = R.qpos + (size_t)e * R.nq;
-  for (int k = 0; k < R.nq; k++) { q[k] = R.qpos0[k]; R.qpos_lo[(size_t)e * R.nq + k] = 0.f; }
-  for (int k = 0; k < R.nv; k++) { R.qvel[(size_t)e * R.nv + k] = 0.f; R.qacc_ws[(size_t)e * R.nv + k] = 0.f; R.qvel_lo[(size_t)e * R.nv + k] = 0.f; }
-  for (int k = 0; k < 24; k++) R.marker[(size_t)e * 24 + k] = R.marker_rest[k];   // sim.reset(): markers back to their XML pose
-  reset_draws(R.task_id, R.seed, (unsigned)e, R.has_free, R.base, q, t, R.goals);          // (env_logic.h: shared with the in-kernel auto-reset)
+  jaco_reset_env(R, e);   // (env_logic.h: sim.reset() + the draws, shared with the CPU tests' host build)
 }
 
 extern "C" int jaco_forward(JacoHandle* h, float* obs_dev, void* stream) {
@@ -750,17 +716,10 @@ extern "C" int jaco_set_noise(JacoHandle* h, const float* noise_dev) {
   h->noise = noise_dev;
   return JACO_OK;
 }
-static_assert(sizeof(JacoContact) == sizeof(JacoContactRec) && offsetof(JacoContact, force) == offsetof(JacoContactRec, force) &&
-              offsetof(JacoContact, geom) == offsetof(JacoContactRec, geom) && offsetof(JacoContact, dim) == offsetof(JacoContactRec, dim),
-              "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
 extern "C" int jaco_set_contact_record(JacoHandle* h, JacoContact* rec_dev, int32_t* ncon_dev, int capacity) {
   if (!h) return JACO_EINVAL;
   if (!rec_dev) { h->con_rec = nullptr; h->con_n = nullptr; h->con_cap = 0; return JACO_OK; }
-  if (!ncon_dev || capacity < 1 || capacity > JACO_CONTACT_MAX_CAPACITY) {
-    h->err = "jaco_set_contact_record: needs a count buffer and 1 <= capacity <= " + std::to_string(JACO_CONTACT_MAX_CAPACITY);
-    return JACO_EINVAL;
-  }
-  if ((reinterpret_cast<uintptr_t>(rec_dev) & 15u) != 0) { h->err = "jaco_set_contact_record: the record buffer must be 16-byte aligned"; return JACO_EINVAL; }
+  if (const char* why = jaco_contact_record_check(rec_dev, ncon_dev, capacity)) { h->err = std::string("jaco_set_contact_record: ") + why; return JACO_EINVAL; }
   h->con_rec = reinterpret_cast<JacoContactRec*>(rec_dev); h->con_n = ncon_dev; h->con_cap = capacity;
   return JACO_OK;
 }
@@ -791,7 +750,6 @@ extern "C" int jaco_set_markers(JacoHandle* h, const float* in_dev, void* stream
 // One wavefront per entry, four entries per 256-thread block: the wave reads its env / row index once, makes it wave-uniform (the
 // addresses below are then scalar base + lane offset) and moves the row 16 bytes per lane on the snapshot side, dword by dword on the
 // side of the library's arrays.  Nothing is shared between waves: an entry that is out of range is skipped by its own wave.
-static_assert(JSNAP_FLAG_BAD == JACO_FLAG_BAD_SNAPSHOT, "flag bit of snapshot.h and the public header must agree");
 #define JSNAP_ENTRIES_PER_BLOCK 4
 __global__ __launch_bounds__(64 * JSNAP_ENTRIES_PER_BLOCK) void jaco_save_envs_kernel(JacoSnapTable T, const int32_t* env_idx, int n, uint32_t* rows) {
   const int i = (int)blockIdx.x * JSNAP_ENTRIES_PER_BLOCK + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
@@ -977,32 +935,18 @@ extern "C" int jaco_step_time_ms(JacoHandle* h, double* avg_ms) {
 }
 
 // ---- robot-configuration queries (query.h): one wavefront per env, nothing of the handle written --------------------------------
-static_assert(sizeof(JacoFrame) == sizeof(JacoQueryFrame) && offsetof(JacoFrame, pos) == offsetof(JacoQueryFrame, pos) &&
-                  offsetof(JacoFrame, mat) == offsetof(JacoQueryFrame, mat) && offsetof(JacoFrame, point) == offsetof(JacoQueryFrame, point) &&
-                  JACO_QUERY_MAX_FRAMES == JQ_MAXFRAMES, "JacoFrame of the public header and the kernel's frame record must agree");
 extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nframes, const float* qpos_dev, const float* qvel_dev,
                           const JacoQueryOut* out, void* stream) {
   if (!h) return JACO_EINVAL;
-  if (nframes < 0 || nframes > JACO_QUERY_MAX_FRAMES || (nframes > 0 && !frames_host)) {
-    h->err = "jaco_query: nframes " + std::to_string(nframes) + " outside [0, " + std::to_string(JACO_QUERY_MAX_FRAMES) + "]";
-    return JACO_EINVAL;
-  }
   JacoQueryArgs Q{};
-  for (int f = 0; f < nframes; f++) {
-    if (frames_host[f].body < -1 || frames_host[f].body >= h->model_host.nbody) {
-      h->err = "jaco_query: frame " + std::to_string(f) + ": body " + std::to_string(frames_host[f].body) + " outside [-1, " +
-               std::to_string(h->model_host.nbody) + ")";
-      return JACO_EINVAL;
-    }
-    memcpy(&Q.fr[f], &frames_host[f], sizeof(JacoFrame));
-  }
+  const std::string why = jaco_query_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, &Q);
+  if (!why.empty()) { h->err = "jaco_query: " + why; return JACO_EINVAL; }
   ENTER(h);
   Q.model = h->model_dev;
   Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
   Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
   if (out) { Q.xpos = out->xpos; Q.xmat = out->xmat; Q.jac = out->jac; Q.qM = out->qM; Q.bias = out->qfrc_bias; }
   Q.nenv = h->num_envs;
-  Q.nframes = nframes;
   jaco_launch_query((unsigned)h->num_envs, (hipStream_t)stream, Q);
   h->nlaunch++;
   HIPCHK(h, hipGetLastError());
@@ -1010,11 +954,6 @@ extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nfram
 }
 
 // ---- inverse kinematics (ik.h): one wavefront per env, nothing of the handle written ---------------------------------------------
-static_assert(sizeof(JacoIkOptions) == sizeof(JacoIkOpts) && offsetof(JacoIkOptions, tol_pos) == offsetof(JacoIkOpts, tol_pos) &&
-                  offsetof(JacoIkOptions, tol_rot) == offsetof(JacoIkOpts, tol_rot) && offsetof(JacoIkOptions, damping) == offsetof(JacoIkOpts, damping) &&
-                  offsetof(JacoIkOptions, max_step) == offsetof(JacoIkOpts, max_step) && offsetof(JacoIkOptions, max_iters) == offsetof(JacoIkOpts, max_iters) &&
-                  offsetof(JacoIkOptions, dof_mask) == offsetof(JacoIkOpts, dof_mask) && JACO_IK_MAX_ITERS == JIK_MAX_ITERS,
-              "JacoIkOptions of the public header and the kernel's option record must agree");
 extern "C" int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt_host, const float* qpos_seed_dev,
                        const float* target_pos_dev, const float* target_quat_dev, float* qpos_out_dev, float* resid_dev, int32_t* status_dev, void* stream) {
   if (!h) return JACO_EINVAL;

@@ -60,7 +60,7 @@ void quat2mat(const double* q, float* M) {
 void cp3(float* d, const double* s) { d[0] = (float)s[0]; d[1] = (float)s[1]; d[2] = (float)s[2]; }
 }  // namespace
 
-int jaco_model_from_blob(const void* buf, size_t size, JacoModelDev* m, std::vector<float>* hull, std::string* error) {
+int jaco_model_from_blob(const void* buf, size_t size, JacoModelDev* m, std::vector<float>* hull, std::string* error, std::vector<float>* qpos0) {
   Blob B;
   memset(m, 0, sizeof(*m));
 #define FAIL(msg) do { *error = (msg); return -1; } while (0)
@@ -78,6 +78,12 @@ int jaco_model_from_blob(const void* buf, size_t size, JacoModelDev* m, std::vec
   if (!ts || !gr || !tol || !mi || !mt || !it || !mpi) FAIL(B.err);
   m->timestep = (float)*ts; m->timestep_lo = (float)(*ts - (double)m->timestep); m->compensated = 1; cp3(m->gravity, gr); m->tolerance = (float)*tol; m->meaninertia = (float)*mi;
   m->mpr_tolerance = (float)*mt; m->iterations = *it; m->mpr_iterations = *mpi; m->ls_iterations = 50; m->ls_tolerance = 0.01f; m->mpr_output = 1;
+  // ---- reset pose: the raw view's qpos0 (same joint order as the fused view)
+  if (qpos0) {
+    const double* qp0 = B.f64("qpos0", nq);
+    if (!qp0) FAIL("qpos0 missing");
+    qpos0->assign(qp0, qp0 + nq);
+  }
 
   // ---- bodies
   const int32_t *par = B.i32("f_parent", nb), *jt = B.i32("f_jtype", nb), *qa = B.i32("f_qposadr", nb), *da = B.i32("f_dofadr", nb);

@@ -14,6 +14,7 @@
 // Per-body / per-row state lives in LDS; vectors of length nv live one element per lane and are
 // broadcast with v_readlane; small reductions use DPP butterflies (jaco/wave_ops.h).
 #pragma once
+#include <stdint.h>
 #include <jaco/model_dev.h>
 #include <jaco/wave_ops.h>
 
@@ -116,13 +117,23 @@ JDEV void jprof_stamp(JProfCtx& pc, int i, int lane) {
 #define JSTAMP_NARROW(i)
 #endif
 
-// One contact of the contact record (jaco_set_contact_record): = JacoContact of include/jaco_env.h (static_assert in jaco_env.hip), 96 bytes
+// One contact of the contact record (jaco_set_contact_record): = JacoContact of include/jaco_env.h (static_assert in abi_agreement.h), 96 bytes
 struct JacoContactRec {
   float dist, pos[3], frame[9];   // MuJoCo's contact: distance, position, frame (row 0 = normal, from geom 1 towards geom 2)
   float force[6];                 // mj_contactForce (pyramidal cone): normal, two tangential, torsional, two rolling, in the contact frame
   int geom[2], body[2], dim;      // the pair's kernel geom ids (JacoPairParam g1 / g2), the geoms' original (unfused) bodies, condim
 };
 #define JCONREC_WORDS 24
+#define JCONREC_MAX_CAPACITY 1024   // = JACO_CONTACT_MAX_CAPACITY
+#define JSTR_(x) #x
+#define JSTR(x) JSTR_(x)
+// The host half shared by jaco_set_contact_record (jaco_env.hip) and the emulator's ctrl-level entry, for a record that is on (rec not
+// null): the count buffer, the capacity range, whole 16-byte stores.  Returns nullptr, or what is wrong.
+static inline const char* jaco_contact_record_check(const void* rec, const int* ncon, int capacity) {
+  if (!ncon || capacity < 1 || capacity > JCONREC_MAX_CAPACITY) return "needs a count buffer and 1 <= capacity <= " JSTR(JCONREC_MAX_CAPACITY);
+  if ((reinterpret_cast<uintptr_t>(rec) & 15u) != 0) return "the record buffer must be 16-byte aligned";
+  return nullptr;
+}
 
 // Launch modes (JacoStepArgs::env_mode, described there), and the rules the kernels and the host apply to them.  The rules are macros on
 // purpose: a function call, even a forceinline one, reaches the optimiser as a different instruction stream than the same test written in

@@ -7,9 +7,10 @@
 // outputs.  Nothing is written back to the env's state, task row, cache, flags or sensordata.
 // Included at the end of physics_kernel.h; the kernel is translation unit 9 (kernels.hip -DJACO_TU=9).
 #pragma once
+#include <string>
 
 #define JQ_MAXFRAMES 16   // = JACO_QUERY_MAX_FRAMES
-struct JacoQueryFrame {   // = JacoFrame of include/jaco_env.h (static_assert in jaco_env.hip)
+struct JacoQueryFrame {   // = JacoFrame of include/jaco_env.h (static_assert in abi_agreement.h)
   int body;               // fused body index, -1: world-fixed
   float pos[3], mat[9];   // frame pose in that body's frame (row-major rotation)
   float point[3];         // Jacobian reference point, in the frame's coordinates
@@ -26,6 +27,20 @@ struct JacoQueryArgs {
   int nenv, nframes;
   JacoQueryFrame fr[JQ_MAXFRAMES];   // by value: no device buffer, no upload
 };
+
+// The host half shared by jaco_query (jaco_env.hip) and the emulator's entry: argument checks, then the frame table and its length into
+// the argument block.  Returns an empty string, or what is wrong.
+static inline std::string jaco_query_resolve(const JacoModelDev& m, const JacoQueryFrame* frames, int nframes, JacoQueryArgs* Q) {
+  if (nframes < 0 || nframes > JQ_MAXFRAMES || (nframes > 0 && !frames))
+    return "nframes " + std::to_string(nframes) + " outside [0, " + std::to_string(JQ_MAXFRAMES) + "]";
+  for (int f = 0; f < nframes; f++) {
+    if (frames[f].body < -1 || frames[f].body >= m.nbody)
+      return "frame " + std::to_string(f) + ": body " + std::to_string(frames[f].body) + " outside [-1, " + std::to_string(m.nbody) + ")";
+    Q->fr[f] = frames[f];
+  }
+  Q->nframes = nframes;
+  return std::string();
+}
 
 // The frame table is indexed per lane: read through the kernarg segment pointer (global loads) rather than the by-value parameter,
 // which a dynamic index would copy to scratch.

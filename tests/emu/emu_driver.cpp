@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: runs the unmodified kernel source under the lockstep wavefront emulator.
 // Built by tests/emu/Makefile into every libjaco_emu*.so; used by CPU-side (-m "not gpu") kernel checks: ctrl-level steps (with the
-// contact record of jaco_set_contact_record), env-level calls, robot-configuration queries (jaco_query) and the host build of the env
-// snapshots (jaco_save_envs / jaco_load_envs).
+// contact record of jaco_set_contact_record), env-level calls, robot-configuration queries (jaco_query), inverse kinematics (jaco_ik) and the
+// host build of the env snapshots (jaco_save_envs / jaco_load_envs).  The argument checks and the reset of one env are the library's own
+// host halves (query.h, ik.h, physics_kernel.h, env_logic.h, model_blob.cpp), called here as jaco_env.hip calls them.
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -12,11 +13,9 @@
 #include "../../mujoco_jaco_amd/csrc/model_blob.h"
 #include "../../mujoco_jaco_amd/csrc/physics_kernel.h"
 #include "../../mujoco_jaco_amd/csrc/snapshot.h"
+#include "../../mujoco_jaco_amd/csrc/abi_agreement.h"
 
 void emu_run_wave(int block, std::function<void()> body);
-
-static_assert(sizeof(JacoContact) == sizeof(JacoContactRec), "JacoContact (include/jaco_env.h) and JacoContactRec (physics_kernel.h) disagree");
-static_assert(JSNAP_FLAG_BAD == JACO_FLAG_BAD_SNAPSHOT, "flag bit of snapshot.h and the public header must agree");
 
 extern "C" int emu_dbg_size() { return JDBG_SIZE; }
 extern "C" int emu_lds_bytes() { return (int)sizeof(JacoLDS<JacoLight>); }
@@ -29,14 +28,18 @@ extern "C" int emu_task_floats() { return JTASK_N; }
 extern "C" int emu_cache_floats() { return JCACHE_N; }
 extern "C" int emu_task_nact(int task_id) { return jaco_task_nact(task_id); }   // width of the task's action row (jaco_dims)
 
+// the message of the last refusal (JACO_EINVAL from an argument check, -1 from the model loader): the text jaco_last_error gives
+static std::string g_error;
+extern "C" const char* emu_last_error() { return g_error.c_str(); }
+static int refuse(const char* who, const std::string& why) { g_error = std::string(who) + ": " + why; return JACO_EINVAL; }
+
 // the model of the last call: every entry loads its blob into it (the loader starts from a zeroed model and a fresh hull table)
 static JacoModelDev g_model;
-static std::vector<float> g_hull;
+static std::vector<float> g_hull, g_qpos0;
 static int g_mpr_output = -1;   // -1: the model loader's default
 extern "C" void emu_set_mpr_output(int v) { g_mpr_output = v; }
 static int load_model(const void* blob, long blob_size) {
-  std::string err;
-  if (jaco_model_from_blob(blob, (size_t)blob_size, &g_model, &g_hull, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return -1; }
+  if (jaco_model_from_blob(blob, (size_t)blob_size, &g_model, &g_hull, &g_error, &g_qpos0)) return -1;
   if (g_mpr_output >= 0) g_model.mpr_output = g_mpr_output;
   return 0;
 }
@@ -111,21 +114,24 @@ static int emu_launch(JacoStepArgs A, int* heavy_envs) {
 }
 // env-level call (mode: JacoMode): JM_STEP = step (nsub = frame_skip), JM_FORWARD = forward only (nsub = 1), JM_HOLD / JM_PREREACH = resets
 static int g_auto_reset = 0;
-static std::vector<float> g_qpos0;
-extern "C" void emu_set_auto_reset(int on, const float* qpos0, int nq) { g_auto_reset = on; g_qpos0.assign(qpos0, qpos0 + nq); }
+extern "C" void emu_set_auto_reset(int on) { g_auto_reset = on; }
 static std::vector<float> g_goal_buf;   // kwarg init_buffer (jaco_set_init_buffer of the library)
 static int g_goal_n = 0, g_goal_stride = 0;
 extern "C" void emu_set_init_buffer(const float* rows, int nrows, int stride) {
   g_goal_buf.assign(rows, rows + (rows ? (size_t)nrows * stride : 0)); g_goal_n = rows ? nrows : 0; g_goal_stride = rows ? stride : 0;
 }
-// what jaco_reset_kernel does for one env (jaco_env.hip): sim.reset() + the draws; the forward pass is a JM_FORWARD emu_env_call
-extern "C" void emu_reset_env(int task_id, unsigned long long seed, int env, int nq, int nv, const float* qpos0, const float* base, float* qpos, float* qvel,
-                              float* qacc_ws, float* task, float* marker, const float* marker_rest) {
-  for (int k = 0; k < nq; k++) qpos[(size_t)env * nq + k] = qpos0[k];
-  for (int k = 0; k < nv; k++) { qvel[(size_t)env * nv + k] = 0.f; qacc_ws[(size_t)env * nv + k] = 0.f; }
-  for (int k = 0; k < 24; k++) marker[(size_t)env * 24 + k] = marker_rest[k];
-  reset_draws(task_id, seed, (unsigned)env, nq >= 23, base, qpos + (size_t)env * nq, task + (size_t)env * JTASK_N,
-              GoalBuffer{g_goal_buf.empty() ? nullptr : g_goal_buf.data(), g_goal_n, g_goal_stride});
+// what jaco_reset does for one env: the argument block jaco_reset fills from the handle, filled from the loaded model, and the routine
+// jaco_reset_kernel calls (the state here has no low halves); the forward pass is a JM_FORWARD emu_env_call
+extern "C" int emu_reset_env(const void* blob, long blob_size, int task_id, unsigned long long seed, int env, float* qpos, float* qvel, float* qacc_ws,
+                             float* task, float* marker) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoResetArgs R{};
+  R.qpos0 = g_qpos0.data(); R.qpos = qpos; R.qvel = qvel; R.qacc_ws = qacc_ws; R.task = task; R.marker = marker; R.marker_rest = &g_model.marker_rest[0][0];
+  R.nq = g_model.nq; R.nv = g_model.nv; R.task_id = task_id; R.has_free = g_model.nq >= 23; R.seed = seed;
+  for (int k = 0; k < 3; k++) R.base[k] = g_model.base_pos[k];
+  R.goals = GoalBuffer{g_goal_buf.empty() ? nullptr : g_goal_buf.data(), g_goal_n, g_goal_stride};
+  jaco_reset_env(R, env);
+  return 0;
 }
 extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode, int frame_skip, int task_id, int nact, unsigned long long seed,
                             float* qpos, float* qvel, float* qacc_ws, float* sensordata, unsigned* flags, int* stats, float* task, float* cache,
@@ -135,9 +141,15 @@ extern "C" int emu_env_call(const void* blob, long blob_size, int nenv, int mode
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = qvel; A.sensordata = sensordata;
   A.flags = flags; A.stats = stats; A.nenv = nenv; A.nsub = mode == JM_FORWARD ? 1 : frame_skip; A.env_mode = mode; A.task_id = task_id; A.nact = nact;
   A.seed = seed; A.task = task; A.cache = cache; A.action = action; A.noise = noise; A.obs = obs; A.reward = reward; A.done = done; A.marker = marker; A.dbg_env = -1;
-  A.auto_reset = g_auto_reset && mode == JM_STEP && jaco_task_auto_resets(task_id); A.qpos0 = g_qpos0.empty() ? nullptr : g_qpos0.data();
+  A.auto_reset = g_auto_reset && mode == JM_STEP && jaco_task_auto_resets(task_id); A.qpos0 = g_qpos0.data();
   A.goal_buf = g_goal_buf.empty() ? nullptr : g_goal_buf.data(); A.goal_n = g_goal_n; A.goal_stride = g_goal_stride;
   return emu_launch(A, heavy_envs);
+}
+// the reset pose the loader reads from the blob (what jaco_create uploads): nq floats; returns nq
+extern "C" int emu_qpos0(const void* blob, long blob_size, float* out) {
+  if (load_model(blob, blob_size)) return -1;
+  std::copy(g_qpos0.begin(), g_qpos0.end(), out);
+  return (int)g_qpos0.size();
 }
 // rest pose of the two task-layer markers (what jaco_reset_state writes): 24 floats
 extern "C" int emu_marker_rest(const void* blob, long blob_size, float* out) {
@@ -151,7 +163,7 @@ extern "C" int emu_marker_rest(const void* blob, long blob_size, float* out) {
 extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int nsub, int disable_contact, float* qpos, float* qvel, float* qacc_ws,
                                 const float* ctrl, float* sensordata, unsigned* flags, int* stats, JacoContact* rec, int* ncon, int cap,
                                 float* dbg, int dbg_env, int* heavy_envs) {
-  if (rec && (!ncon || cap < 1 || cap > JACO_CONTACT_MAX_CAPACITY)) return JACO_EINVAL;
+  if (const char* why = rec ? jaco_contact_record_check(rec, ncon, cap) : nullptr) return refuse("jaco_set_contact_record", why);
   if (load_model(blob, blob_size)) return -1;
   JacoStepArgs A{};
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = ctrl; A.sensordata = sensordata;
@@ -160,20 +172,34 @@ extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int 
   return emu_launch(A, heavy_envs);
 }
 
-// the host half of jaco_query (argument checks, frame table by value) and the grid of the kernel: one wavefront per env
+// the host half of jaco_query (jaco_query_resolve of query.h: argument checks, frame table by value) and the grid of the kernel: one wavefront per env
 extern "C" int emu_query(const void* blob, long blob_size, int nenv, const float* qpos, const float* qvel, const JacoFrame* frames, int nframes,
                          float* xpos, float* xmat, float* jac, float* qM, float* qfrc_bias) {
   if (load_model(blob, blob_size)) return -1;
-  if (nframes < 0 || nframes > JACO_QUERY_MAX_FRAMES) return JACO_EINVAL;
   JacoQueryArgs Q{};
-  for (int f = 0; f < nframes; f++) {
-    if (frames[f].body < -1 || frames[f].body >= g_model.nbody) return JACO_EINVAL;
-    memcpy(&Q.fr[f], &frames[f], sizeof(JacoFrame));
-  }
+  const std::string why = jaco_query_resolve(g_model, reinterpret_cast<const JacoQueryFrame*>(frames), nframes, &Q);
+  if (!why.empty()) return refuse("jaco_query", why);
   Q.model = &g_model; Q.qpos = qpos; Q.qvel = qvel; Q.xpos = xpos; Q.xmat = xmat; Q.jac = jac; Q.qM = qM; Q.bias = qfrc_bias;
-  Q.nenv = nenv; Q.nframes = nframes;
+  Q.nenv = nenv;
   emu_grid = nenv;   // (the kernel reads only blockIdx; the grid jaco_query launches)
   for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_query_kernel(Q); });
+  return 0;
+}
+
+// the host half of jaco_ik (argument checks, active dof set: jaco_ik_resolve of ik.h) and the grid of jaco_ik_kernel, one wavefront per env
+extern "C" int emu_ik(const void* blob, long blob_size, int nenv, const JacoFrame* frame, const JacoIkOptions* opt, const float* qpos_seed,
+                      const float* target_pos, const float* target_quat, float* qpos_out, float* resid, int* status) {
+  if (load_model(blob, blob_size)) return -1;
+  if (!frame || !qpos_seed || !target_pos || !qpos_out) return refuse("jaco_ik", "the frame, the target positions and the output qpos are required");
+  const JacoIkOptions defaults = JACO_IK_DEFAULTS;
+  JacoIkArgs Q{};
+  memcpy(&Q.fr, frame, sizeof(JacoFrame));
+  memcpy(&Q.opt, opt ? opt : &defaults, sizeof(JacoIkOptions));
+  if (const char* why = jaco_ik_resolve(g_model, Q.fr, Q.opt, &Q.active)) return refuse("jaco_ik", why);
+  Q.model = &g_model; Q.qpos = qpos_seed; Q.target_pos = target_pos; Q.target_quat = target_quat;
+  Q.qpos_out = qpos_out; Q.resid = resid; Q.status = status; Q.nenv = nenv;
+  emu_grid = nenv;
+  for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_ik_kernel(Q); });
   return 0;
 }
 

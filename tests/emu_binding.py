@@ -4,7 +4,8 @@ Runs the *unmodified* HIP kernel source (mujoco_jaco_amd/csrc/physics_kernel.h) 
 against a lockstep 64-lane wavefront emulator, so kernel logic can be checked against the oracle
 without a GPU.  Not a product path: the product library refuses to run without a HIP device.
 One library per layout / build option holds every entry: ctrl-level steps (with the contact record),
-env-level calls and robot-configuration queries (tests/query_binding.py), and one set of option switches.
+env-level calls, robot-configuration queries (tests/query_binding.py) and inverse kinematics (tests/ik_binding.py), and one set of
+option switches.  A refused call raises ValueError with the text the library would leave in jaco_last_error.
 """
 import ctypes
 import sys
@@ -41,8 +42,11 @@ def lib(layout=""):
                                    fp, fp, fp, fp, up, ip, fp, fp, fp, fp, fp, fp, ctypes.POINTER(ctypes.c_ubyte), fp, ip]
         L.emu_query.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, fp, fp, ctypes.c_void_p, ctypes.c_int, fp, fp, fp, fp, fp]
         L.emu_marker_rest.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]
-        L.emu_set_auto_reset.argtypes = [ctypes.c_int, fp, ctypes.c_int]
-        L.emu_reset_env.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp]
+        L.emu_ik.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, fp, fp, fp, fp, fp, ip]
+        L.emu_last_error.restype = ctypes.c_char_p
+        L.emu_qpos0.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]
+        L.emu_set_auto_reset.argtypes = [ctypes.c_int]
+        L.emu_reset_env.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, fp, fp, fp, fp, fp]
         L.emu_set_init_buffer.argtypes = [fp, ctypes.c_int, ctypes.c_int]
         for switch in ("obs_mode", "hints", "sep_cache", "mpr_pairs", "pair_list", "handdown", "mpr_output", "tier_return"):
             getattr(L, "emu_set_" + switch).argtypes = [ctypes.c_int]
@@ -51,6 +55,12 @@ def lib(layout=""):
         L.emu_task_nact.argtypes = [ctypes.c_int]
         _libs[layout] = L
     return _libs[layout]
+
+
+def check(L, rc, entry):
+    """A refused call (argument check or model loader) raises ValueError with the driver's message."""
+    if rc != 0:
+        raise ValueError("%s returned %d: %s" % (entry, rc, L.emu_last_error().decode()))
 
 
 class EmuEnv:
@@ -98,7 +108,7 @@ class EmuEnv:
                                      ctypes.c_void_p(rec.ctypes.data) if rec is not None else None,
                                      ncon.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if ncon is not None else None, cap,
                                      fp(self.dbg) if dbg_env >= 0 else None, dbg_env, ctypes.byref(hv))
-        assert rc == 0, rc
+        check(self.L, rc, "emu_physics_step")
         self.heavy_envs = hv.value
 
 
@@ -150,8 +160,7 @@ class EmuJacoEnv(EmuEnv):
 
     def set_auto_reset(self, on):
         """option "auto_reset": a finished env is reset (draws + sim.forward() + first observation) by the wave that finished it."""
-        q0 = np.ascontiguousarray(self.M["qpos0"], np.float32)
-        self.L.emu_set_auto_reset(int(on), q0.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), self.nq)
+        self.L.emu_set_auto_reset(int(on))
 
     def set_init_buffer(self, rows):
         """kwarg init_buffer (jaco_set_init_buffer of the library): recorded rows every reset draws its reaching goal from; None = sampled goals."""
@@ -165,12 +174,8 @@ class EmuJacoEnv(EmuEnv):
         """jaco_reset(mask = {env}): the reset kernel's work for one env, then the forward pass + observation (JM_FORWARD; here for all envs,
         which is harmless for the others: a forward pass does not change state)."""
         fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        q0 = np.ascontiguousarray(self.M["qpos0"], np.float32)
-        base = np.ascontiguousarray(self.M["f_pos"].reshape(-1, 3)[0], np.float32)
-        rest = np.zeros(24, np.float32)
-        assert self.L.emu_marker_rest(self.blob, len(self.blob), fp(rest)) == 0
-        self.L.emu_reset_env(self.task_id, self.seed, env, self.nq, self.nv, fp(q0), fp(base), fp(self.qpos), fp(self.qvel), fp(self.qacc_ws), fp(self.task),
-                             fp(self.marker), fp(rest))
+        check(self.L, self.L.emu_reset_env(self.blob, len(self.blob), self.task_id, self.seed, env, fp(self.qpos), fp(self.qvel), fp(self.qacc_ws),
+                                           fp(self.task), fp(self.marker)), "emu_reset_env")
 
     def forward(self, noise=None):
         self._call(JM_FORWARD, None, None if noise is None else np.ascontiguousarray(noise, np.float32))

@@ -1,5 +1,5 @@
 """The inverse-kinematics kernel (mujoco_jaco_amd/csrc/ik.h) under the wavefront emulator (emu_ik of
-tests/emu_ik/libjaco_emu_ik{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 numpy restatement of the algorithm on modelc.kin.fk / jac_point, the fp64 oracle's forward kinematics as the judge of a
 returned configuration, the target sets of the tests, and a stand-in for BatchedMujoco's query + ik surface backed by the emulator (CPU
@@ -7,31 +7,17 @@ tests of robot_config.BatchedMujocoConfig.ik).
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import emu_binding
 import query_binding as qb
-from emu_binding import ASSETS, ROOT
+from emu_binding import ASSETS
 from mujoco_jaco_amd import _lib as product_lib
 from mujoco_jaco_amd.modelc import blob as blobmod
 from mujoco_jaco_amd.modelc import kin, rot
 
-EMU_IK_DIR = os.path.join(ROOT, "tests", "emu_ik")
-_libs = {}
 DEFAULTS = dict(product_lib.JacoIkOptions.DEFAULTS)
-
-
-def lib(layout=""):
-    if layout not in _libs:
-        name = "libjaco_emu_ik%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_IK_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_IK_DIR, name))
-        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
-        L.emu_ik.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, fp, fp, fp, fp, fp, ip]
-        L.emu_ik_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def load_model(model):
@@ -48,7 +34,7 @@ def ik(model, frame, qpos, target_pos, target_quat=None, resid=True, status=True
     [B, nq], targets [B, 3] / [B, 4] (None: NULL).  defaults=True hands a NULL options pointer.  Raises ValueError with the library's
     message when the call is refused."""
     blob = qb.blob_of(model)
-    L = lib(product_lib.variant_for(blob))
+    L = emu_binding.lib(product_lib.variant_for(blob))
     qpos = np.ascontiguousarray(qpos, np.float32)
     B = qpos.shape[0]
     fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -61,8 +47,7 @@ def ik(model, frame, qpos, target_pos, target_quat=None, resid=True, status=True
     rc = L.emu_ik(blob, len(blob), B, ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p) if frame is not None else None,
                   None if defaults else ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), fp(qpos), fp(tp), fp(tq), fp(out), fp(res),
                   None if st is None else st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
-    if rc != 0:
-        raise ValueError("emu_ik returned %d: %s" % (rc, L.emu_ik_last_error().decode()))
+    emu_binding.check(L, rc, "emu_ik")
     r = {"qpos": out}
     if res is not None:
         r["resid"] = res

@@ -20,7 +20,8 @@ def blob_of(model):
 
 
 def query(model, qpos, qvel, frames, want=OUTS):
-    """Emulated jaco_query: {output: array} at the fp32 states qpos [B, nq] / qvel [B, nv] for a list of _lib.JacoFrame."""
+    """Emulated jaco_query: {output: array} at the fp32 states qpos [B, nq] / qvel [B, nv] for a list of _lib.JacoFrame.  Raises ValueError
+    with the library's message when the call is refused."""
     from mujoco_jaco_amd import _lib as product_lib
     blob = blob_of(model)
     L = emu_binding.lib(product_lib.variant_for(blob))
@@ -33,8 +34,7 @@ def query(model, qpos, qvel, frames, want=OUTS):
     arr = (product_lib.JacoFrame * max(nf, 1))(*frames)
     rc = L.emu_query(blob, len(blob), B, fp(qpos), fp(qvel), ctypes.cast(arr, ctypes.c_void_p), nf,
                      *[fp(res[k]) if k in res else None for k in OUTS])
-    if rc != 0:
-        raise ValueError("emu_query returned %d" % rc)
+    emu_binding.check(L, rc, "emu_query")
     return res
 
 
