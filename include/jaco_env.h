@@ -254,6 +254,41 @@ typedef struct JacoIkOptions {
 int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt_host, const float* qpos_seed_dev,
             const float* target_pos_dev, const float* target_quat_dev, float* qpos_out_dev, float* resid_dev, int32_t* status_dev, void* stream);
 
+/* ---- operational-space controller: which torques drive this frame towards this pose?  abr_control's OSC(robot_config, kp, ko, kv,
+ * vmax).generate() (env_mujoco_util.py:59-63, 85-90) for up to JACO_OSC_MAX_FRAMES frames per env, all of it in one kernel launch
+ * (mujoco_jaco_amd/csrc/osc.h).  For each env and each frame f, with the values of a sim.forward() on the given state -- fresh, not one
+ * substep stale as the reference's controller reads them; a caller who wants that lag computes from the previous state:
+ *   p, R = the frame's point and orientation, composed as jaco_query composes them;  J = the 6 x n Jacobian at p on the frame's active
+ *   dofs;  M = the n x n submatrix of qM on those dofs (the reference's M[arm, arm]; not a Schur complement);  bias = qfrc_bias there;
+ *   Mx = (J M^-1 J^T)^-1 when |det| >= 1e-3, else the pseudo-inverse that drops singular values < 0.005;
+ *   u_task = [p - p*; -vec(q* conj(q_R)) sign(w)], its two halves scaled down to the norms vmax_xyz / kp * kv and vmax_abg / ko * kv
+ *   when they exceed them, then multiplied by kp and ko;      u = -kv M dq - J^T Mx u_task + bias.
+ * Active dofs of a frame: the hinge dofs on the chain of the frame's body, intersected with dof_mask (bit d = dof d) when that is
+ * non-zero; 1 <= n <= 6.  With n < 6 the 6 x 6 rule is applied to the rank-deficient matrix as it stands (M padded with identity, J with
+ * zero columns): its determinant is 0, the pseudo-inverse branch runs and the status is 1.
+ * Inputs (device): qpos_dev [num_envs][nq] / qvel_dev [num_envs][nv] (NULL = the handle's current state, the fp32 words jaco_get_state
+ * returns); target_pos_dev [num_envs][nframes][3]; target_quat_dev [num_envs][nframes][4] (unit quaternions, w first; normalised again
+ * in the kernel); ctrl_in_dev [num_envs][nu] (NULL = zeros).  Outputs (device): ctrl_out_dev [num_envs][nu] = the ctrl_in row with u_d
+ * written at the motor actuator of every active dof d and every other word copied bit for bit (gripper commands, the other arm); it may
+ * be ctrl_in_dev itself.  No clamping here: the step's actuator stage applies ctrlrange / forcerange.  status_dev [num_envs][nframes]
+ * int32 (or NULL): 1 = the pseudo-inverse branch ran.  opt_host NULL = JACO_OSC_DEFAULTS (the reference's gains).
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch, no allocation, no synchronisation, no host copy (frames
+ * and options travel in the kernel arguments).
+ * JACO_EINVAL for nframes outside [1, JACO_OSC_MAX_FRAMES], a frame body outside [0, fused bodies), an empty active set or one larger
+ * than 6, active sets of two frames that overlap, an active dof without a motor actuator, a non-positive gain or vmax, NULL targets and
+ * a NULL ctrl_out.  Position-only control (abr_control's ctrlr_dof) is not offered. */
+#define JACO_OSC_MAX_FRAMES 2
+typedef struct JacoOscOptions {
+  float kp, ko, kv;            /* 50, 180, 20 */
+  float vmax_xyz, vmax_abg;    /* 0.4 m/s, 1.0472 rad/s */
+  int32_t reserved;
+  uint64_t dof_mask;           /* 0 = every hinge dof on the frame's chain */
+} JacoOscOptions;
+#define JACO_OSC_DEFAULTS {50.f, 180.f, 20.f, 0.4f, 1.0472f, 0, 0}
+int jaco_osc(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const float* qpos_dev,
+             const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev, const float* ctrl_in_dev, float* ctrl_out_dev,
+             int32_t* status_dev, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

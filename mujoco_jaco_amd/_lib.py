@@ -39,6 +39,22 @@ class JacoIkOptions(ctypes.Structure):
         super().__init__(**{**self.DEFAULTS, **options})
 
 
+JACO_OSC_MAX_FRAMES = 2
+
+
+class JacoOscOptions(ctypes.Structure):
+    """JacoOscOptions of include/jaco_env.h; a fresh instance holds the API defaults (JACO_OSC_DEFAULTS: the reference's gains)."""
+    _fields_ = [("kp", ctypes.c_float), ("ko", ctypes.c_float), ("kv", ctypes.c_float), ("vmax_xyz", ctypes.c_float), ("vmax_abg", ctypes.c_float),
+                ("reserved", ctypes.c_int32), ("dof_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(kp=50.0, ko=180.0, kv=20.0, vmax_xyz=0.4, vmax_abg=1.0472, dof_mask=0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown OSC option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
 class JacoContact(ctypes.Structure):
     """JacoContact of include/jaco_env.h: one record of the contact record (jaco_set_contact_record), 96 bytes."""
     _fields_ = [("dist", ctypes.c_float), ("pos", ctypes.c_float * 3), ("frame", ctypes.c_float * 9), ("force", ctypes.c_float * 6),
@@ -103,6 +119,7 @@ SYMBOLS = {
     "jaco_stage_profile": (_ci, [_vp, ctypes.POINTER(ctypes.c_uint64), _ci]),
     "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "jaco_ik": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_osc": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h and ik.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h and osc.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -21,3 +21,8 @@ static_assert(sizeof(JacoIkOptions) == sizeof(JacoIkOpts) && offsetof(JacoIkOpti
                   offsetof(JacoIkOptions, max_step) == offsetof(JacoIkOpts, max_step) && offsetof(JacoIkOptions, max_iters) == offsetof(JacoIkOpts, max_iters) &&
                   offsetof(JacoIkOptions, dof_mask) == offsetof(JacoIkOpts, dof_mask) && JACO_IK_MAX_ITERS == JIK_MAX_ITERS,
               "JacoIkOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoOscOptions) == sizeof(JacoOscOpts) && offsetof(JacoOscOptions, kp) == offsetof(JacoOscOpts, kp) &&
+                  offsetof(JacoOscOptions, ko) == offsetof(JacoOscOpts, ko) && offsetof(JacoOscOptions, kv) == offsetof(JacoOscOpts, kv) &&
+                  offsetof(JacoOscOptions, vmax_xyz) == offsetof(JacoOscOpts, vmax_xyz) && offsetof(JacoOscOptions, vmax_abg) == offsetof(JacoOscOpts, vmax_abg) &&
+                  offsetof(JacoOscOptions, dof_mask) == offsetof(JacoOscOpts, dof_mask) && JACO_OSC_MAX_FRAMES == JOSC_MAXFRAMES,
+              "JacoOscOptions of the public header and the kernel's option record must agree");

@@ -974,3 +974,26 @@ extern "C" int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkO
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- operational-space controller (osc.h): one wavefront per env, nothing of the handle written -----------------------------------
+extern "C" int jaco_osc(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const float* qpos_dev,
+                        const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev, const float* ctrl_in_dev, float* ctrl_out_dev,
+                        int32_t* status_dev, void* stream) {
+  if (!h) return JACO_EINVAL;
+  const JacoOscOptions defaults = JACO_OSC_DEFAULTS;
+  JacoOscOpts opt;
+  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoOscOptions));
+  JacoOscArgs Q{};
+  Q.target_pos = target_pos_dev; Q.target_quat = target_quat_dev; Q.ctrl_in = ctrl_in_dev; Q.ctrl_out = ctrl_out_dev; Q.status = status_dev;
+  const std::string why = jaco_osc_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, opt, &Q);
+  if (!why.empty()) { h->err = "jaco_osc: " + why; return JACO_EINVAL; }
+  ENTER(h);
+  Q.model = h->model_dev;
+  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
+  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
+  Q.nenv = h->num_envs;
+  jaco_launch_osc((unsigned)h->num_envs, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

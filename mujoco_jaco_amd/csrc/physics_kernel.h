@@ -2816,3 +2816,5 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #include "query.h"
 // the inverse-kinematics kernel (jaco_ik): translation unit 10
 #include "ik.h"
+// the operational-space controller kernel (jaco_osc): translation unit 11
+#include "osc.h"

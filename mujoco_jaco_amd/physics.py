@@ -215,6 +215,29 @@ class BatchedMujoco:
                                  ctypes.c_void_p(resid.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream()))
         return {"qpos": out, "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
 
+    # ---- operational-space controller (jaco_osc: abr_control's OSC.generate per env and frame, one launch)
+    def osc(self, frames, target_pos, target_quat, qpos=None, qvel=None, ctrl=None, **options):
+        """The torques that drive `frames` (one or two _lib.JacoFrame; FrameTable.jaco_frame(name, point=...): `point` is the controlled
+        point) towards target_pos [B, nf, 3] / target_quat [B, nf, 4] (unit quaternions, w first), from the values of a forward pass on
+        qpos [B, nq] / qvel [B, nv] (default: the current state).  ctrl [B, nu]: the row the torques are written into (default zeros);
+        only the motor actuators of the frames' active dofs change.  options: kp, ko, kv, vmax_xyz, vmax_abg, dof_mask
+        (include/jaco_env.h).  One launch on the current stream, no synchronisation; {"ctrl": [B, nu], "singular": [B, nf] bool, True
+        where the pseudo-inverse branch ran}.  The sim's state is not touched: apply the result with send_forces."""
+        if isinstance(frames, _lib.JacoFrame):
+            frames = [frames]
+        nf, B, dev = len(frames), self.num_envs, self.device
+        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
+        tp, tq = prep(target_pos, 3 * nf), prep(target_quat, 4 * nf)
+        q, v, cin = prep(qpos, self.nq), prep(qvel, self.nv), prep(ctrl, self.nu)
+        out = torch.empty(B, self.nu, device=dev)
+        status = torch.empty(B, max(nf, 1), dtype=torch.int32, device=dev)
+        opt = _lib.JacoOscOptions(**options)
+        arr = (_lib.JacoFrame * max(nf, 1))(*frames)
+        self._chk(self.L.jaco_osc(self.h, ctypes.cast(arr, ctypes.c_void_p), nf, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
+                                  self._dev(q, self.nq), self._dev(v, self.nv), self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(cin, self.nu),
+                                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream()))
+        return {"ctrl": out, "singular": status != 0}
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

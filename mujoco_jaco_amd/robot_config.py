@@ -238,6 +238,10 @@ class BatchedMujocoConfig:
         r = self.sim.ik(frame, pos, quat, seed, **options)
         return r["qpos"][:, self.arm_qadr], r["converged"]
 
+    def osc(self, names=None, **gains):
+        """BatchedOSC over this sim: abr_control's OSC(robot_config, kp, ko, kv, vmax); names default to this config's end effector."""
+        return BatchedOSC(self, names=(self.ee,) if names is None else names, **gains)
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
@@ -248,3 +252,58 @@ class BatchedMujocoConfig:
         import torch
         x = torch.as_tensor(x, dtype=p.dtype, device=p.device).reshape(3)
         return p + (r["xmat"][:, i].reshape(-1, 3, 3) @ x)
+
+
+def quat_from_euler_rxyz(e):
+    """[..., 3] 'rxyz' Euler angles -> [..., 4] unit quaternions, w first (transformations.quaternion_from_euler(a, b, c, 'rxyz'):
+    qx(a) qy(b) qz(c)), in torch on the tensor's device."""
+    import torch
+    h = 0.5 * e
+    ca, cb, cc = torch.cos(h[..., 0]), torch.cos(h[..., 1]), torch.cos(h[..., 2])
+    sa, sb, sc = torch.sin(h[..., 0]), torch.sin(h[..., 1]), torch.sin(h[..., 2])
+    w1, x1, y1, z1 = ca * cb, sa * cb, ca * sb, sa * sb
+    q = torch.stack([w1 * cc - z1 * sc, x1 * cc + y1 * sc, y1 * cc - x1 * sc, w1 * sc + z1 * cc], -1)
+    return q / q.norm(dim=-1, keepdim=True)
+
+
+class BatchedOSC:
+    """abr_control's OSC(robot_config, kp, ko, kv, vmax) (env_mujoco_util.py:59-63) over a BatchedMujocoConfig: .generate() returns the
+    ctrl rows of every env from ONE jaco_osc launch.  names: one or two MJCF bodies whose origins and orientations are controlled
+    (("EE",); ("EE_1", "EE_2") on the two-arm model: both arms in one launch); each drives the hinge joints on its own chain.  The
+    quantities are those of a forward pass on the state the call is given (fresh; the reference's are one substep stale)."""
+
+    def __init__(self, robot_config, names=("EE",), kp=50.0, ko=180.0, kv=20.0, vmax=(0.4, 1.0472)):
+        self.robot_config, self.sim = robot_config, robot_config.sim
+        self.names = (names,) if isinstance(names, str) else tuple(names)
+        if not 1 <= len(self.names) <= _lib.JACO_OSC_MAX_FRAMES:
+            raise ValueError("BatchedOSC controls 1 to %d frames, not %d" % (_lib.JACO_OSC_MAX_FRAMES, len(self.names)))
+        self.frames = [robot_config.table.jaco_frame(n, point=np.zeros(3)) for n in self.names]
+        self.chains = [robot_config.table.chain(n) for n in self.names]   # (qpos addresses, dof addresses) per name
+        self.options = dict(kp=float(kp), ko=float(ko), kv=float(kv), vmax_xyz=float(vmax[0]), vmax_abg=float(vmax[1]))
+
+    def _state(self, q, dq):
+        """Full qpos / qvel rows with the controlled chains' q / dq ([B, sum of chain lengths]) spliced into the current state."""
+        if q is None and dq is None:
+            return None, None
+        import torch
+        qpos, qvel, _ = self.sim.get_state()
+        qadr = [a for c in self.chains for a in c[0]]
+        dadr = [d for c in self.chains for d in c[1]]
+        if q is not None:
+            qpos[:, qadr] = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], len(qadr))
+        if dq is not None:
+            qvel[:, dadr] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], len(dadr))
+        return qpos.contiguous(), qvel.contiguous()
+
+    def generate_pose(self, pos, quat, q=None, dq=None, ctrl=None):
+        """ctrl [B, nu] for target positions pos [B, 3] (or [B, n_names, 3]) and unit quaternions quat [B, 4] ([B, n_names, 4]), w first.
+        q / dq: joint angles / velocities of the controlled chains (default: the sim's state); ctrl: the row to write into (default
+        zeros) -- every word but the controlled motors' is kept."""
+        qpos, qvel = self._state(q, dq)
+        return self.sim.osc(self.frames, pos, quat, qpos, qvel, ctrl, **self.options)["ctrl"]
+
+    def generate(self, target, q=None, dq=None, ctrl=None):
+        """abr_control's generate(q, dq, target): target [B, 6] (or [B, n_names, 6]) = position + 'rxyz' Euler angles."""
+        import torch
+        t = torch.as_tensor(target, dtype=torch.float32, device=self.sim.device).reshape(self.sim.num_envs, len(self.names), 6)
+        return self.generate_pose(t[..., :3], quat_from_euler_rxyz(t[..., 3:]), q, dq, ctrl)
