@@ -276,7 +276,7 @@ int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt
  * and options travel in the kernel arguments).
  * JACO_EINVAL for nframes outside [1, JACO_OSC_MAX_FRAMES], a frame body outside [0, fused bodies), an empty active set or one larger
  * than 6, active sets of two frames that overlap, an active dof without a motor actuator, a non-positive gain or vmax, NULL targets and
- * a NULL ctrl_out.  Position-only control (abr_control's ctrlr_dof) is not offered. */
+ * a NULL ctrl_out.  Task axes (abr_control's ctrlr_dof) and null-space terms: jaco_osc_task below. */
 #define JACO_OSC_MAX_FRAMES 2
 typedef struct JacoOscOptions {
   float kp, ko, kv;            /* 50, 180, 20 */
@@ -288,6 +288,38 @@ typedef struct JacoOscOptions {
 int jaco_osc(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const float* qpos_dev,
              const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev, const float* ctrl_in_dev, float* ctrl_out_dev,
              int32_t* status_dev, void* stream);
+
+/* ---- ... on chosen task axes, with null-space posture terms: abr_control's OSC(..., ctrlr_dof, null_controllers=[Damping, RestingConfig])
+ * .generate(), one kernel launch (mujoco_jaco_amd/csrc/osc_task.h).  Everything is as in jaco_osc -- p, R, J, M, bias, the active dofs,
+ * the inputs, ctrl_out and its aliasing, the normalisation of target_quat, status, "nothing of the handle is written" -- except:
+ *   rows = the task rows that axes[f] selects (bit 0-2: the world x, y, z rows of J; bit 3-5: the three rotational rows; 0 = all six),
+ *   k of them, 1 <= k <= 6;  Js = J[rows] (k x n; abr_control's J[ctrlr_dof]);
+ *   Mx = (Js M^-1 Js^T)^-1 when n >= k and |det| >= 1e-3, else the pseudo-inverse that drops singular values < 0.005 (status 1); with
+ *   n < k the matrix is exactly rank deficient and the pseudo-inverse always runs;
+ *   u_task = [p - p*; -vec(q* conj(q_R)) sign(w)], each half saturated on the norm of its full three components and multiplied by its
+ *   gain exactly as in jaco_osc, and only then reduced to the selected rows (abr_control's order);
+ *   u = -kv M dq - Js^T Mx u_task[rows] + bias;
+ *   u_null = -null_kv M dq                          (Damping; off when null_kv == 0)
+ *          + M (rest_kp e - rest_kv v)              (RestingConfig; on when rest_qpos_dev != NULL), where for every active dof d that
+ *            rest_mask selects (bit d = dof d; 0 = every active dof) e_d = ((rest_d - q_d + pi) mod 2 pi) - pi in [-pi, pi) (floor-style
+ *            modulus) and v_d = dq_d, and e_d = v_d = 0 for the others;
+ *   u += u_null - Js^T Mx (Js (M^-1 u_null))        (the null-space filter (I - Js^T Jbar^T) with Jbar = M^-1 Js^T Mx; the same Mx).
+ * rest_qpos_dev [num_envs][nq] fp32 is read only at the qpos addresses of the selected dofs: a jaco_ik result row can be handed in as it
+ * is.  target_quat_dev may be NULL when no frame selects a rotational row; it is not read then.  task_host NULL = jaco_osc itself (the
+ * call forwards to it; rest_qpos_dev is ignored).  One kernel launch, no allocation, no synchronisation, no host copy.
+ * JACO_EINVAL for everything jaco_osc refuses, and for an axes word with bits above bit 5, a negative or non-finite null_kv, rest_kp or
+ * rest_kv, a rest_mask that leaves no active dof of some frame while rest_qpos_dev is given, and a NULL target_quat_dev with a
+ * rotational row selected. */
+typedef struct JacoOscTask {
+  uint32_t axes[JACO_OSC_MAX_FRAMES]; /* bit r = task row r (x y z, then the three rotational rows); 0 = all six */
+  float null_kv;                      /* >= 0; 0 = no damping term */
+  float rest_kp, rest_kv;             /* >= 0; used when rest_qpos_dev is given */
+  int32_t reserved;
+  uint64_t rest_mask;                 /* dofs held by the resting term; 0 = every active dof */
+} JacoOscTask;
+int jaco_osc_task(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const JacoOscTask* task_host,
+                  const float* qpos_dev, const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev,
+                  const float* rest_qpos_dev, const float* ctrl_in_dev, float* ctrl_out_dev, int32_t* status_dev, void* stream);
 
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the

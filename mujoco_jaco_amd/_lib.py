@@ -4,6 +4,7 @@ There is deliberately no fallback: if the HIP extension has not been built
 (``python -c "import __graft_entry__ as g; g.build()"``) importing this module raises.
 """
 import ctypes
+import numbers
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,6 +54,44 @@ class JacoOscOptions(ctypes.Structure):
         if unknown:
             raise TypeError("unknown OSC option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
         super().__init__(**{**self.DEFAULTS, **options})
+
+
+class JacoOscTask(ctypes.Structure):
+    """JacoOscTask of include/jaco_env.h: the task axes and null-space terms of jaco_osc_task; a fresh instance is plain jaco_osc (all six
+    axes, no null-space term)."""
+    _fields_ = [("axes", ctypes.c_uint32 * JACO_OSC_MAX_FRAMES), ("null_kv", ctypes.c_float), ("rest_kp", ctypes.c_float), ("rest_kv", ctypes.c_float),
+                ("reserved", ctypes.c_int32), ("rest_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(axes=(0,) * JACO_OSC_MAX_FRAMES, null_kv=0.0, rest_kp=0.0, rest_kv=0.0, rest_mask=0)
+
+    def __init__(self, **task):
+        unknown = set(task) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown OSC task field(s) %s: the fields are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        f = {**self.DEFAULTS, **task}
+        f["axes"] = (ctypes.c_uint32 * JACO_OSC_MAX_FRAMES)(*f["axes"])
+        super().__init__(**f)
+
+
+def osc_axes(axes, nframes):
+    """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
+    or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
+    def one(a):
+        if isinstance(a, numbers.Integral):
+            return int(a)
+        a = list(a)
+        if len(a) != 6:
+            raise ValueError("task axes are a 6-bit mask or six booleans, not %d entries" % len(a))
+        mask = sum(1 << r for r, on in enumerate(a) if on)
+        if not mask:
+            raise ValueError("the task axes select no row")
+        return mask
+    if axes is None:
+        return (0,) * JACO_OSC_MAX_FRAMES
+    shared = isinstance(axes, numbers.Integral) or (len(axes) == 6 and not any(hasattr(a, "__len__") for a in axes))
+    if not shared and len(axes) != nframes:
+        raise ValueError("%d task-axis entries for %d frames" % (len(axes), nframes))
+    per = [one(axes)] * nframes if shared else [one(a) for a in axes]
+    return tuple(per[:JACO_OSC_MAX_FRAMES]) + (0,) * (JACO_OSC_MAX_FRAMES - len(per))
 
 
 class JacoContact(ctypes.Structure):
@@ -120,6 +159,7 @@ SYMBOLS = {
     "jaco_query": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "jaco_ik": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_osc": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_osc_task": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

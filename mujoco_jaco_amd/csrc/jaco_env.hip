@@ -997,3 +997,30 @@ extern "C" int jaco_osc(JacoHandle* h, const JacoFrame* frames_host, int nframes
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- ... on task axes, with null-space terms (osc_task.h): task_host NULL is jaco_osc itself -------------------------------------
+extern "C" int jaco_osc_task(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const JacoOscTask* task_host,
+                             const float* qpos_dev, const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev,
+                             const float* rest_qpos_dev, const float* ctrl_in_dev, float* ctrl_out_dev, int32_t* status_dev, void* stream) {
+  if (!task_host) return jaco_osc(h, frames_host, nframes, opt_host, qpos_dev, qvel_dev, target_pos_dev, target_quat_dev, ctrl_in_dev, ctrl_out_dev, status_dev, stream);
+  if (!h) return JACO_EINVAL;
+  const JacoOscOptions defaults = JACO_OSC_DEFAULTS;
+  JacoOscOpts opt;
+  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoOscOptions));
+  JacoOscTaskOpts task;
+  memcpy(&task, task_host, sizeof(JacoOscTask));
+  JacoOscTaskArgs T{};
+  T.o.target_pos = target_pos_dev; T.o.target_quat = target_quat_dev; T.o.ctrl_in = ctrl_in_dev; T.o.ctrl_out = ctrl_out_dev; T.o.status = status_dev;
+  T.rest_qpos = rest_qpos_dev;
+  const std::string why = jaco_osc_task_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, opt, task, &T);
+  if (!why.empty()) { h->err = "jaco_osc_task: " + why; return JACO_EINVAL; }
+  ENTER(h);
+  T.o.model = h->model_dev;
+  T.o.qpos = qpos_dev ? qpos_dev : h->env.qpos;
+  T.o.qvel = qvel_dev ? qvel_dev : h->env.qvel;
+  T.o.nenv = h->num_envs;
+  jaco_launch_osc_task((unsigned)h->num_envs, (hipStream_t)stream, T);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

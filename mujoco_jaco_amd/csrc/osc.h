@@ -245,3 +245,5 @@ void jaco_launch_osc(unsigned grid, hipStream_t st, const JacoOscArgs& Q);
 void jaco_launch_osc(unsigned grid, hipStream_t st, const JacoOscArgs& Q) { hipLaunchKernelGGL(jaco_osc_kernel, dim3(grid), dim3(64), 0, st, Q); }
 #endif
 #endif
+
+#include "osc_task.h"

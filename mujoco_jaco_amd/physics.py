@@ -216,13 +216,19 @@ class BatchedMujoco:
         return {"qpos": out, "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
 
     # ---- operational-space controller (jaco_osc: abr_control's OSC.generate per env and frame, one launch)
-    def osc(self, frames, target_pos, target_quat, qpos=None, qvel=None, ctrl=None, **options):
+    def osc(self, frames, target_pos, target_quat=None, qpos=None, qvel=None, ctrl=None, axes=None, null_kv=0.0, rest_qpos=None, rest_kp=0.0,
+            rest_kv=0.0, rest_mask=0, **options):
         """The torques that drive `frames` (one or two _lib.JacoFrame; FrameTable.jaco_frame(name, point=...): `point` is the controlled
         point) towards target_pos [B, nf, 3] / target_quat [B, nf, 4] (unit quaternions, w first), from the values of a forward pass on
         qpos [B, nq] / qvel [B, nv] (default: the current state).  ctrl [B, nu]: the row the torques are written into (default zeros);
         only the motor actuators of the frames' active dofs change.  options: kp, ko, kv, vmax_xyz, vmax_abg, dof_mask
         (include/jaco_env.h).  One launch on the current stream, no synchronisation; {"ctrl": [B, nu], "singular": [B, nf] bool, True
-        where the pseudo-inverse branch ran}.  The sim's state is not touched: apply the result with send_forces."""
+        where the pseudo-inverse branch ran}.  The sim's state is not touched: apply the result with send_forces.
+        Task axes and null-space terms (jaco_osc_task; with all of them at their defaults the call is jaco_osc): axes = one 6-bit mask
+        (bit 0-2: x, y, z; bit 3-5: the rotational rows) or six booleans, or one of those per frame -- abr_control's ctrlr_dof;
+        target_quat may be None when no rotational row is selected.  null_kv > 0: Damping(null_kv).  rest_qpos [B, nq]:
+        RestingConfig(rest_kp, rest_kv) towards those joint angles on the dofs of rest_mask (bit d = dof d; 0: every active dof), read
+        only at those dofs' qpos addresses.  Both act in the null space of the selected task rows."""
         if isinstance(frames, _lib.JacoFrame):
             frames = [frames]
         nf, B, dev = len(frames), self.num_envs, self.device
@@ -233,9 +239,15 @@ class BatchedMujoco:
         status = torch.empty(B, max(nf, 1), dtype=torch.int32, device=dev)
         opt = _lib.JacoOscOptions(**options)
         arr = (_lib.JacoFrame * max(nf, 1))(*frames)
-        self._chk(self.L.jaco_osc(self.h, ctypes.cast(arr, ctypes.c_void_p), nf, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                                  self._dev(q, self.nq), self._dev(v, self.nv), self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(cin, self.nu),
-                                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream()))
+        head = (self.h, ctypes.cast(arr, ctypes.c_void_p), nf, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p))
+        tail = (self._dev(cin, self.nu), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream())
+        if axes is None and null_kv == 0.0 and rest_qpos is None and rest_kp == 0.0 and rest_kv == 0.0 and rest_mask == 0:
+            self._chk(self.L.jaco_osc(*head, self._dev(q, self.nq), self._dev(v, self.nv), self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), *tail))
+        else:
+            rest = prep(rest_qpos, self.nq)
+            task = _lib.JacoOscTask(axes=_lib.osc_axes(axes, nf), null_kv=null_kv, rest_kp=rest_kp, rest_kv=rest_kv, rest_mask=rest_mask)
+            self._chk(self.L.jaco_osc_task(*head, ctypes.cast(ctypes.pointer(task), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
+                                           self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(rest, self.nq), *tail))
         return {"ctrl": out, "singular": status != 0}
 
     def get_xyz(self, name):

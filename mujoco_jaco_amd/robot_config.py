@@ -266,13 +266,33 @@ def quat_from_euler_rxyz(e):
     return q / q.norm(dim=-1, keepdim=True)
 
 
-class BatchedOSC:
-    """abr_control's OSC(robot_config, kp, ko, kv, vmax) (env_mujoco_util.py:59-63) over a BatchedMujocoConfig: .generate() returns the
-    ctrl rows of every env from ONE jaco_osc launch.  names: one or two MJCF bodies whose origins and orientations are controlled
-    (("EE",); ("EE_1", "EE_2") on the two-arm model: both arms in one launch); each drives the hinge joints on its own chain.  The
-    quantities are those of a forward pass on the state the call is given (fresh; the reference's are one substep stale)."""
+class Damping:
+    """abr_control's null-space controller Damping(robot_config, kv): -kv M dq, filtered into the null space of the task."""
 
-    def __init__(self, robot_config, names=("EE",), kp=50.0, ko=180.0, kv=20.0, vmax=(0.4, 1.0472)):
+    def __init__(self, kv):
+        self.kv = float(kv)
+
+
+class RestingConfig:
+    """abr_control's null-space controller RestingConfig(robot_config, rest_angles, kp, kv): M (kp e - kv dq) on the held joints, e the
+    wrapped difference to their rest angles, filtered into the null space of the task.  rest_angles covers the joints of the controlled
+    chains in order (one entry per joint; with two names either one list per name or both chains one after the other): a list with None
+    for joints that are not held, or a [B, chain length] tensor (every joint held, per env)."""
+
+    def __init__(self, rest_angles, kp, kv):
+        self.rest_angles, self.kp, self.kv = rest_angles, float(kp), float(kv)
+
+
+class BatchedOSC:
+    """abr_control's OSC(robot_config, kp, ko, kv, vmax, ctrlr_dof, null_controllers) (env_mujoco_util.py:59-63) over a
+    BatchedMujocoConfig: .generate() returns the ctrl rows of every env from ONE launch (jaco_osc; jaco_osc_task when task axes or
+    null-space controllers are given).  names: one or two MJCF bodies whose origins and orientations are controlled (("EE",);
+    ("EE_1", "EE_2") on the two-arm model: both arms in one launch); each drives the hinge joints on its own chain.  ctrlr_dof: six
+    booleans (x, y, z, then the three rotational rows), or one such list per name; None: all six.  null_controllers: Damping and / or
+    RestingConfig instances.  The quantities are those of a forward pass on the state the call is given (fresh; the reference's are one
+    substep stale)."""
+
+    def __init__(self, robot_config, names=("EE",), kp=50.0, ko=180.0, kv=20.0, vmax=(0.4, 1.0472), ctrlr_dof=None, null_controllers=()):
         self.robot_config, self.sim = robot_config, robot_config.sim
         self.names = (names,) if isinstance(names, str) else tuple(names)
         if not 1 <= len(self.names) <= _lib.JACO_OSC_MAX_FRAMES:
@@ -280,6 +300,44 @@ class BatchedOSC:
         self.frames = [robot_config.table.jaco_frame(n, point=np.zeros(3)) for n in self.names]
         self.chains = [robot_config.table.chain(n) for n in self.names]   # (qpos addresses, dof addresses) per name
         self.options = dict(kp=float(kp), ko=float(ko), kv=float(kv), vmax_xyz=float(vmax[0]), vmax_abg=float(vmax[1]))
+        self.axes = _lib.osc_axes(ctrlr_dof, len(self.names))[:len(self.names)]
+        self.rotational = any((a or 63) & 56 for a in self.axes)
+        self.task = self._task(ctrlr_dof, list(null_controllers))   # the task keywords of sim.osc; empty: plain jaco_osc
+
+    def _task(self, ctrlr_dof, null_controllers):
+        task = {} if ctrlr_dof is None else dict(axes=list(self.axes))
+        unknown = [c for c in null_controllers if not isinstance(c, (Damping, RestingConfig))]
+        resting = [c for c in null_controllers if isinstance(c, RestingConfig)]
+        if unknown or len(resting) > 1:
+            raise ValueError("null_controllers holds Damping instances and at most one RestingConfig")
+        damping = sum(c.kv for c in null_controllers if isinstance(c, Damping))
+        if damping:
+            task["null_kv"] = damping
+        if resting:
+            import torch
+            qadr = [a for c in self.chains for a in c[0]]
+            dadr = [d for c in self.chains for d in c[1]]
+            ra = resting[0].rest_angles
+            B = self.sim.num_envs
+            rest = torch.zeros(B, self.sim.nq, dtype=torch.float32, device=self.sim.device)
+            if torch.is_tensor(ra):
+                rest[:, qadr] = ra.to(dtype=torch.float32, device=rest.device).reshape(B, len(qadr))
+                held = dadr
+            else:
+                ra = list(ra)
+                if len(ra) == len(self.chains) and all(hasattr(r, "__len__") for r in ra):
+                    ra = [torch.as_tensor(r, dtype=torch.float32).reshape(B, -1).T if torch.is_tensor(r) else r for r in ra]
+                    ra = [x for r in ra for x in r]
+                if len(ra) != len(qadr):
+                    raise ValueError("RestingConfig: %d rest angles for %d controlled joints" % (len(ra), len(qadr)))
+                held = [d for d, r in zip(dadr, ra) if r is not None]
+                for a, r in zip(qadr, ra):
+                    if r is not None:
+                        rest[:, a] = torch.as_tensor(r, dtype=torch.float32, device=rest.device)
+            if not held:
+                raise ValueError("RestingConfig holds no joint")
+            task.update(rest_qpos=rest, rest_kp=resting[0].kp, rest_kv=resting[0].kv, rest_mask=sum(1 << d for d in held))
+        return task
 
     def _state(self, q, dq):
         """Full qpos / qvel rows with the controlled chains' q / dq ([B, sum of chain lengths]) spliced into the current state."""
@@ -295,12 +353,14 @@ class BatchedOSC:
             qvel[:, dadr] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], len(dadr))
         return qpos.contiguous(), qvel.contiguous()
 
-    def generate_pose(self, pos, quat, q=None, dq=None, ctrl=None):
-        """ctrl [B, nu] for target positions pos [B, 3] (or [B, n_names, 3]) and unit quaternions quat [B, 4] ([B, n_names, 4]), w first.
-        q / dq: joint angles / velocities of the controlled chains (default: the sim's state); ctrl: the row to write into (default
-        zeros) -- every word but the controlled motors' is kept."""
+    def generate_pose(self, pos, quat=None, q=None, dq=None, ctrl=None):
+        """ctrl [B, nu] for target positions pos [B, 3] (or [B, n_names, 3]) and unit quaternions quat [B, 4] ([B, n_names, 4]), w first;
+        quat may be left out when ctrlr_dof selects no rotational row.  q / dq: joint angles / velocities of the controlled chains
+        (default: the sim's state); ctrl: the row to write into (default zeros) -- every word but the controlled motors' is kept."""
+        if quat is None and self.rotational:
+            raise ValueError("generate_pose needs target quaternions: ctrlr_dof selects a rotational axis")
         qpos, qvel = self._state(q, dq)
-        return self.sim.osc(self.frames, pos, quat, qpos, qvel, ctrl, **self.options)["ctrl"]
+        return self.sim.osc(self.frames, pos, quat, qpos, qvel, ctrl, **self.task, **self.options)["ctrl"]
 
     def generate(self, target, q=None, dq=None, ctrl=None):
         """abr_control's generate(q, dq, target): target [B, 6] (or [B, n_names, 6]) = position + 'rxyz' Euler angles."""

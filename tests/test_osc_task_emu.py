@@ -1,0 +1,333 @@
+"""CPU tier: the task-axis / null-space controller kernel (mujoco_jaco_amd/csrc/osc_task.h, jaco_osc_task) under the wavefront emulator
+against the fp64 restatement of abr_control's OSC.generate() with ctrlr_dof and null_controllers (tests/osc_task_binding.py generate /
+reference: true k x k matrices on the fp64 oracle's J, qM, qfrc_bias, point and quaternion).  Inputs: those of tests/test_osc_emu.py
+(osc_binding.states("jaco2_curtain_torque", 67), targets6, kernel_targets, frame EE).
+
+Error measure: osc_binding.error, max over the active dofs of |u - u_ref| / (1 + |u_ref|).  Bounds = 3 x the largest value measured on
+the emulator (MEASURE lines of a run with -s):
+  the restatement against osc_binding.reference, all six axes, no null term (fp64 against fp64) ....... 1.4e-14 -> fixed bound 1e-12
+  regular branch, masks 0b000111 / 0b111000 / 0b100111 / 0b011011 (no env in the band, none singular) .. 7.20e-6 -> 2.2e-5
+  pseudo-inverse by count: dof_mask 0b11, position only (n = 2 < k = 3) .............................. 5.29e-6 -> 1.6e-5
+  pseudo-inverse branch of the filter: the 8 elbow-scan configurations, all six axes, both null terms .. 4.32e-6 -> 1.3e-5
+  null-space terms, position only (both, both with rest_mask = wrist, damping alone, resting alone) .... 8.35e-6 -> 2.5e-5
+  the filter: |Js M^-1 du|, du = with - without the null terms (the fp64 reference's own: 6.2e-15) .... 4.32e-6 -> 1.3e-5
+  explicit axes 0b111111 against jaco_osc: bit-identical on the emulator (measured 0); the bound is 8 ulps of an fp32 near 1 + |u|,
+  what a regrouping of the last sums could move ........................................................ 0 -> 1e-6
+  two frames on jaco2_dual_torque (position only + all six, resting term on both), B = 9 ............... 3.56e-6 -> 1.1e-5
+  position only on jaco2_torque (d12) and jaco2_reaching_torque, B = 5 ................................. 2.53e-6 -> 7.6e-6
+Closed loop (jaco2_reaching_torque, B = 8, 200 x {osc -> one substep}, position only, Damping(10), RestingConfig(q0 + [0, 0, 0, 0.4,
+-0.4, 0.4], 20, 5)): final EE position emulator - fp64 reference at most 1.60e-6 m -> bound 4.8e-6 m.  The loop does not arrive in 200 ticks of
+1 ms with force-limited motors (the reference ends centimetres from its targets), so agreement and finiteness are asserted, not arrival.
+"""
+import numpy as np
+import pytest
+
+import ik_binding as ib
+import osc_binding as ob
+import osc_task_binding as tb
+from osc_task_binding import ALL, NULL, POS
+
+MODEL = "jaco2_curtain_torque"
+B = 67
+MASKS = (0b000111, 0b111000, 0b100111, 0b011011)
+SUBSET_BOUND = 2.2e-5     # 3 x 7.20e-6 (emulator)
+COUNT_BOUND = 1.6e-5      # 3 x 5.29e-6
+PINVNULL_BOUND = 1.3e-5   # 3 x 4.32e-6
+NULL_BOUND = 2.5e-5       # 3 x 8.35e-6
+FILTER_BOUND = 1.3e-5     # 3 x 4.32e-6
+ALL6_BOUND = 1e-6         # measured 0: 8 ulps of an fp32 near 1 + |u|
+DUAL_BOUND = 1.1e-5       # 3 x 3.56e-6
+LAYOUT_BOUND = 7.6e-6     # 3 x 2.53e-6
+LOOP_BOUND = 4.8e-6       # m; 3 x 1.60e-6
+NULL_CASES = {   # task keywords, rest_mask (None: no resting term)
+    "both": (NULL, 0),
+    "both_wrist": (NULL, 0b111000),
+    "damping": (dict(null_kv=NULL["null_kv"]), None),
+    "resting": (dict(rest_kp=NULL["rest_kp"], rest_kv=NULL["rest_kv"]), 0),
+}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def frame_of(model, name):
+    return ib.table_of(model).jaco_frame(name)
+
+
+def motors(model, dofs):
+    m = ob.motor_of(model)
+    return [m[d] for d in dofs]
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    """The inputs of the existing OSC tests and jaco_osc's emulated answer, computed once."""
+    q, v = ob.states(MODEL, B)
+    T6 = ob.targets6(MODEL, "EE", q)
+    tp, tq = ob.kernel_targets(T6[:, None, :])
+    fr = [frame_of(MODEL, "EE")]
+    return dict(q=q, v=v, T6=T6[:, None, :], tp=tp, tq=tq, fr=fr, osc=ob.osc(MODEL, fr, q, v, tp, tq))
+
+
+@pytest.fixture(scope="module")
+def position_only(inputs):
+    """Position-only control without a null term: the fp64 reference and the emulator's answer (cases 2 and 5 share them)."""
+    g = inputs
+    return dict(ref=tb.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"], axes=POS), r=tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], None, axes=POS))
+
+
+def test_restatement_is_anchored_to_the_six_axis_reference(inputs):
+    g = inputs
+    U = ob.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"])[0]
+    R = tb.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"])
+    d = np.abs(R["u"] - U).max()
+    print("MEASURE anchor: restatement - osc_binding.reference max %.3g" % d)
+    assert d <= 1e-12, d
+
+
+@pytest.mark.parametrize("mask", MASKS)
+def test_regular_branch_under_axis_subsets(inputs, position_only, mask):
+    g = inputs
+    ref = position_only["ref"] if mask == POS else tb.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"], axes=mask)
+    r = position_only["r"] if mask == POS else tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], g["tq"] if mask & 56 else None, axes=mask)
+    D = ref["det"][:, 0]
+    knife = (D > 2.5e-4) & (D < 4e-3)
+    reg = D >= 4e-3
+    assert knife.mean() <= 0.2, knife.sum()
+    if mask == POS:   # position only: fp64 |det X| is 5.07e-3 .. 1.09e-2 on these states, five times above the 1e-3 threshold
+        assert D.min() >= 5e-3 and reg.all()
+    err = ob.error(r["ctrl"][:, :6], ref["u"][:, 0])
+    print("MEASURE subset %s: fp64 |det| %.3g .. %.3g, %d envs compared, error max %.3g" % (bin(mask), D.min(), D.max(), reg.sum(), err[reg].max()))
+    assert (r["status"][reg, 0] == 0).all() and not ref["sing"][reg].any()
+    assert err[reg].max() <= SUBSET_BOUND, err[reg].max()
+    assert (bits(r["ctrl"][:, 6:]) == 0).all()
+
+
+def test_fewer_dofs_than_rows_take_the_pseudo_inverse_by_count(inputs):
+    g = inputs
+    ref = tb.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"], axes=POS, dof_mask=0b11)
+    assert ref["acts"][0] == [0, 1] and ref["sing"].all()
+    cin = np.random.default_rng(4).normal(size=(B, 9)).astype(np.float32)
+    r = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], None, cin, axes=POS, dof_mask=0b11)
+    err = ob.error(r["ctrl"][:, :2], ref["u"][:, 0, :2])
+    print("MEASURE count: n = 2 < k = 3, error max %.3g" % err.max())
+    assert (r["status"] == 1).all()
+    assert (bits(r["ctrl"][:, 2:]) == bits(cin[:, 2:])).all()
+    assert err.max() <= COUNT_BOUND, err.max()
+
+
+def test_pseudo_inverse_branch_serves_the_filter():
+    q, v = ob.singular_states(MODEL, "EE", want=8)
+    T6 = ob.targets6(MODEL, "EE", q)[:, None, :]
+    tp, tq = ob.kernel_targets(T6)
+    rest = tb.rest_rows(MODEL, "EE", q)
+    ref = tb.reference(MODEL, ["EE"], q, v, T6, axes=ALL, rest_qpos=rest, **NULL)
+    assert ref["sing"].all() and (ref["det"] < 2.5e-4).all()
+    r = tb.osc_task(MODEL, [frame_of(MODEL, "EE")], q, v, tp, tq, None, rest, axes=ALL, **NULL)
+    plain = ob.reference(MODEL, ["EE"], q, v, T6)[0]
+    assert np.abs(ref["u"][:, 0] - plain[:, 0]).max() > 1.0   # (the filter lets something through: the matrix has lost rank)
+    err = ob.error(r["ctrl"][:, :6], ref["u"][:, 0])
+    print("MEASURE pinv + null: error max %.3g" % err.max())
+    assert (r["status"] == 1).all()
+    assert err.max() <= PINVNULL_BOUND, err.max()
+
+
+def null_case(g, label):
+    kw, rm = NULL_CASES[label]
+    rest = None if rm is None else tb.rest_rows(MODEL, "EE", g["q"], mask=rm)
+    ref = tb.reference(MODEL, ["EE"], g["q"], g["v"], g["T6"], axes=POS, rest_qpos=rest, rest_mask=rm or 0, **kw)
+    return rest, dict(axes=POS, rest_mask=rm or 0, **kw), ref
+
+
+@pytest.mark.parametrize("label", list(NULL_CASES))
+def test_null_space_terms_match_the_fp64_reference(inputs, position_only, label):
+    g = inputs
+    rest, task, ref = null_case(g, label)
+    r = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], None, None, rest, **task)
+    assert np.abs(ref["u"] - position_only["ref"]["u"]).max() > 1.0   # (the term matters)
+    err = ob.error(r["ctrl"][:, :6], ref["u"][:, 0])
+    print("MEASURE null %s: error max %.3g" % (label, err.max()))
+    assert (r["status"] == 0).all() and np.isfinite(r["ctrl"]).all()
+    assert err.max() <= NULL_BOUND, err.max()
+
+
+def test_null_space_torques_do_not_move_the_task(inputs, position_only):
+    g = inputs
+    rest, task, ref = null_case(g, "both")
+    r = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], None, None, rest, **task)
+    du = r["ctrl"][:, :6].astype(np.float64) - position_only["r"]["ctrl"][:, :6].astype(np.float64)
+    img = np.array([np.abs(ref["Js"][e][0] @ np.linalg.solve(ref["M"][e][0], du[e])).max() for e in range(B)])
+    du_ref = ref["u"][:, 0] - position_only["ref"]["u"][:, 0]
+    img_ref = np.array([np.abs(ref["Js"][e][0] @ np.linalg.solve(ref["M"][e][0], du_ref[e])).max() for e in range(B)])
+    n = np.linalg.norm(du, axis=1)
+    print("MEASURE filter: |Js M^-1 du| max %.3g (fp64 reference %.3g), |du| %.3g .. %.3g" % (img.max(), img_ref.max(), n.min(), n.max()))
+    assert np.abs(du).max() > 1.0   # (du is not zero: the terms act)
+    assert img.max() <= FILTER_BOUND, img.max()
+
+
+def test_null_task_record_is_jaco_osc_and_explicit_six_axes_agree_with_it(inputs):
+    g = inputs
+    same = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], g["tq"], no_task=True)
+    assert (bits(same["ctrl"]) == bits(g["osc"]["ctrl"])).all() and (same["status"] == g["osc"]["status"]).all()
+    six = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], g["tq"], axes=ALL)
+    err = ob.error(six["ctrl"][:, :6], g["osc"]["ctrl"][:, :6])
+    print("MEASURE all six - jaco_osc: error max %.3g, bit-identical: %s" % (err.max(), (bits(six["ctrl"]) == bits(g["osc"]["ctrl"])).all()))
+    assert (six["status"] == g["osc"]["status"]).all()
+    assert err.max() <= ALL6_BOUND, err.max()
+    zero = tb.osc_task(MODEL, g["fr"], g["q"], g["v"], g["tp"], g["tq"], axes=0)   # (an axes word of 0 = all six)
+    assert (bits(zero["ctrl"]) == bits(six["ctrl"])).all()
+
+
+def test_two_frames_with_different_axes_and_a_resting_term_on_both():
+    model, names, nenv = "jaco2_dual_torque", ["EE_1", "EE_2"], 9
+    q, v = ob.states(model, nenv)
+    T6 = np.stack([ob.targets6(model, n, q) for n in names], 1)
+    tp, tq = ob.kernel_targets(T6)
+    rest = tb.rest_rows(model, "EE_1", q)
+    other = tb.rest_rows(model, "EE_2", q, seed=18)
+    rest = np.where(np.isnan(rest), other, rest)
+    kw = dict(rest_kp=NULL["rest_kp"], rest_kv=NULL["rest_kv"])
+    ref = tb.reference(model, names, q, v, T6, axes=[POS, ALL], rest_qpos=rest, **kw)
+    fr = [frame_of(model, n) for n in names]
+    cin = np.random.default_rng(6).normal(size=(nenv, 18)).astype(np.float32)
+    r = tb.osc_task(model, fr, q, v, tp, tq, cin, rest, axes=[POS, ALL], **kw)
+    mine = [motors(model, a) for a in ref["acts"]]
+    err = max(ob.error(r["ctrl"][:, mine[f]], ref["u"][:, f]).max() for f in range(2))
+    print("MEASURE dual: error max %.3g" % err)
+    assert (r["status"] == 0).all() and not ref["sing"].any()
+    assert err <= DUAL_BOUND, err
+    others = [a for a in range(18) if a not in mine[0] + mine[1]]
+    assert len(others) == 6 and (bits(r["ctrl"][:, others]) == bits(cin[:, others])).all()
+    one = tb.osc_task(model, fr[:1], q, v, tp[:, :1], None, cin, rest, axes=POS, **kw)   # one arm alone: the other arm's words pass through too
+    assert (bits(one["ctrl"][:, others + mine[1]]) == bits(cin[:, others + mine[1]])).all()
+    assert (bits(one["ctrl"][:, mine[0]]) == bits(r["ctrl"][:, mine[0]])).all()
+
+
+@pytest.mark.parametrize("model", ["jaco2_torque", "jaco2_reaching_torque"])
+def test_position_only_on_the_other_builds(model):
+    q, v = ob.states(model, 5)
+    T6 = ob.targets6(model, "EE", q)[:, None, :]
+    tp = ob.kernel_targets(T6)[0]
+    ref = tb.reference(model, ["EE"], q, v, T6, axes=POS)
+    r = tb.osc_task(model, [frame_of(model, "EE")], q, v, tp, None, axes=POS)
+    err = ob.error(r["ctrl"][:, motors(model, ref["acts"][0])], ref["u"][:, 0])
+    print("MEASURE layout %s: fp64 |det| min %.3g, error max %.3g" % (model, ref["det"].min(), err.max()))
+    assert (ref["det"] >= 4e-3).all() and (r["status"] == 0).all()
+    assert err.max() <= LAYOUT_BOUND, err.max()
+
+
+@pytest.mark.parametrize("case", list(tb.REFUSALS))
+def test_refusals(inputs, case):
+    g = inputs
+    tq, rest, task = tb.refusal_args(case)
+    with pytest.raises(ValueError) as e:
+        tb.osc_task(MODEL, g["fr"], g["q"][:2], g["v"][:2], g["tp"][:2], tq, None, rest, **task)
+    assert str(e.value) == "emu_osc_task returned -1: jaco_osc_task: " + tb.REFUSALS[case]
+
+
+def test_every_refusal_of_jaco_osc_is_kept_and_a_missing_quaternion_is_allowed_without_rotational_rows(inputs):
+    g = inputs
+    q, v, tp = g["q"][:2], g["v"][:2], g["tp"][:2]
+    with pytest.raises(ValueError, match="jaco_osc_task: kp, ko, kv, vmax_xyz and vmax_abg must be positive"):
+        tb.osc_task(MODEL, g["fr"], q, v, tp, None, axes=POS, kv=0.0)
+    with pytest.raises(ValueError, match="are required"):
+        tb.osc_task(MODEL, g["fr"], q, v, None, None, axes=POS)
+    with pytest.raises(ValueError, match=r"outside \[1, 2\]"):
+        tb.osc_task(MODEL, g["fr"] * 3, q, v, tp, None, raw_axes=(POS, POS))
+    for axes in (ALL, 0, 0b001000):
+        with pytest.raises(ValueError, match="rotational axis"):
+            tb.osc_task(MODEL, g["fr"], q, v, tp, None, axes=axes)
+    # a resting term whose mask keeps one active dof is accepted, and a rest row is not read without one
+    ok = tb.osc_task(MODEL, g["fr"], q, v, tp, None, None, tb.rest_rows(MODEL, "EE", q, mask=0b100000), axes=POS, rest_kp=1.0, rest_mask=0b1100000)
+    assert np.isfinite(ok["ctrl"]).all()
+
+
+def test_closed_loop_follows_the_fp64_reference():
+    q0, T6 = ob.loop_inputs()
+    rest = tb.loop_rest(q0)
+    qo = tb.closed_loop_oracle(q0, T6, rest)
+    qe = tb.closed_loop_emu(q0, T6, rest)
+    com = ib.table_of(ob.LOOP_MODEL).com("EE")
+    po, pe = ib.oracle_pose(ob.LOOP_MODEL, "EE", com, qo)[0], ib.oracle_pose(ob.LOOP_MODEL, "EE", com, qe)[0]
+    left = np.linalg.norm(po - T6[:, :3], axis=1)
+    d = np.linalg.norm(pe - po, axis=1)
+    print("MEASURE loop: the reference ends %.3g .. %.3g m from its targets; EE distance emulator - reference max %.3g m" % (left.min(), left.max(), d.max()))
+    assert np.isfinite(qe).all()
+    assert d.max() <= LOOP_BOUND, d
+
+
+def test_batched_osc_with_ctrlr_dof_and_null_controllers_reproduces_the_raw_call(inputs):
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedMujocoConfig, BatchedOSC, Damping, RestingConfig
+    g = inputs
+    sim = tb.EmuOscTaskSim(MODEL, g["q"], g["v"])
+    a, b, c = 0.3, -1.1, 2.0
+    ctl = BatchedOSC(BatchedMujocoConfig(sim), ctrlr_dof=[1, 1, 1, 0, 0, 0], null_controllers=[Damping(10), RestingConfig([None, None, None, a, b, c], 20, 5)])
+    frame0 = [ib.table_of(MODEL).jaco_frame("EE", point=np.zeros(3))]
+    rest = np.full(g["q"].shape, np.nan, np.float32)
+    rest[:, 3:6] = np.float32([a, b, c])
+    raw = tb.osc_task(MODEL, frame0, g["q"], g["v"], g["tp"], None, None, rest, axes=POS, rest_mask=0b111000, **NULL)["ctrl"]
+    u = ctl.generate_pose(torch.tensor(g["tp"][:, 0]))
+    assert sim.entries == ["jaco_osc_task"] and (bits(u.numpy()) == bits(raw)).all()
+    u6 = ctl.generate(torch.tensor(g["T6"][:, 0], dtype=torch.float32))   # abr_control's six-wide target: the angles are not used
+    assert (bits(u6.numpy()) == bits(raw)).all()
+    # a [B, chain length] tensor of rest angles holds every joint of the chain, per env
+    per_env = tb.rest_rows(MODEL, "EE", g["q"])
+    ctl2 = BatchedOSC(BatchedMujocoConfig(sim), ctrlr_dof=[1, 1, 1, 0, 0, 0], null_controllers=[RestingConfig(torch.tensor(per_env[:, :6]), 20, 5)])
+    raw2 = tb.osc_task(MODEL, frame0, g["q"], g["v"], g["tp"], None, None, per_env, axes=POS, rest_kp=20.0, rest_kv=5.0)["ctrl"]
+    assert (bits(ctl2.generate_pose(torch.tensor(g["tp"][:, 0])).numpy()) == bits(raw2)).all()
+    # a rotational axis needs a quaternion
+    rot = BatchedOSC(BatchedMujocoConfig(sim), ctrlr_dof=[1, 1, 1, 0, 0, 1])
+    with pytest.raises(ValueError, match="needs target quaternions"):
+        rot.generate_pose(torch.tensor(g["tp"][:, 0]))
+    with pytest.raises(ValueError, match="needs target quaternions"):
+        BatchedOSC(BatchedMujocoConfig(sim)).generate_pose(torch.tensor(g["tp"][:, 0]))
+    with pytest.raises(ValueError, match="at most one RestingConfig"):
+        BatchedOSC(BatchedMujocoConfig(sim), null_controllers=[RestingConfig([0.0] * 6, 1, 1)] * 2)
+    # without the new arguments the controller hands sim.osc no task keyword: the call is jaco_osc
+    sim.entries.clear()
+    plain = BatchedOSC(BatchedMujocoConfig(sim))
+    assert plain.task == {}
+    plain.generate_pose(torch.tensor(g["tp"][:, 0]), torch.tensor(g["tq"][:, 0]))
+    assert sim.entries == ["jaco_osc"]
+
+
+def test_batched_mujoco_osc_reaches_jaco_osc_unless_a_task_keyword_is_given():
+    """BatchedMujoco.osc's choice of entry, on a stand-in library that records the calls (no device)."""
+    import torch
+    from mujoco_jaco_amd import _lib
+    from mujoco_jaco_amd.physics import BatchedMujoco
+    calls = []
+
+    class Recorder:
+        def __getattr__(self, name):
+            return lambda *a: (calls.append((name, a)), 0)[1]
+
+    sim = object.__new__(BatchedMujoco)
+    sim.num_envs, sim.device, sim.nq, sim.nv, sim.nu, sim.h, sim.L = 2, "cpu", 23, 21, 9, None, Recorder()
+    sim._dev = lambda t, n, dtype=torch.float32: None if t is None else t.data_ptr()
+    sim._stream = lambda: None
+    fr = [frame_of(MODEL, "EE")]
+    tp, tq = torch.zeros(2, 1, 3), torch.zeros(2, 1, 4)
+    sim.osc(fr, tp, tq)
+    sim.osc(fr, tp, tq, kp=30.0, dof_mask=0b1111)
+    assert [c[0] for c in calls] == ["jaco_osc", "jaco_osc"] and len(calls[0][1]) == 12
+    calls.clear()
+    sim.osc(fr, tp, axes=[1, 1, 1, 0, 0, 0])
+    sim.osc(fr, tp, tq, null_kv=10.0)
+    sim.osc(fr, tp, tq, rest_qpos=torch.zeros(2, 23), rest_kp=20.0, rest_kv=5.0, rest_mask=0b111000)
+    assert [c[0] for c in calls] == ["jaco_osc_task"] * 3 and all(len(c[1]) == 14 for c in calls)
+    task = ctypes_task(calls[0][1][4])
+    assert list(task.axes) == [POS, 0] and calls[0][1][8] is None     # position only: no quaternion buffer
+    task = ctypes_task(calls[2][1][4])
+    assert (task.rest_kp, task.rest_kv, task.rest_mask) == (20.0, 5.0, 0b111000) and calls[2][1][9] is not None
+    assert _lib.osc_axes([[1, 1, 1, 0, 0, 0], 0b111111], 2) == (POS, ALL) and _lib.osc_axes(POS, 2) == (POS, POS)
+    with pytest.raises(ValueError, match="select no row"):
+        _lib.osc_axes([0] * 6, 1)
+
+
+def ctypes_task(pointer):
+    import ctypes
+    from mujoco_jaco_amd import _lib
+    return ctypes.cast(pointer, ctypes.POINTER(_lib.JacoOscTask)).contents
