@@ -129,14 +129,13 @@ JDEV void collide_plane_convex(const JacoStepArgs& A, const JacoModelDev* m, L& 
 // lanes one edge crossing each.  Contacts come out row by row, within a row in candidate order (vertices, corners, crossings).
 // Row r handles candidate cbase + r of the list; lane c of the A-arrays holds candidate c's pair index, code and contact bookkeeping.
 template <class L>
-JDEV void collide_box_box4(const JacoModelDev* m, L& s, int cbase, int nrows, int pkA, int codeA, unsigned m1A, unsigned m2A, int obA, int dimA,
+JDEV void collide_box_box4(const JacoModelDev* m, L& s, int cbase, int nrows, int pkA, int codeA, int obA, int dimA,
                            v3 saA, v3 sbA, int lane, int& ncon, unsigned& flags) {
   constexpr int MAXCON = L::Caps::MAXCON;
   const int g = lane >> 4, a = lane & 15, rb = lane & 48;
   const bool slot = g < nrows;
   const int src = cbase + (slot ? g : 0);
   const int code = wave_shfl_i(codeA, src), pair = wave_shfl_i(pkA, src);
-  const unsigned pm1 = (unsigned)wave_shfl_i((int)m1A, src), pm2 = (unsigned)wave_shfl_i((int)m2A, src);
   const int pob = wave_shfl_i(obA, src), pdim = wave_shfl_i(dimA, src);
   const int g1 = code & 255, g2 = (code >> 8) & 255;
   GeomPose P1 = geom_pose(s, g1), P2 = geom_pose(s, g2);
@@ -288,11 +287,11 @@ JDEV void collide_box_box4(const JacoModelDev* m, L& s, int cbase, int nrows, in
   const int i1 = ncon + off + popc64(r1 & below), i2 = ncon + off + popc64(r1) + popc64(r2 & below);
   if (h1 && i1 < MAXCON) {
     s.c_dist[i1] = d1; st3(s.c_pos[i1], x1); make_frame(nrm, s.c_frame[i1]); s.c_pair[i1] = pair;
-    s.c_m1[i1] = pm1; s.c_m2[i1] = pm2; s.c_ob[i1] = pob; s.c_dim[i1] = pdim;
+    s.c_ob[i1] = pob; s.c_dim[i1] = pdim;
   }
   if (h2 && i2 < MAXCON) {
     s.c_dist[i2] = d2; st3(s.c_pos[i2], x2); make_frame(nrm, s.c_frame[i2]); s.c_pair[i2] = pair;
-    s.c_m1[i2] = pm1; s.c_m2[i2] = pm2; s.c_ob[i2] = pob; s.c_dim[i2] = pdim;
+    s.c_ob[i2] = pob; s.c_dim[i2] = pdim;
   }
   if (ncon + tot > MAXCON) { flags |= JFLAG_CON_OVERFLOW; tot = MAXCON - ncon; }
   ncon += tot;
@@ -928,7 +927,6 @@ JDEV void stage_collision(const JacoStepArgs& A, const JacoModelDev* m, L& s, in
     const v4 rec0 = ld4(reinterpret_cast<const float*>(&m->pair_obb[pkA])), rec1 = ld4(reinterpret_cast<const float*>(&m->pair_obb[pkA]) + 4);
     const int codeA = __builtin_bit_cast(int, rec0.x);
     const v3 saA = mk3(rec0.y, rec0.z, rec0.w), sbA = mk3(rec1.x, rec1.y, rec1.z);
-    const unsigned m1A = m->pair[pkA].m1, m2A = m->pair[pkA].m2;
     const int obA = m->pair[pkA].ob, dimA = m->pair[pkA].condim;
     const unsigned long long boxes = wave_ballot(lane < nhere && ((codeA >> 16) & 255) == (JG_BOX | (JG_BOX << 4)));
     // candidates that go through MPR (neither plane-* nor box-box): two in a row can share a wave (mpr_pair2)
@@ -996,13 +994,12 @@ JDEV void stage_collision(const JacoStepArgs& A, const JacoModelDev* m, L& s, in
       if (L::Caps::MAXEFC < JacoHuge::MAXEFC && (wave_uniform_i((int)flags) & (int)JFLAG_CON_OVERFLOW)) break;
       if ((boxes >> c) & 1ull) {   // a run of up to four box-box pairs, one 16-lane row each
         const int run = ffs64(~(boxes >> c) | 16ull);
-        collide_box_box4(m, s, c, run, pkA, codeA, m1A, m2A, obA, dimA, saA, sbA, lane, ncon, flags);
+        collide_box_box4(m, s, c, run, pkA, codeA, obA, dimA, saA, sbA, lane, ncon, flags);
         c += run;
         JSTAMP_NARROW(12);
         continue;
       }
       const int pk = wave_bcast_i(pkA, c), code = wave_bcast_i(codeA, c);
-      const unsigned pm1 = (unsigned)wave_bcast_i((int)m1A, c), pm2 = (unsigned)wave_bcast_i((int)m2A, c);
       const int pob = wave_bcast_i(obA, c), pdim = wave_bcast_i(dimA, c);
       const int g1 = code & 255, g2 = (code >> 8) & 255, t1 = (code >> 16) & 15, t2 = (code >> 20) & 15;
       const int before = ncon;
@@ -1053,9 +1050,9 @@ JDEV void stage_collision(const JacoStepArgs& A, const JacoModelDev* m, L& s, in
         push_contacts(s, hit && lane == 0, -depth, pos, dir, pk, ncon, flags, 1);
         JSTAMP_NARROW(hit ? 14 : 1);
       }
-      if (ncon > before) {   // dof chain masks / body ids of the two geoms, for the row builder and the touch stage
+      if (ncon > before) {   // body ids of the two geoms and the condim, for the row builder and the touch stage
         int cc = before + lane;
-        if (cc < ncon) { s.c_m1[cc] = pm1; s.c_m2[cc] = pm2; s.c_ob[cc] = pob; s.c_dim[cc] = pdim; }
+        if (cc < ncon) { s.c_ob[cc] = pob; s.c_dim[cc] = pdim; }
       }
       c++;
     }
@@ -1112,10 +1109,8 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
   constexpr int MAXEFC = L::Caps::MAXEFC;
   constexpr bool SIDE = SideRows<L>::on;
   const int nv = m->nv, ncon = wave_uniform_i(s.ncon), nlim = wave_uniform_i(s.nlimit);
-  // per-contact parameters handed to the row lanes through LDS: a contact's chain masks are dead once its own lane has read
-  // them (each lane only ever overwrites its own contact's slots), c_fn is not yet in use
-  float* pa0 = reinterpret_cast<float*>(s.c_m1);
-  float* pbc = reinterpret_cast<float*>(s.c_m2);
+  // per-contact parameters handed to the row lanes through LDS: the contact's own lane writes a0 and 1 / R into e_aref / e_D of each of
+  // its rows (the row lanes then only fold the velocity part into e_aref) and the velocity coefficient into c_fn, which is not yet in use
   float* sd = side_buf(s);
   int rowbase = nlim, kept_total = 0, nside = 0, side_cand = 0;
   // Jacobian rows: lane = (contact slot 0..2, dof); the slot's contact data is fetched from its owner lane
@@ -1137,7 +1132,7 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
       const JacoPairParam& P = m->pair[s.c_pair[ci]];
       dim = s.c_dim[ci]; nrow = dim == 1 ? 1 : 2 * (dim - 1);
       mu0 = P.mu[0]; mu1 = P.mu[2]; mu2 = P.mu[3];   // (mu[1] == mu[0], mu[4] == mu[3]: one tangential, one rolling coefficient)
-      cm1 = s.c_m1[ci]; cm2 = s.c_m2[ci];
+      cm1 = P.m1; cm2 = P.m2;   // dof chain masks of the two bodies
       const float pos = s.c_dist[ci] - P.margin, tran = P.tran;
       float R, imp;
       a0 = row_params(P.solref, P.solimp, pos, 0.f, dim == 1 ? tran : tran + mu0 * mu0 * tran, &R, &imp);
@@ -1197,16 +1192,16 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
       if (!sidec) for (int e = 0; e < nrow; e++) {
         s.e_con[r0 + e] = ci | (e << 8) | (blk << 16) | bodies;
         s.e_f[r0 + e] = e < 4 ? mu0 : (e < 6 ? mu1 : mu2);   // friction of the row's pyramid edge (e_f is free until the solver runs)
+        s.e_aref[r0 + e] = a0; s.e_D[r0 + e] = dinv;
       }
-      pa0[ci] = a0; pbc[ci] = bcoef; s.c_fn[ci] = dinv;
+      s.c_fn[ci] = bcoef;
     }
     wave_sync();   // e_con, the per-contact parameters and the row maps are visible
     // per-row parameters of this chunk's main rows, lane = row (before the Jacobian rows: in split mode those overwrite cvel)
     for (int rr = rowbase + lane; rr < total; rr += 64) {
       const int ce = s.e_con[rr], c = ce & 255, e = (ce >> 8) & 255;
       const float vel = contact_row_vel(s, c, e, s.e_f[rr]);
-      s.e_aref[rr] = pa0[c] - pbc[c] * vel;
-      s.e_D[rr] = s.c_fn[c];
+      s.e_aref[rr] = s.e_aref[rr] - s.c_fn[c] * vel;
     }
     // ... and of the side rows, by their contact's own lane, into registers (the side buffer overlays cvel, which is still being read)
     float aside[4] = {0.f, 0.f, 0.f, 0.f};

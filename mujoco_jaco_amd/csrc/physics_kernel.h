@@ -31,7 +31,7 @@
 //   J v      = w . D_c,  D_c = signed sum of S_k v_k over the dofs that move exactly one of the contact's two bodies (lane = (contact, component))
 //   J^T D J  = the matrix-core pass generates its J entries on the fly: lane (column k) holds S_k and forms sgn_k(r) w_r . S_k per row
 //   J^T f    = S_k . (sum of the wrenches of the contacts dof k moves)
-// so the light tier holds 128 rows in the LDS that holds 64 dense ones (13 584 B, 168 VGPRs, 3 waves per SIMD either way; medium / heavy /
+// so the light tier holds 128 rows in the LDS that holds 64 dense ones (13 584 B at the time, 168 VGPRs, 3 waves per SIMD either way; medium / heavy /
 // huge: 14.7 / 22.1 / 39.5 KB instead of 20.2 / 43 / 80 KB).  Joint-limit rows (J = +-e_d) are "unit rows": flag + dof + sign.
 // Parity: every emulator suite green (tests/, built with -DJACO_WRENCH=1).  MEASURED on MI355X (profiles/r05_ab_wrench_rows.txt): headline
 // 1.84 -> 1.70 M env-steps/s, action scale 0.05 0.50 -> 0.21 M, policy-driven 1.33 -> 1.22 M -- the envs do stay in the light tier (bigger-tier
@@ -279,7 +279,10 @@ JDEV int m_index(int d, int j) {   // (d, j in the same block)
 //   * body inertias / forces (tree walk .. mass matrix)            with   the contact list (collision .. Euler);
 //   * geom poses + broadphase survivors (tree walk .. collision)   with   the constraint rows (row builders .. Euler), behind the
 //     first JSCRATCH floats of that area, which the early stages use as scratch.
-// Light tier: 13.3 KB -> 12 envs per CU (3 waves per SIMD); it was 20.5 KB -> 8.
+// The hardware hands LDS out in blocks of 1 280 bytes (160 KB / 128; measured with tools/gpu_residency.py, profiles/residency.txt): a
+// workgroup of n bytes takes ceil(n / 1280) blocks, so twelve one-wave workgroups fit a CU up to 12 800 B each and eleven up to 14 080 B.
+// Light tier: 12 672 B -> 12 envs per CU (3 waves per SIMD).  It was 13 584 B, which the device ran at 11 per CU (the 12 of 160 KB / 13 584
+// and of the occupancy calculator ignore the block size), and 20.5 KB before that.
 // (body-space rows only: per-body dof chain masks; an empty base otherwise -- four more bytes take the medium tier from 20 480 B = 8 workgroups
 //  per CU to 20 496 B = 7)
 template <bool W> struct JacoChainTab { unsigned b_chain[JNB]; };   // bit d set: dof d moves body b
@@ -303,10 +306,12 @@ struct JacoLDS {
     };
     struct {                                    // collision .. Euler: contacts
       float c_dist[C::MAXCON], c_pos[C::MAXCON][3], c_frame[C::MAXCON][9], c_fn[C::MAXCON];
-      int c_pair[C::MAXCON], c_efc[C::MAXCON];
-      unsigned c_m1[C::MAXCON], c_m2[C::MAXCON];   // dof chain masks of the two bodies
       int c_ob[C::MAXCON];                          // per geom: original (unfused) body id | (fused body + 1) << 8; geom 2 in the upper half
-      int c_dim[C::MAXCON];
+      // small integers in sub-word arrays (ds_read_u16 / ds_read_u8 widen for free): pair index < JMAXPAIR, first row < JSIDE_BASE + JSIDE_ROWS
+      // or the tier's MAXEFC, condim 1 / 3 / 6.  The pair's dof chain masks are not kept: the row builder reads them from the pair record,
+      // next to the friction coefficients it fetches anyway.
+      unsigned short c_pair[C::MAXCON], c_efc[C::MAXCON];
+      unsigned char c_dim[C::MAXCON];
     };
   };
   union {
@@ -333,14 +338,16 @@ struct JacoLDS {
   // per-launch copy of the small, hot model tables (per-lane gathers from LDS instead of dependent global loads)
   struct McTab : JacoChainTab<C::WRENCH> {
     float b_pos[JNB][3], b_mat[JNB][9], b_axis[JNB][3], b_com[JNB][3], b_qpos0[JNB];
-    int b_jtype[JNB], b_qadr[JNB], b_dadr[JNB], b_parent[JNB];
     int inner_body[JMAXINNER];
     unsigned b_descmask[JNB];
-    int b_anc[JNB][3];                          // ancestors 1, 2 and 4 levels up (-1: none), for the pointer-jumping tree stages
-    int d_body[JNV], d_parent[JNV];
-    int q_dof[JNQ + 1];                         // dof that advances position coordinate q linearly (hinge angle, free-body translation), -1: quaternion component
+    // body / dof / coordinate indices, all in [-1, 32]: one byte each (ds_read_i8 sign-extends for free)
+    signed char b_jtype[JNB], b_qadr[JNB], b_dadr[JNB], b_parent[JNB];
+    signed char b_anc[JNB][3];                  // ancestors 1, 2 and 4 levels up (-1: none), for the pointer-jumping tree stages
+    signed char d_body[JNV], d_parent[JNV];
+    signed char q_dof[JNQ + 1];                 // dof that advances position coordinate q linearly (hinge angle, free-body translation), -1: quaternion component
   } mc;
 };
+static_assert(JMAXPAIR <= 65536 && JNB <= 127 && JNQ <= 127, "sub-word index arrays of JacoLDS: pair indices in 16 bits, body / dof / coordinate indices in a signed byte");
 static_assert((JB1 - JB0 == 6 || JB1 == JB0) && (JNV - JB1 == 6 || JNV == JB1) && JB0 >= 6 && JNV <= 31 && JNV - JB0 <= 15 && JNV <= 64,
               "dof blocks: the arm tree(s) of at least the six arm joints, then zero, one or two free bodies; dofs + the residual column fit the 32-column matrix-core tile");
 
@@ -2531,7 +2538,13 @@ again:
 #endif
 // light tier: one workgroup (= one wavefront) per env
 #ifndef JACO_LIGHT_WAVES
-#define JACO_LIGHT_WAVES 3   // waves per SIMD the light kernel is compiled for: 13.3 KB of LDS per env allow 12 envs per CU, 168 VGPRs each
+#define JACO_LIGHT_WAVES 3   // waves per SIMD the light kernel is compiled for: 12 envs per CU, 168 VGPRs each -- and 12 800 B of LDS each at most
+#endif
+#define JACO_LDS_GRANULE 1280   // bytes per LDS allocation block on MI355X (measured: profiles/residency.txt)
+#define JACO_LDS_PER_CU (160 * 1024)
+#if JNB == 11 && JNV == 21 && JMAXGEOM == 64 && !JACO_WRENCH
+static_assert((sizeof(JacoLDS<JacoLight>) + JACO_LDS_GRANULE - 1) / JACO_LDS_GRANULE * JACO_LDS_GRANULE * (4 * JACO_LIGHT_WAVES) <= JACO_LDS_PER_CU,
+              "default layout: the light tier's LDS, rounded up to whole allocation blocks, must fit 4 x JACO_LIGHT_WAVES envs per CU (<= 12 800 B)");
 #endif
 template <bool FULL, class C = JacoLight>
 JDEV void light_grid(const JacoStepArgs& A, JacoLDS<C>& s) {
