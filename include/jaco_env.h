@@ -321,6 +321,39 @@ int jaco_osc_task(JacoHandle* h, const JacoFrame* frames_host, int nframes, cons
                   const float* qpos_dev, const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev,
                   const float* rest_qpos_dev, const float* ctrl_in_dev, float* ctrl_out_dev, int32_t* status_dev, void* stream);
 
+/* ---- joint-space controller and inverse dynamics: which torques drive the arm to this configuration?  abr_control's
+ * Joint(robot_config, kp, kv).generate(q, dq, target, target_velocity) with a feed-forward acceleration, for any set of motor-driven hinge
+ * dofs, in one kernel launch (mujoco_jaco_amd/csrc/joint.h).  For each env, with the values of a sim.forward() on the given state (qM,
+ * qfrc_bias) and the active dof set A = the dofs of dof_mask (bit d = dof d), or every hinge dof with a motor actuator when that is 0 --
+ * not limited to six: the two-arm model's twelve go in one call:
+ *   e_d = q*_d - q_d for a limited joint; e_d = ((q*_d - q_d + pi) mod 2 pi) - pi in [-pi, pi) (floor-style modulus) for an unlimited
+ *         one.  abr_control wraps every joint; a limited joint is never wrapped here, so that a long move (Jaco joint 2: 260 degrees)
+ *         is not sent the short way through the limit.  e = 0 without target_qpos_dev;
+ *   s   = min(1, (vmax kv / kp) / max over A of |e_d|) when vmax > 0 and kp > 0, else 1: one scale for every dof (the move stays a
+ *         straight line in joint space);
+ *   a_d = qacc_ff_d + kp s e_d + kv (dq*_d - dq_d) for d in A, 0 for every other dof; a NULL input counts as zeros;
+ *   u_d = sum over k in A of M[d][k] a_k + qfrc_bias_d,  M the submatrix of qM on A (as in jaco_osc; not a Schur complement).
+ * Joint damping is not compensated.  Modes: kp = kv = 0 with qacc_ff_dev is inverse dynamics (the torques for a wanted joint
+ * acceleration); kp = kv = 0 with no target and no qacc_ff_dev is bias compensation (u = qfrc_bias on A; abr_control's Floating); kp = 0,
+ * kv > 0 without targets adds the damping -kv M dq to it.
+ * Inputs (device): qpos_dev / qvel_dev as in jaco_osc (NULL = the handle's state); target_qpos_dev [num_envs][nq] (or NULL), read only
+ * at the qpos addresses of the active dofs, so a jaco_ik result row goes in as it is; target_qvel_dev, qacc_ff_dev [num_envs][nv] (or
+ * NULL); ctrl_in_dev [num_envs][nu] (NULL = zeros).  Output: ctrl_out_dev [num_envs][nu] = the ctrl_in row with u_d at the motor
+ * actuator of every active dof and every other word copied bit for bit; it may be ctrl_in_dev itself.  No clamping.  opt_host NULL =
+ * JACO_JOINT_DEFAULTS.  Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch, no allocation, no
+ * synchronisation, no host copy.
+ * JACO_EINVAL for a dof_mask bit on a free-joint dof, on a dof without a motor actuator (the finger position servos) or at or beyond nv,
+ * an empty active set, a negative or non-finite kp, kv or vmax, kp > 0 with a NULL target_qpos_dev, and a NULL ctrl_out_dev. */
+typedef struct JacoJointOptions {
+  float kp, kv;        /* >= 0, finite; 50, 20 */
+  float vmax;          /* rad/s, >= 0; 0 = no limiting */
+  int32_t reserved;
+  uint64_t dof_mask;   /* 0 = every hinge dof that has a motor actuator */
+} JacoJointOptions;
+#define JACO_JOINT_DEFAULTS {50.f, 20.f, 0.f, 0, 0}
+int jaco_joint(JacoHandle* h, const JacoJointOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* target_qpos_dev,
+               const float* target_qvel_dev, const float* qacc_ff_dev, const float* ctrl_in_dev, float* ctrl_out_dev, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

@@ -72,6 +72,18 @@ class JacoOscTask(ctypes.Structure):
         super().__init__(**f)
 
 
+class JacoJointOptions(ctypes.Structure):
+    """JacoJointOptions of include/jaco_env.h; a fresh instance holds the API defaults (JACO_JOINT_DEFAULTS)."""
+    _fields_ = [("kp", ctypes.c_float), ("kv", ctypes.c_float), ("vmax", ctypes.c_float), ("reserved", ctypes.c_int32), ("dof_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(kp=50.0, kv=20.0, vmax=0.0, dof_mask=0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown joint-controller option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
 def osc_axes(axes, nframes):
     """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
     or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
@@ -160,6 +172,7 @@ SYMBOLS = {
     "jaco_ik": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_osc": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_osc_task": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_joint": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

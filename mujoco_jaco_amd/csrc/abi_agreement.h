@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h and osc_task.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h and joint.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -30,3 +30,7 @@ static_assert(sizeof(JacoOscTask) == sizeof(JacoOscTaskOpts) && offsetof(JacoOsc
                   offsetof(JacoOscTask, null_kv) == offsetof(JacoOscTaskOpts, null_kv) && offsetof(JacoOscTask, rest_kp) == offsetof(JacoOscTaskOpts, rest_kp) &&
                   offsetof(JacoOscTask, rest_kv) == offsetof(JacoOscTaskOpts, rest_kv) && offsetof(JacoOscTask, rest_mask) == offsetof(JacoOscTaskOpts, rest_mask),
               "JacoOscTask of the public header and the kernel's task record must agree");
+static_assert(sizeof(JacoJointOptions) == sizeof(JacoJointOpts) && offsetof(JacoJointOptions, kp) == offsetof(JacoJointOpts, kp) &&
+                  offsetof(JacoJointOptions, kv) == offsetof(JacoJointOpts, kv) && offsetof(JacoJointOptions, vmax) == offsetof(JacoJointOpts, vmax) &&
+                  offsetof(JacoJointOptions, dof_mask) == offsetof(JacoJointOpts, dof_mask),
+              "JacoJointOptions of the public header and the kernel's option record must agree");

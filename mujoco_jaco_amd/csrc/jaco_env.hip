@@ -1024,3 +1024,25 @@ extern "C" int jaco_osc_task(JacoHandle* h, const JacoFrame* frames_host, int nf
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- joint-space controller and inverse dynamics (joint.h): one wavefront per env, nothing of the handle written -------------------
+extern "C" int jaco_joint(JacoHandle* h, const JacoJointOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* target_qpos_dev,
+                          const float* target_qvel_dev, const float* qacc_ff_dev, const float* ctrl_in_dev, float* ctrl_out_dev, void* stream) {
+  if (!h) return JACO_EINVAL;
+  const JacoJointOptions defaults = JACO_JOINT_DEFAULTS;
+  JacoJointOpts opt;
+  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoJointOptions));
+  JacoJointArgs Q{};
+  Q.target_qpos = target_qpos_dev; Q.target_qvel = target_qvel_dev; Q.qacc_ff = qacc_ff_dev; Q.ctrl_in = ctrl_in_dev; Q.ctrl_out = ctrl_out_dev;
+  const std::string why = jaco_joint_resolve(h->model_host, opt, &Q);
+  if (!why.empty()) { h->err = "jaco_joint: " + why; return JACO_EINVAL; }
+  ENTER(h);
+  Q.model = h->model_dev;
+  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
+  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
+  Q.nenv = h->num_envs;
+  jaco_launch_joint((unsigned)h->num_envs, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

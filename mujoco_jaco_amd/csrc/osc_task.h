@@ -298,3 +298,5 @@ void jaco_launch_osc_task(unsigned grid, hipStream_t st, const JacoOscTaskArgs& 
 void jaco_launch_osc_task(unsigned grid, hipStream_t st, const JacoOscTaskArgs& T) { hipLaunchKernelGGL(jaco_osc_task_kernel, dim3(grid), dim3(64), 0, st, T); }
 #endif
 #endif
+
+#include "joint.h"

@@ -250,6 +250,28 @@ class BatchedMujoco:
                                            self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(rest, self.nq), *tail))
         return {"ctrl": out, "singular": status != 0}
 
+    # ---- joint-space controller and inverse dynamics (jaco_joint: abr_control's Joint.generate per env, one launch)
+    def joint(self, target_qpos=None, target_qvel=None, qacc=None, qpos=None, qvel=None, ctrl=None, **options):
+        """The torques that drive the arm to the configuration target_qpos [B, nq] (read only at the qpos addresses of the active dofs: a
+        row of ik()["qpos"] goes in as it is) with the joint velocities target_qvel [B, nv] and the feed-forward accelerations qacc
+        [B, nv] (each None: zeros; without target_qpos there is no position term and kp must be 0), from the values of a forward pass
+        on qpos [B, nq] / qvel [B, nv] (default: the current state):  u = M[A, A] (qacc + kp s e + kv (target_qvel - qvel)) + qfrc_bias
+        on the active dofs A, e the joint error (wrapped into [-pi, pi) on unlimited joints only), s the velocity limit's one scale.
+        ctrl [B, nu]: the row the torques are written into (default zeros); only the motor actuators of the active dofs change.
+        options: kp, kv, vmax, dof_mask (include/jaco_env.h; dof_mask 0: every hinge dof with a motor actuator).  kp = kv = 0 with qacc
+        is inverse dynamics; kp = kv = 0 with nothing else is bias compensation.  One launch on the current stream, no synchronisation;
+        returns the ctrl tensor [B, nu].  The sim's state is not touched: apply the result with send_forces."""
+        B, dev = self.num_envs, self.device
+        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
+        tq, tv, ff = prep(target_qpos, self.nq), prep(target_qvel, self.nv), prep(qacc, self.nv)
+        q, v, cin = prep(qpos, self.nq), prep(qvel, self.nv), prep(ctrl, self.nu)
+        out = torch.empty(B, self.nu, device=dev)
+        opt = _lib.JacoJointOptions(**options)
+        self._chk(self.L.jaco_joint(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
+                                    self._dev(tq, self.nq), self._dev(tv, self.nv), self._dev(ff, self.nv), self._dev(cin, self.nu),
+                                    ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

@@ -242,6 +242,10 @@ class BatchedMujocoConfig:
         """BatchedOSC over this sim: abr_control's OSC(robot_config, kp, ko, kv, vmax); names default to this config's end effector."""
         return BatchedOSC(self, names=(self.ee,) if names is None else names, **gains)
 
+    def joint(self, kp=50.0, kv=20.0, vmax=None, joints=None):
+        """BatchedJoint over this sim: abr_control's Joint(robot_config, kp, kv); joints default to every motor-driven hinge joint."""
+        return BatchedJoint(self, kp=kp, kv=kv, vmax=vmax, joints=joints)
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
@@ -367,3 +371,90 @@ class BatchedOSC:
         import torch
         t = torch.as_tensor(target, dtype=torch.float32, device=self.sim.device).reshape(self.sim.num_envs, len(self.names), 6)
         return self.generate_pose(t[..., :3], quat_from_euler_rxyz(t[..., 3:]), q, dq, ctrl)
+
+
+class BatchedJoint:
+    """abr_control's Joint(robot_config, kp, kv) over a BatchedMujocoConfig: .generate() returns the ctrl rows of every env from ONE
+    launch (jaco_joint): u = M (kp s e + kv (target_velocity - dq)) + qfrc_bias on the controlled joints, e the joint error (wrapped
+    into [-pi, pi) on unlimited joints only -- abr_control wraps every joint; a limited joint is never sent through its limit here), s
+    the one scale of the velocity limit vmax (rad/s; None: no limiting).  joints: MJCF joint names (hinge joints with a motor actuator),
+    in the order the per-joint lists of the methods follow; default: every such joint of the model, in dof order (both arms on the
+    two-arm model).  The quantities are those of a forward pass on the state the call is given.  Joint damping is not compensated."""
+
+    def __init__(self, robot_config, kp=50.0, kv=20.0, vmax=None, joints=None):
+        self.robot_config, self.sim = robot_config, robot_config.sim
+        M, names = robot_config.table.M, robot_config.table.names["joint"]
+        motor = {int(M["jnt_dofadr"][int(j)]) for j, pos in zip(M["actuator_jntid"], M["actuator_position"]) if not pos}
+        if joints is None:
+            ids = sorted((j for j in range(len(names)) if M["jnt_type"][j] == kin.JNT_HINGE and int(M["jnt_dofadr"][j]) in motor),
+                         key=lambda j: int(M["jnt_dofadr"][j]))
+        else:
+            ids = []
+            for n in ([joints] if isinstance(joints, str) else joints):
+                if n is None or n not in names:
+                    raise ValueError("unknown joint %r: the model's joints are %s" % (n, [x for x in names if x]))
+                j = names.index(n)
+                if M["jnt_type"][j] != kin.JNT_HINGE:
+                    raise ValueError("joint %r is not a hinge joint" % n)
+                if int(M["jnt_dofadr"][j]) not in motor:
+                    raise ValueError("joint %r has no motor actuator (a position servo cannot be torque controlled)" % n)
+                if j in ids:
+                    raise ValueError("joint %r is listed twice" % n)
+                ids.append(j)
+        if not ids:
+            raise ValueError("BatchedJoint controls no joint")
+        self.joints = [names[j] for j in ids]
+        self.qadr = [int(M["jnt_qposadr"][j]) for j in ids]
+        self.dadr = [int(M["jnt_dofadr"][j]) for j in ids]
+        self.dof_mask = sum(1 << d for d in self.dadr)
+        self.kp, self.kv, self.vmax = float(kp), float(kv), 0.0 if vmax is None else float(vmax)
+
+    def _rows(self, t, adr, width, base, what):
+        """A full [B, width] row from t: a full row already, or one entry per controlled joint spliced into base() at `adr`."""
+        if t is None:
+            return None
+        import torch
+        B, n = self.sim.num_envs, len(adr)
+        t = torch.as_tensor(t, dtype=torch.float32, device=self.sim.device)
+        if t.dim() == 1 and t.numel() == n:
+            t = t.reshape(1, n).expand(B, n)
+        if t.dim() >= 1 and t.shape[-1] == n and t.numel() == B * n:
+            row = base()
+            row[:, adr] = t.reshape(B, n)
+            return row.contiguous()
+        if t.dim() >= 1 and t.shape[-1] == width and t.numel() == B * width:
+            return t.reshape(B, width).contiguous()
+        raise ValueError("%s has shape %s: one entry per controlled joint ([%d] or [%d, %d]) or full rows ([%d, %d])" % (what, tuple(t.shape), n, B, n, B, width))
+
+    def _call(self, target, target_velocity, qacc, q, dq, ctrl, kp, kv, vmax):
+        import torch
+        state = {}
+
+        def cur(i):
+            if not state:
+                state["s"] = self.sim.get_state()
+            return state["s"][i].clone()
+        zeros = lambda w: (lambda: torch.zeros(self.sim.num_envs, w, dtype=torch.float32, device=self.sim.device))
+        return self.sim.joint(self._rows(target, self.qadr, self.sim.nq, zeros(self.sim.nq), "target"),
+                              self._rows(target_velocity, self.dadr, self.sim.nv, zeros(self.sim.nv), "target_velocity"),
+                              self._rows(qacc, self.dadr, self.sim.nv, zeros(self.sim.nv), "qacc"),
+                              self._rows(q, self.qadr, self.sim.nq, lambda: cur(0), "q"), self._rows(dq, self.dadr, self.sim.nv, lambda: cur(1), "dq"),
+                              ctrl, kp=kp, kv=kv, vmax=vmax, dof_mask=self.dof_mask)
+
+    def generate(self, target, target_velocity=None, q=None, dq=None, ctrl=None):
+        """ctrl [B, nu] for the joint targets `target`: one angle per controlled joint ([n] for every env, or [B, n]) or a full qpos row
+        [B, nq] (a BatchedMujoco.ik result row as it is); target_velocity likewise ([n], [B, n] or [B, nv]; default zeros).  q / dq: the
+        state to compute at, per controlled joint (spliced into the sim's state) or full rows; default: the sim's state.  ctrl: the row
+        to write into (default zeros) -- every word but the controlled motors' is kept.  (abr_control's generate(q, dq, target,
+        target_velocity) with the state last, since it defaults to the sim's.)"""
+        return self._call(target, target_velocity, None, q, dq, ctrl, self.kp, self.kv, self.vmax)
+
+    def inverse_dynamics(self, qacc, q=None, dq=None, ctrl=None):
+        """ctrl [B, nu] holding the torques that give the controlled joints the accelerations qacc ([n], [B, n] or [B, nv]) at the state:
+        M[A, A] qacc + qfrc_bias (the other dofs' accelerations taken as zero)."""
+        return self._call(None, None, qacc, q, dq, ctrl, 0.0, 0.0, 0.0)
+
+    def gravity_compensation(self, q=None, dq=None, ctrl=None):
+        """ctrl [B, nu] holding qfrc_bias on the controlled joints: gravity, Coriolis and centrifugal forces cancelled (abr_control's
+        Floating)."""
+        return self._call(None, None, None, q, dq, ctrl, 0.0, 0.0, 0.0)

@@ -1,0 +1,212 @@
+"""CPU tier: the joint-space controller kernel (mujoco_jaco_amd/csrc/joint.h, jaco_joint) under the wavefront emulator against the
+formula of include/jaco_env.h in fp64 on the fp64 oracle's qM, qfrc_bias and qvel (tests/joint_binding.py holds the emulated call, the
+inputs, the cases and the reference; tests/test_gpu_joint.py is the GPU-tier twin).
+
+Error measure: max over the active dofs of |u - u_ref| / (1 + |u_ref|).  Bounds = 3 x the largest value measured on the emulator:
+  all terms (PD, qacc_ff, target_qvel), default and non-default gains, B = 67 .................... 9.70e-6 -> 2.9e-5
+  targets of unlimited joints shifted by 2 pi k, k in -2 .. 2, and a target across +-pi ........... 4.74e-5 -> 1.4e-4
+    (the shifted fp32 targets are up to 4.8e-7 rad off the exact shift: times kp = 50 that is most of the figure)
+  limited joint 2 at 0.9 rad, target 5.4 rad (plain difference +4.5, wrapped -1.78) ............... 1.80e-6 -> 5.4e-6
+  vmax below / above saturation, and the two unsaturated answers of the scale identity ............ 4.82e-6 -> 1.4e-5
+  inverse dynamics (kp = kv = 0 with qacc_ff) ..................................................... 1.19e-6 -> 3.6e-6
+  dof_mask subsets (one dof, dofs 0-3, dofs 0, 3, 5) .............................................. 6.58e-6 -> 2.0e-5
+  jaco2_dual_torque (12 dofs in one call, then one arm) and jaco2_curtain_torque_old, B = 9 ....... 7.81e-6 / 6.53e-6: inside the first
+  bound, which they share.
+Closed loop (jaco2_reaching_torque, B = 4, 40 x {joint -> one substep} towards a jaco_ik row 5 cm away, kp 100, kv 20, vmax 0.4): the
+reference's joint error shrinks at every one of the last 20 substeps; the emulated loop's final arm qpos is at most 6.87e-7 rad
+from the reference's -> bound 2.1e-6 rad.
+Inputs stay off the knife edges by construction and by assertion on the fp64 side: wrapped differences at least 0.05 rad from +-pi,
+max |e| at most 0.8 or at least 1.25 of the saturation level.
+"""
+import numpy as np
+import pytest
+
+import ik_binding as ib
+import joint_binding as jb
+import osc_binding as ob
+import query_binding as qb
+
+ALL_BOUND = 2.9e-5    # 3 x 9.70e-6 (emulator)
+WRAP_BOUND = 1.4e-4   # 3 x 4.74e-5
+LIM_BOUND = 5.4e-6    # 3 x 1.80e-6
+SAT_BOUND = 1.4e-5    # 3 x 4.82e-6
+ID_BOUND = 3.6e-6     # 3 x 1.19e-6
+MASK_BOUND = 2.0e-5   # 3 x 6.58e-6
+LOOP_BOUND = 2.1e-6   # rad; 3 x 6.87e-7
+
+
+def run(model, q, v, t, tv, ff, cin, **options):
+    return jb.joint(model, q, v, t, tv, ff, cin, **options)
+
+
+def run_alias(model, q, v, t, tv, ff, cin, **options):
+    return jb.joint(model, q, v, t, tv, ff, cin, alias=True, **options)
+
+
+def query_bias(model, q, v):
+    return qb.query(model, q, v, [], want=("qfrc_bias",))["qfrc_bias"]
+
+
+def test_all_terms_match_the_fp64_reference():
+    worst = jb.case_all_terms(run)
+    print("MEASURE all terms: error max %.3g" % worst)
+    assert worst <= ALL_BOUND, worst
+    g = jb.regular_inputs()   # a NULL options pointer = the defaults
+    assert (jb.bits(jb.joint(jb.MODEL, g["q"], g["v"], g["t"], g["tv"], g["ff"], defaults=True)) == jb.bits(run(jb.MODEL, g["q"], g["v"], g["t"], g["tv"], g["ff"], None))).all()
+
+
+def test_unlimited_joints_wrap_and_take_the_short_way():
+    worst = jb.case_wrapping(run)
+    print("MEASURE wrapping: error max %.3g" % worst)
+    assert worst <= WRAP_BOUND, worst
+
+
+def test_a_limited_joint_follows_the_plain_difference():
+    worst = jb.case_limited_joint_is_not_wrapped(run)
+    print("MEASURE limited joint: error max %.3g" % worst)
+    assert worst <= LIM_BOUND, worst
+
+
+def test_velocity_limit_below_and_above_saturation():
+    worst, resid, slack = jb.case_saturation(run)
+    print("MEASURE saturation: error max %.3g" % worst)
+    assert worst <= SAT_BOUND, worst
+    assert (resid <= SAT_BOUND * slack).all()   # the same factor sat / max |e| on every dof
+
+
+def test_inverse_dynamics_and_bias_compensation():
+    worst = jb.case_modes(run, query_bias)
+    print("MEASURE inverse dynamics: error max %.3g" % worst)
+    assert worst <= ID_BOUND, worst
+
+
+def test_masks_pass_through_and_aliasing():
+    worst = jb.case_masks_and_pass_through(run, run_alias)
+    print("MEASURE masks: error max %.3g" % worst)
+    assert worst <= MASK_BOUND, worst
+
+
+def test_two_arms_twelve_dofs_in_one_call():
+    worst = jb.case_two_arms(run)
+    print("MEASURE jaco2_dual_torque: error max %.3g" % worst)
+    assert worst <= ALL_BOUND, worst
+
+
+def test_the_older_curtain_model():
+    worst = jb.case_other_layout(run)
+    print("MEASURE jaco2_curtain_torque_old: error max %.3g" % worst)
+    assert worst <= ALL_BOUND, worst
+
+
+def refused(case):
+    q, v = ob.states(jb.REFUSAL_MODEL, 2)
+    with_target, no_out, opts = jb.refusal_args(case)
+    with pytest.raises(ValueError) as e:
+        jb.joint(jb.REFUSAL_MODEL, q, v, q if with_target else None, no_out=no_out, **opts)
+    return str(e.value)
+
+
+@pytest.mark.parametrize("case", sorted(jb.REFUSALS))
+def test_refusals(case):
+    assert refused(case) == "emu_joint returned -1: jaco_joint: " + jb.REFUSALS[case]
+
+
+def test_an_empty_active_set_is_refused():
+    q, v = ob.states(jb.REFUSAL_MODEL, 2)
+    with pytest.raises(ValueError) as e:
+        jb.joint_on_blob(jb.servo_only_blob(), q, v)
+    assert str(e.value) == "emu_joint returned -1: jaco_joint: " + jb.EMPTY_MESSAGE
+
+
+def test_every_gain_is_checked_and_the_modes_are_legal():
+    q, v = ob.states(jb.MODEL, 1)
+    for k in ("kp", "kv", "vmax"):
+        for bad in (-1.0, float("nan"), float("inf"), -float("inf")):
+            with pytest.raises(ValueError, match="finite and not negative"):
+                jb.joint(jb.MODEL, q, v, q, **{k: bad})
+    assert np.isfinite(jb.joint(jb.MODEL, q, v, kp=0.0)[:, :6]).all()            # no target: legal with kp = 0 (bias + damping)
+    assert np.isfinite(jb.joint(jb.MODEL, q, v, q, kv=0.0, vmax=1.0)[:, :6]).all()   # kv = 0 with vmax: saturation level 0 = no limiting
+
+
+def test_closed_loop_follows_the_fp64_reference():
+    q0, tp = jb.loop_inputs()
+    r = ib.ik(jb.LOOP_MODEL, jb.loop_frame(), q0, tp)
+    assert r["converged"].all()
+    P, _ = ib.oracle_pose(jb.LOOP_MODEL, "EE", np.zeros(3), q0)
+    assert np.allclose(np.linalg.norm(tp - P, axis=1), 0.05, atol=1e-6)
+    row = r["qpos"]
+    qo, errs = jb.closed_loop_oracle(q0, row)
+    assert (np.diff(errs[:, jb.LOOP_STEPS - 20:], axis=1) < 0).all(), errs   # the reference's error shrinks at each of the last 20 substeps
+    qe = jb.closed_loop_emu(q0, row)
+    d = np.abs(qe[:, :6] - qo[:, :6]).max()
+    print("MEASURE loop: joint error %.3g -> %.3g rad in the reference; arm qpos emulator - reference max %.3g rad" % (errs[:, 0].max(), errs[:, -1].max(), d))
+    assert d <= LOOP_BOUND, d
+
+
+def test_batched_joint_mirrors_abr_control_on_the_emulator():
+    """robot_config.BatchedJoint over the emulator stand-in: joint names to mask, per-joint lists against full rows, the three methods."""
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedJoint, BatchedMujocoConfig
+    g = jb.regular_inputs()
+    sim = jb.EmuJointSim(jb.MODEL, g["q"], g["v"])
+    cfg = BatchedMujocoConfig(sim)
+    ctl = cfg.joint()
+    assert isinstance(ctl, BatchedJoint) and ctl.joints == ["joint%d" % i for i in range(6)] and ctl.dof_mask == 0b111111
+    t_full = np.nan_to_num(g["t"], nan=0.0)
+    u = ctl.generate(torch.tensor(t_full), torch.tensor(g["tv"])).numpy()
+    assert sim.calls[-1] == dict(kp=50.0, kv=20.0, vmax=0.0, dof_mask=0b111111)
+    direct = jb.joint(jb.MODEL, g["q"], g["v"], g["t"], g["tv"], None, dof_mask=0b111111)
+    assert (jb.bits(u) == jb.bits(direct)).all()
+    # one angle per controlled joint = the full row; one list for every env is broadcast
+    u_list = ctl.generate(torch.tensor(g["t"][:, :6]), torch.tensor(g["tv"][:, :6])).numpy()
+    assert (jb.bits(u_list) == jb.bits(direct)).all()
+    one = [0.1, 1.5, 2.0, -0.3, 0.4, 0.5]
+    rows = np.zeros_like(g["q"])
+    rows[:, :6] = one
+    assert (jb.bits(ctl.generate(one).numpy()) == jb.bits(jb.joint(jb.MODEL, g["q"], g["v"], rows, dof_mask=0b111111))).all()
+    # a subset by name, in the order given; gains and vmax; q / dq spliced into the sim's state; ctrl passed through
+    sub = cfg.joint(kp=30.0, kv=12.0, vmax=0.5, joints=["joint3", "joint0"])
+    assert sub.dof_mask == 0b001001 and sub.dadr == [3, 0]
+    q2, v2 = ob.states(jb.MODEL, jb.B, seed=9, vseed=10)
+    cin = np.random.default_rng(1).normal(size=(jb.B, 9)).astype(np.float32)
+    u2 = sub.generate(torch.tensor(g["t"][:, [3, 0]]), q=torch.tensor(q2[:, [3, 0]]), dq=torch.tensor(v2[:, [3, 0]]), ctrl=torch.tensor(cin)).numpy()
+    qs, vs = g["q"].copy(), g["v"].copy()
+    qs[:, [3, 0]], vs[:, [3, 0]] = q2[:, [3, 0]], v2[:, [3, 0]]
+    d2 = jb.joint(jb.MODEL, qs, vs, g["t"], None, None, cin, dof_mask=0b001001, **jb.SAT)
+    assert (jb.bits(u2) == jb.bits(d2)).all() and (jb.bits(u2[:, [1, 2, 4, 5, 6, 7, 8]]) == jb.bits(cin[:, [1, 2, 4, 5, 6, 7, 8]])).all()
+    # the two degenerate forms
+    ff = ctl.inverse_dynamics(torch.tensor(g["ff"][:, :6])).numpy()
+    assert sim.calls[-1] == dict(kp=0.0, kv=0.0, vmax=0.0, dof_mask=0b111111)
+    assert (jb.bits(ff) == jb.bits(jb.joint(jb.MODEL, g["q"], g["v"], None, None, g["ff"], kp=0.0, kv=0.0))).all()
+    gc = ctl.gravity_compensation().numpy()
+    assert (gc[:, :6] == query_bias(jb.MODEL, g["q"], g["v"])[:, :6]).all() and (jb.bits(gc[:, 6:]) == 0).all()
+    assert torch.equal(torch.as_tensor(gc[:, :6]), -cfg.g())   # MujocoConfig.g() is -qfrc_bias
+    # the error messages
+    with pytest.raises(ValueError, match="unknown joint 'elbow'"):
+        cfg.joint(joints=["elbow"])
+    with pytest.raises(ValueError, match="'joint_thumb' has no motor actuator"):
+        cfg.joint(joints=["joint0", "joint_thumb"])
+    with pytest.raises(ValueError, match="listed twice"):
+        cfg.joint(joints=["joint0", "joint0"])
+    with pytest.raises(ValueError, match="controls no joint"):
+        cfg.joint(joints=[])
+    with pytest.raises(ValueError, match=r"target has shape \(67, 5\)"):
+        ctl.generate(torch.zeros(jb.B, 5))
+    with pytest.raises(TypeError, match="unknown joint-controller option"):
+        sim.joint(torch.tensor(t_full), ko=1.0)
+
+
+def test_batched_joint_drives_both_arms_by_default():
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
+    model = "jaco2_dual_torque"
+    q, v = ob.states(model, 3)
+    sim = jb.EmuJointSim(model, q, v)
+    ctl = BatchedMujocoConfig(sim, ee="EE_1").joint()
+    assert ctl.joints == ["joint%d_%d" % (i, a) for a in (1, 2) for i in range(6)] and bin(ctl.dof_mask).count("1") == 12
+    t = jb.targets(model, q)
+    u = ctl.generate(torch.tensor(np.nan_to_num(t, nan=0.0))).numpy()
+    r = jb.reference(model, q, v, t)
+    assert jb.error(u[:, jb.motors(model, r["acts"])], r["u"]).max() <= ALL_BOUND
+    arm2 = BatchedMujocoConfig(sim, ee="EE_1").joint(joints=["joint%d_2" % i for i in range(6)])
+    assert arm2.dadr == r["acts"][6:]
