@@ -116,6 +116,16 @@ JDEV void jprof_stamp(JProfCtx& pc, int i, int lane) {
 #define JSTAMP_NEWTON(i) JSTAMP(i)
 #define JSTAMP_NARROW(i)
 #endif
+// -DJACO_REGIME_CENSUS (diagnostic builds only; tools/gpu_regime_census.py, profiles/newton_regime.txt): no stamps; the profile row counts the
+// constrained solves of stage_newton instead -- slot 0 solves with rows, 1 those without a row on the arm/finger block ((rowblocks & 1) == 0),
+// 2 those of slot 1 that also deliver the damped solve (have_qdamped), 3 the rows of slot 1's solves.  The shipped kernel has no counter.
+#ifdef JACO_REGIME_CENSUS
+#undef JSTAMP
+#define JSTAMP(i)
+#define JCENSUS(ne, rowblocks, dual) do { if (lane == 0 && pc.row) { pc.row[0] += 1; if (((rowblocks) & 1) == 0) { pc.row[1] += 1; pc.row[2] += (dual) ? 1 : 0; pc.row[3] += (ne); } } } while (0)
+#else
+#define JCENSUS(ne, rowblocks, dual)
+#endif
 
 // One contact of the contact record (jaco_set_contact_record): = JacoContact of include/jaco_env.h (static_assert in abi_agreement.h), 96 bytes
 struct JacoContactRec {
@@ -1088,36 +1098,56 @@ struct NewtonOut { float qacc, qfrc_con, qdamped; int iters; bool have_qdamped; 
 
 // out[q] = sum_k J[row(q)][k] * v[k] for the lane's NR rows; v distributed one element per lane.
 // NR == 1 keeps the lane's J row in registers (jrow) for the whole solve: no LDS traffic here.
+//
+// Column range.  `free_only` (wave-uniform; stage_newton: no constraint row touches the arm/finger dof block [0, JB0)) drops the columns
+// [0, JB0) from both products: every term there is an exact zero -- J[r][k] is +-0 for k < JB0 on every row (the row builder writes
+// coef = 0 outside both chain masks, and `rowblocks` comes from those masks), M is block diagonal and only lanes of row-carrying blocks
+// keep their M v -- and +0 + (+-0) = +0, so the sum that reaches column JB0 is the +0 it starts from either way.  The head is one
+// branch in front of the tail, not a second copy of it: the surviving terms keep their order (ascending k) and their form.
+// -DJACO_NEWTON_REGIME=0 (A/B and bit-equality builds, tools/build_variant.sh): all columns, J^T f always, as before the regime was used.
+#ifndef JACO_NEWTON_REGIME
+#define JACO_NEWTON_REGIME 1
+#endif
 template <int NR>
-JDEV void rows_dot(const float* J, const float (&jrow)[JNV], float vk, int lane, int ne, int nv, float (&out)[NR]) {
+JDEV void rows_dot(const float* J, const float (&jrow)[JNV], float vk, int lane, int ne, int nv, float (&out)[NR], bool free_only = false) {
   // (the broadcasts first, then the products: a v_readlane straight in front of the VALU that reads its SGPR costs wait states)
-  float vb[JNV];
-#pragma unroll
-  for (int k = 0; k < JNV; k++) vb[k] = wave_bcast(vk, k);
-  if (NR == 1) {
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < JNV; k++) acc += jrow[k] * vb[k];
-    out[0] = acc;
-    return;
-  }
   const float* Jr[NR];
 #pragma unroll
   for (int q = 0; q < NR; q++) { int r = lane + 64 * q; Jr[q] = J + (r < ne ? r : 0) * JLD; out[q] = 0.f; }
+  if (!(JACO_NEWTON_REGIME && free_only)) {
+    float vb[JB0];
 #pragma unroll
-  for (int k = 0; k < JNV; k++) {
+    for (int k = 0; k < JB0; k++) vb[k] = wave_bcast(vk, k);
 #pragma unroll
-    for (int q = 0; q < NR; q++) out[q] += Jr[q][k] * vb[k];
+    for (int k = 0; k < JB0; k++) {
+#pragma unroll
+      for (int q = 0; q < NR; q++) out[q] += (NR == 1 ? jrow[k] : Jr[q][k]) * vb[k];
+    }
+  }
+  float vb[JNV - JB0];
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) vb[k - JB0] = wave_bcast(vk, k);
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) {
+#pragma unroll
+    for (int q = 0; q < NR; q++) out[q] += (NR == 1 ? jrow[k] : Jr[q][k]) * vb[k - JB0];
   }
   (void)nv;
 }
-JDEV float mat_vec(const float (&mrow)[JNV], float vk) {  // (M v)[lane], mrow = M[lane][:] (zero for lanes >= nv)
-  float vb[JNV];
-#pragma unroll
-  for (int k = 0; k < JNV; k++) vb[k] = wave_bcast(vk, k);
+JDEV float mat_vec(const float (&mrow)[JNV], float vk, bool free_only = false) {  // (M v)[lane], mrow = M[lane][:] (zero for lanes >= nv)
   float acc = 0.f;
+  if (!(JACO_NEWTON_REGIME && free_only)) {
+    float vb[JB0];
 #pragma unroll
-  for (int k = 0; k < JNV; k++) acc += mrow[k] * vb[k];
+    for (int k = 0; k < JB0; k++) vb[k] = wave_bcast(vk, k);
+#pragma unroll
+    for (int k = 0; k < JB0; k++) acc += mrow[k] * vb[k];
+  }
+  float vb[JNV - JB0];
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) vb[k - JB0] = wave_bcast(vk, k);
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) acc += mrow[k] * vb[k - JB0];
   return acc;
 }
 // sum_r J[r][lane] * f_r, f distributed over the row slots; 4 rows in flight per step to cover LDS latency
@@ -1153,8 +1183,14 @@ JDEV bool newton_next_round_is_idle(bool any_row_switched, float al, float impro
   const float r = 1.f - al;
   return JACO_NEWTON_LOOKAHEAD && !any_row_switched && r * r * improvement * scale < tol;
 }
+// Who reads NewtonOut::qfrc_con (= J^T f): the Euler stage's damped solve (M + h D) qacc = qfrc_smooth + qfrc_con, which only runs when the
+// model has joint damping and the solver did not already deliver that solve (have_qdamped), and the debug dump of the last substep
+// (`dump`, wave-uniform).  Nobody else: the stages form it only then and leave the 0 they start from otherwise.
+JDEV bool newton_qfrc_wanted(const JacoModelDev* m, const NewtonOut& out, bool dump) {
+  return !JACO_NEWTON_REGIME || dump || (m->has_damping && !out.have_qdamped);
+}
 template <class L>
-JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, float hd, int lane, JProfCtx& pc) {
+JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, float hd, int lane, JProfCtx& pc, bool dump) {
   (void)pc;
   constexpr int NR = L::Caps::NR, MAXEFC = L::Caps::MAXEFC;
   NewtonOut out;
@@ -1185,8 +1221,6 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
     ar[q] = valid[q] ? s.e_aref[r] : 0.f;
     blk[q] = valid[q] ? (s.e_con[r] >> 16) & 7 : 0;
   }
-#pragma unroll
-  for (int k = 0; k < JNV; k++) jrow[k] = (NR == 1 && lane < ne) ? s.J[lane * JLD + k] : 0.f;
   float scale = 1.f / (m->meaninertia * (float)(nv > 1 ? nv : 1));
   float tol = m->tolerance;
   // dof blocks that carry any constraint row; for the others the optimum is exactly M^-1 qfrc_smooth and stays there
@@ -1195,6 +1229,17 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
   for (int q = 0; q < NR; q++) rowblk |= blk[q];
   const int rowblocks = (wave_ballot(rowblk & 1) ? 1 : 0) | (wave_ballot(rowblk & 2) ? 2 : 0) | (wave_ballot(rowblk & 4) ? 4 : 0);
   const bool mine = lane < nv && ((lane < JB0 ? 1 : (lane < JB1 ? 2 : 4)) & rowblocks) != 0;
+  // no row on the arm/finger block: the products below leave its columns out (rows_dot), and the row is loaded over the same range
+  const bool free_only = JACO_NEWTON_REGIME && (rowblocks & 1) == 0;
+#pragma unroll
+  for (int k = 0; k < JNV; k++) jrow[k] = 0.f;
+  if (NR == 1 && !free_only) {
+#pragma unroll
+    for (int k = 0; k < JB0; k++) jrow[k] = lane < ne ? s.J[lane * JLD + k] : 0.f;
+  }
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) jrow[k] = (NR == 1 && lane < ne) ? s.J[lane * JLD + k] : 0.f;
+  JCENSUS(ne, rowblocks, m->has_damping == 1);
   float afree;
   if ((rowblocks & 1) == 0 && m->has_damping == 1) {   // (1: damping on the finger joints only, dofs >= JLDL_NSH)
     // the arm/finger block carries no row: its acceleration is M^-1 qfrc_smooth, and the Euler step's implicitly damped
@@ -1208,14 +1253,14 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
   // Start: warm start on the row-carrying blocks (MuJoCo additionally compares it with the unconstrained point; with
   // an exact line search either start reaches the same optimum), exact solution elsewhere.
   float a = mine ? s.qacc_ws[lane] : afree;
-  float Ma = mat_vec(mrow, a) - smooth;   // from here on "Ma" = gradient of the smooth part, M a - qfrc_smooth
+  float Ma = mat_vec(mrow, a, free_only) - smooth;   // from here on "Ma" = gradient of the smooth part, M a - qfrc_smooth
   Ma = mine ? Ma : 0.f;
-  rows_dot<NR>(s.J, jrow, a, lane, ne, nv, x);
+  rows_dot<NR>(s.J, jrow, a, lane, ne, nv, x, free_only);
 #pragma unroll
   for (int q = 0; q < NR; q++) x[q] = valid[q] ? x[q] - ar[q] : 0.f;
   JSTAMP_NEWTON(11);
 #ifdef JACO_EMULATED
-  if (lane == 0) emu_counter[8]++;   // (CPU tests: constrained solves, and -- below -- the Hessian builds they took)
+  if (lane == 0) { emu_counter[8]++; if ((rowblocks & 1) == 0) emu_counter[11]++; }   // (CPU tests: constrained solves -- 11: those without a row on the arm/finger block -- and, below, the Hessian builds they took)
 #endif
   int it = 0, nls = 0;
   for (; it < m->iterations; it++) {
@@ -1313,10 +1358,10 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
     p = lane < nv ? p : 0.f;
     JSTAMP_NEWTON(13);
     // exact line search on phi(al) = cost(a + al p)
-    float Mp = mat_vec(mrow, p);
+    float Mp = mat_vec(mrow, p, free_only);
     float pMp, pMa;
     wave_sum2(p * Mp, p * Ma, &pMp, &pMa);
-    rows_dot<NR>(s.J, jrow, p, lane, ne, nv, jp);
+    rows_dot<NR>(s.J, jrow, p, lane, ne, nv, jp, free_only);
 #pragma unroll
     for (int q = 0; q < NR; q++) jp[q] = valid[q] ? jp[q] : 0.f;
     float al = 0.f, lo = 0.f, hi = 3.0e38f, d10 = 0.f, dlo = 0.f, dhi = 0.f;
@@ -1370,7 +1415,10 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
 #pragma unroll
   for (int q = 0; q < NR; q++) f[q] = x[q] < 0.f ? -D[q] * x[q] : 0.f;
   out.qacc = a;
-  out.qfrc_con = jt_vec<NR>(s.J, f, ne, lane, nv);
+  if (newton_qfrc_wanted(m, out, dump)) out.qfrc_con = jt_vec<NR>(s.J, f, ne, lane, nv);
+#ifdef JACO_EMULATED
+  if (lane == 0 && newton_qfrc_wanted(m, out, dump)) emu_counter[12]++;   // (CPU tests: solves that formed J^T f; 13, in run_env: damped solves of the Euler stage)
+#endif
   out.iters = it | (nls << 8);
 #pragma unroll
   for (int q = 0; q < NR; q++) if (valid[q]) s.e_f[lane + 64 * q] = f[q];
@@ -1434,7 +1482,7 @@ JDEV void rows_dot_w(L& s, const float (&w)[NR][6], const int (&con)[NR], float 
 
 // The same primal Newton iteration as stage_newton (start point, tolerances, block logic, exact line search), on body-space rows.
 template <class L>
-JDEV NewtonOut stage_newton_w(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, float hd, int lane, JProfCtx& pc) {
+JDEV NewtonOut stage_newton_w(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, float hd, int lane, JProfCtx& pc, bool dump) {
   (void)pc;
   constexpr int NR = L::Caps::NR, MAXEFC = L::Caps::MAXEFC;
   NewtonOut out;
@@ -1633,7 +1681,7 @@ JDEV NewtonOut stage_newton_w(const JacoModelDev* m, L& s, const float (&mrow)[J
     for (int c = 0; c < 6; c++) s.c_frame[ci][3 + c] = F[c];
   }
   wave_sync();
-  {
+  if (newton_qfrc_wanted(m, out, dump)) {   // (the per-contact wrenches above stay: the contact record copies those slots out)
     const WCol own = wcol_load(s, lane, nv);
     float acc = 0.f;
     for (int c = 0; c < ncon; c++) {
@@ -1810,7 +1858,7 @@ JDEV void stage_integrate_pos(const JacoModelDev* m, L& s, int lane) {
 // exact line search as stage_newton; the Hessian is built by a loop over the rows (a handful of rank-1 updates of a 6 x 6 matrix: not
 // worth a matrix-core pass).  Overwrites the block's entries of the main solve's output (there they are the unconstrained solution).
 template <class L>
-JDEV void newton_side(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, int lane, NewtonOut& out) {
+JDEV void newton_side(const JacoModelDev* m, L& s, const float (&mrow)[JNV], float smooth, int lane, NewtonOut& out, bool dump) {
   float* sd = side_buf(s);
   int ns = wave_uniform_i(s.nside);
   ns = ns < 0 ? 0 : (ns > JSIDE_ROWS ? JSIDE_ROWS : ns);
@@ -1888,10 +1936,12 @@ JDEV void newton_side(const JacoModelDev* m, L& s, const float (&mrow)[JNV], flo
   wave_sync();
   if (vr) sd[JSIDE_F + lane] = f;
   wave_sync();
-  float qf = 0.f;
-  for (int r = 0; r < ns; r++) qf += sd[JSIDE_J + r * 6 + kk] * sd[JSIDE_F + r];
   out.qacc = mine ? a : out.qacc;
-  out.qfrc_con = mine ? qf : out.qfrc_con;
+  if (newton_qfrc_wanted(m, out, dump)) {   // (the same rule as the main solve: its lanes and these add up to one vector)
+    float qf = 0.f;
+    for (int r = 0; r < ns; r++) qf += sd[JSIDE_J + r * 6 + kk] * sd[JSIDE_F + r];
+    out.qfrc_con = mine ? qf : out.qfrc_con;
+  }
   if (it > (out.iters & 255)) out.iters = (out.iters & ~255) | (it & 255);
 }
 
@@ -2240,10 +2290,11 @@ again:
     wave_sync();
     const float hdamp = (m->has_damping && lane < nv) ? m->timestep * pf.damping : 0.f;
     NewtonOut nw;
-    if constexpr (C::WRENCH) nw = stage_newton_w(m, s, mrow, smooth, hdamp, lane, pc);
-    else if constexpr (C::CONTACT) nw = stage_newton(m, s, mrow, smooth, hdamp, lane, pc);
+    const bool dump = A.dbg && env == A.dbg_env && sub == nsub - 1;   // (this substep's derived quantities go to the debug dump, below)
+    if constexpr (C::WRENCH) nw = stage_newton_w(m, s, mrow, smooth, hdamp, lane, pc, dump);
+    else if constexpr (C::CONTACT) nw = stage_newton(m, s, mrow, smooth, hdamp, lane, pc, dump);
     else nw = stage_newton_limits(m, s, mrow, smooth, hdamp, lane);
-    if (SideRows<JacoLDS<C>>::on) { if (wave_uniform_i(s.nside) > 0) newton_side(m, s, mrow, smooth, lane, nw); }
+    if (SideRows<JacoLDS<C>>::on) { if (wave_uniform_i(s.nside) > 0) newton_side(m, s, mrow, smooth, lane, nw, dump); }
     JSTAMP(6);
     iters = nw.iters & 255;
     int nls_dbg = nw.iters >> 8;
@@ -2261,10 +2312,13 @@ again:
 #pragma unroll
         for (int j = 0; j < JNV; j++) h[j] = (lane < nv ? mrow[j] : 0.f) + (lane == j ? (lane < nv ? hdamp : 1.f) : 0.f);
         qd = ldl_solve_blocks(h, total, lane, JDAMPED_BLOCKS);
+#ifdef JACO_EMULATED
+        if (lane == 0) emu_counter[13]++;
+#endif
       }
       qacc_e = lane < JB0 ? qd : nw.qacc;
     }
-    if (A.dbg && env == A.dbg_env && sub == nsub - 1) {
+    if (dump) {
       float* D = A.dbg;
       if (lane < m->nbody) {
         for (int k = 0; k < 3; k++) D[JDBG_XPOS + 3 * lane + k] = s.xpos[lane][k];
