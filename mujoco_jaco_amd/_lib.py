@@ -84,6 +84,24 @@ class JacoJointOptions(ctypes.Structure):
         super().__init__(**{**self.DEFAULTS, **options})
 
 
+class JacoFdOptions(ctypes.Structure):
+    """JacoFdOptions of include/jaco_env.h; a fresh instance holds the API defaults (JACO_FD_DEFAULTS)."""
+    _fields_ = [("eps_qpos", ctypes.c_float), ("eps_qvel", ctypes.c_float), ("implicit_damping", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("dof_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(eps_qpos=2.0 ** -8, eps_qvel=2.0 ** -3, implicit_damping=0, dof_mask=0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown forward-dynamics option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
+class JacoFdOut(ctypes.Structure):
+    _fields_ = [("qacc", ctypes.c_void_p), ("qfrc_smooth", ctypes.c_void_p), ("dqacc_dqpos", ctypes.c_void_p), ("dqacc_dqvel", ctypes.c_void_p),
+                ("dqacc_dctrl", ctypes.c_void_p)]
+
+
 def osc_axes(axes, nframes):
     """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
     or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
@@ -173,6 +191,7 @@ SYMBOLS = {
     "jaco_osc": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_osc_task": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_joint": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_fd": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h and joint.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h and fd.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -34,3 +34,7 @@ static_assert(sizeof(JacoJointOptions) == sizeof(JacoJointOpts) && offsetof(Jaco
                   offsetof(JacoJointOptions, kv) == offsetof(JacoJointOpts, kv) && offsetof(JacoJointOptions, vmax) == offsetof(JacoJointOpts, vmax) &&
                   offsetof(JacoJointOptions, dof_mask) == offsetof(JacoJointOpts, dof_mask),
               "JacoJointOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoFdOptions) == sizeof(JacoFdOpts) && offsetof(JacoFdOptions, eps_qpos) == offsetof(JacoFdOpts, eps_qpos) &&
+                  offsetof(JacoFdOptions, eps_qvel) == offsetof(JacoFdOpts, eps_qvel) && offsetof(JacoFdOptions, implicit_damping) == offsetof(JacoFdOpts, implicit_damping) &&
+                  offsetof(JacoFdOptions, dof_mask) == offsetof(JacoFdOpts, dof_mask),
+              "JacoFdOptions of the public header and the kernel's option record must agree");

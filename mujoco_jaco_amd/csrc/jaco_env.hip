@@ -1046,3 +1046,26 @@ extern "C" int jaco_joint(JacoHandle* h, const JacoJointOptions* opt_host, const
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- forward dynamics and its linearisation (fd.h): one wavefront per env, nothing of the handle written ----------------------------
+extern "C" int jaco_fd(JacoHandle* h, const JacoFdOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
+                       const JacoFdOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  const JacoFdOptions defaults = JACO_FD_DEFAULTS;
+  JacoFdOpts opt;
+  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoFdOptions));
+  JacoFdArgs Q{};
+  if (out) { Q.qacc = out->qacc; Q.qfrc_smooth = out->qfrc_smooth; Q.dqacc_dqpos = out->dqacc_dqpos; Q.dqacc_dqvel = out->dqacc_dqvel; Q.dqacc_dctrl = out->dqacc_dctrl; }
+  const std::string why = jaco_fd_resolve(h->model_host, opt, out != nullptr, &Q);
+  if (!why.empty()) { h->err = "jaco_fd: " + why; return JACO_EINVAL; }
+  ENTER(h);
+  Q.model = h->model_dev;
+  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
+  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
+  Q.ctrl = ctrl_dev;
+  Q.nenv = h->num_envs;
+  jaco_launch_fd((unsigned)h->num_envs, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

@@ -147,3 +147,5 @@ void jaco_launch_joint(unsigned grid, hipStream_t st, const JacoJointArgs& Q);
 void jaco_launch_joint(unsigned grid, hipStream_t st, const JacoJointArgs& Q) { hipLaunchKernelGGL(jaco_joint_kernel, dim3(grid), dim3(64), 0, st, Q); }
 #endif
 #endif
+
+#include "fd.h"

@@ -272,6 +272,45 @@ class BatchedMujoco:
                                     ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # ---- forward dynamics and its linearisation (jaco_fd: qacc_smooth of a forward pass and its derivatives per env, one launch)
+    def _fd(self, ctrl, qpos, qvel, want, **options):
+        """One jaco_fd launch: {name: tensor} of the outputs in `want` (names of JacoFdOut), in the C ABI's layout."""
+        B, dev = self.num_envs, self.device
+        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
+        c, q, v = prep(ctrl, self.nu), prep(qpos, self.nq), prep(qvel, self.nv)
+        shapes = {"qacc": (B, self.nv), "qfrc_smooth": (B, self.nv), "dqacc_dqpos": (B, self.nv, self.nv), "dqacc_dqvel": (B, self.nv, self.nv),
+                  "dqacc_dctrl": (B, self.nu, self.nv)}
+        res = {k: torch.empty(shapes[k], device=dev) for k in want}
+        out = _lib.JacoFdOut(*[ctypes.c_void_p(res[k].data_ptr()) if k in res else None for k in shapes])
+        opt = _lib.JacoFdOptions(**options)
+        self._chk(self.L.jaco_fd(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
+                                 self._dev(c, self.nu), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        return res
+
+    def forward_dynamics(self, ctrl=None, qpos=None, qvel=None, implicit_damping=False, want_qfrc=False):
+        """qacc [B, nv]: the acceleration that ctrl [B, nu] (None: zeros) produces at qpos [B, nq] / qvel [B, nv] (default: the current
+        state) -- data.qacc_smooth after a forward pass: M^-1 qfrc_smooth, qfrc_smooth = passive - bias + actuator, the actuators as
+        the step applies them (ctrlrange, the fingers' position servos, forcerange).  UNCONSTRAINED: no contacts, no joint limits.
+        implicit_damping=True: (M + h D)^-1 qfrc_smooth, what a contact-free substep adds to qvel per h.  want_qfrc=True: (qacc,
+        qfrc_smooth).  One launch on the current stream, no synchronisation; the sim's state is not touched."""
+        r = self._fd(ctrl, qpos, qvel, ("qacc", "qfrc_smooth") if want_qfrc else ("qacc",), implicit_damping=int(bool(implicit_damping)))
+        return (r["qacc"], r["qfrc_smooth"]) if want_qfrc else r["qacc"]
+
+    def linearize(self, ctrl=None, qpos=None, qvel=None, dofs=None, eps_qpos=_lib.JacoFdOptions.DEFAULTS["eps_qpos"],
+                  eps_qvel=_lib.JacoFdOptions.DEFAULTS["eps_qvel"], implicit_damping=True):
+        """{"qacc": [B, nv], "dq": [B, nv, nv], "dv": [B, nv, nv], "du": [B, nv, nu]}: forward_dynamics and its Jacobians with respect to
+        the hinge coordinates, the joint velocities and the ctrl (dq[b, i, j] = d qacc_i / d q_j, j a dof index), from ONE launch: central
+        differences of half-width eps_qpos / eps_qvel for dq / dv (the whole chain re-evaluated, the servos included), analytic du
+        (exactly zero for an actuator held by its ctrlrange or forcerange).  dofs: the hinge dofs to differentiate by (default: all of
+        them); the other columns of dq and dv are zero.  The returned Jacobians are transposed views of the kernel's row-per-perturbation
+        arrays."""
+        mask = 0 if dofs is None else sum(1 << int(d) for d in dofs)
+        if dofs is not None and not mask:
+            raise ValueError("linearize: an empty dof list")
+        r = self._fd(ctrl, qpos, qvel, ("qacc", "dqacc_dqpos", "dqacc_dqvel", "dqacc_dctrl"), eps_qpos=eps_qpos, eps_qvel=eps_qvel,
+                     implicit_damping=int(bool(implicit_damping)), dof_mask=mask)
+        return {"qacc": r["qacc"], "dq": r["dqacc_dqpos"].transpose(1, 2), "dv": r["dqacc_dqvel"].transpose(1, 2), "du": r["dqacc_dctrl"].transpose(1, 2)}
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

@@ -246,6 +246,70 @@ class BatchedMujocoConfig:
         """BatchedJoint over this sim: abr_control's Joint(robot_config, kp, kv); joints default to every motor-driven hinge joint."""
         return BatchedJoint(self, kp=kp, kv=kv, vmax=vmax, joints=joints)
 
+    def _spliced(self, q, dq):
+        """(qpos, qvel) rows for the sim: None where the current state is meant, else q / dq [num_envs, n_arm] spliced into it."""
+        if q is None and dq is None:
+            return None, None
+        import torch
+        qpos, qvel, _ = self.sim.get_state()
+        if q is not None:
+            qpos[:, self.arm_qadr] = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], self.n_arm)
+        if dq is not None:
+            qvel[:, self.arm] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], self.n_arm)
+        return qpos.contiguous(), qvel.contiguous()
+
+    def forward_dynamics(self, ctrl=None, q=None, dq=None, implicit_damping=False, full=False):
+        """[num_envs, n_arm] joint accelerations that ctrl [num_envs, nu] (None: zeros) produces (full=True: all nv dofs): mj_forward's
+        qacc_smooth, contact-free (BatchedMujoco.forward_dynamics).  q / dq: arm angles / velocities spliced into the current state."""
+        qpos, qvel = self._spliced(q, dq)
+        return self._cols(self.sim.forward_dynamics(ctrl, qpos, qvel, implicit_damping=implicit_damping), full)
+
+    def linearize(self, joints=None, ctrl=None, q=None, dq=None, **steps):
+        """(A [num_envs, 2 n, 2 n], B [num_envs, 2 n, m], c [num_envs, 2 n]) of the discrete contact-free transition of one substep on
+        the hinge joints `joints` (MJCF names; default: this config's arm), around the current state (or q / dq spliced into it) and
+        ctrl [num_envs, nu] (None: zeros):  x' ~ A x + B u + c  with the state x = [q_J, dq_J], u the ctrl words of the motor actuators
+        of those joints (in the joints' order; B.shape[-1] of them), and the integrator's order: dq' = dq + h qacc, q' = q + h dq'
+        (h the model's timestep, qacc with the implicit joint damping of the step).  The other dofs and ctrl words are held at their
+        values.  One jaco_fd launch (BatchedMujoco.linearize) plus the assembly in torch; steps: eps_qpos, eps_qvel."""
+        import torch
+        M, names = self.table.M, self.table.names["joint"]
+        if joints is None:
+            dofs, qadr = list(self.arm), list(self.arm_qadr)
+        else:
+            dofs, qadr = [], []
+            for n in ([joints] if isinstance(joints, str) else joints):
+                if n is None or n not in names:
+                    raise ValueError("unknown joint %r: the model's joints are %s" % (n, [x for x in names if x]))
+                j = names.index(n)
+                if M["jnt_type"][j] != kin.JNT_HINGE:
+                    raise ValueError("joint %r is not a hinge joint" % n)
+                if int(M["jnt_dofadr"][j]) in dofs:
+                    raise ValueError("joint %r is listed twice" % n)
+                dofs.append(int(M["jnt_dofadr"][j])); qadr.append(int(M["jnt_qposadr"][j]))
+        if not dofs:
+            raise ValueError("linearize: no joint chosen")
+        motor = {int(M["jnt_dofadr"][int(j)]): a for a, (j, pos) in enumerate(zip(M["actuator_jntid"], M["actuator_position"])) if not pos}
+        acts = [motor[d] for d in dofs if d in motor]
+        h = float(M["opt_timestep"][0])
+        qpos, qvel = self._spliced(q, dq)
+        r = self.sim.linearize(ctrl, qpos, qvel, dofs=dofs, implicit_damping=True, **steps)
+        if qpos is None:
+            qpos, qvel, _ = self.sim.get_state()
+        n, B = len(dofs), qpos.shape[0]
+        a = r["qacc"][:, dofs]
+        Aq, Av, Bu = r["dq"][:, dofs][:, :, dofs], r["dv"][:, dofs][:, :, dofs], r["du"][:, dofs][:, :, acts]
+        I = torch.eye(n, dtype=a.dtype, device=a.device).expand(B, n, n)
+        Fv = I + h * Av                      # d dq' / d dq
+        A = torch.cat([torch.cat([I + h * h * Aq, h * Fv], 2), torch.cat([h * Aq, Fv], 2)], 1)
+        Bm = torch.cat([h * h * Bu, h * Bu], 1)
+        x = torch.cat([qpos[:, qadr], qvel[:, dofs]], 1)
+        u = torch.zeros(B, len(acts), dtype=a.dtype, device=a.device) if ctrl is None else \
+            torch.as_tensor(ctrl, dtype=a.dtype, device=a.device).reshape(B, -1)[:, acts]
+        v1 = x[:, n:] + h * a
+        x1 = torch.cat([x[:, :n] + h * v1, v1], 1)
+        c = x1 - (A @ x[:, :, None])[:, :, 0] - (Bm @ u[:, :, None])[:, :, 0]
+        return A, Bm, c
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)

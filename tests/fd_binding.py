@@ -1,0 +1,463 @@
+"""The forward-dynamics kernel (mujoco_jaco_amd/csrc/fd.h, jaco_fd) under the wavefront emulator (emu_fd of
+tests/emu_fd/libjaco_emu_fd{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+
+Also: the fp64 references -- the oracle's qacc_smooth / qfrc_smooth after forward() at the fp32-rounded inputs, (qM + h diag(damping))^-1
+qfrc_smooth from the oracle's quantities for implicit_damping = 1, central differences of the oracle's acceleration with eps 1e-6 for
+the state derivatives, the columns of the fp64 inverse times the actuator's gate for dqacc_dctrl --, the input sets (kept off the
+actuator model's knife edges, asserted on the fp64 side), the cases shared by the CPU and the GPU tier, the refusals and a stand-in
+for BatchedMujoco.forward_dynamics / linearize backed by the emulator (CPU tests of robot_config).
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import emu_binding
+import ik_binding as ib
+import osc_binding as ob
+import query_binding as qb
+from emu_binding import ROOT
+from mujoco_jaco_amd import _lib as product_lib
+
+EMU_DIR = os.path.join(ROOT, "tests", "emu_fd")
+DEFAULTS = dict(product_lib.JacoFdOptions.DEFAULTS)
+OUTS = ("qacc", "qfrc_smooth", "dqacc_dqpos", "dqacc_dqvel", "dqacc_dctrl")
+REF_EPS = 1e-6          # the fp64 central differences of the reference
+CTRL_MARGIN = 0.05      # a limited ctrl is at least this far inside or outside its ctrlrange
+_libs = {}
+
+
+def lib(layout=""):
+    """libjaco_emu_fd<layout>.so: the emulator library of that layout with the emu_fd entry (built on first use)."""
+    if layout not in _libs:
+        name = "libjaco_emu_fd%s.so" % layout
+        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
+        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.emu_fd.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, fp, fp, fp, ctypes.c_void_p]
+        L.emu_last_error.restype = ctypes.c_char_p
+        _libs[layout] = L
+    return _libs[layout]
+
+
+def fd(model, qpos, qvel, ctrl=None, want=OUTS, defaults=False, no_out=False, **options):
+    """Emulated jaco_fd: {output: array} in the C ABI's layout (dqacc_dqpos / dqacc_dqvel [B, nv, nv] and dqacc_dctrl [B, nu, nv]: one row
+    per perturbation) for fp32 states qpos [B, nq] / qvel [B, nv] and ctrl [B, nu] (None: NULL).  want: the outputs handed in (the others
+    NULL).  defaults=True hands a NULL options pointer, no_out=True a NULL output record.  Raises ValueError with the library's message
+    when the call is refused."""
+    blob, layout, nu = ob._model_info(model)
+    L = lib(layout)
+    qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
+    B, nv = qpos.shape[0], qvel.shape[1]
+    c = None if ctrl is None else np.ascontiguousarray(ctrl, np.float32).reshape(B, nu)
+    fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    shapes = {"qacc": (B, nv), "qfrc_smooth": (B, nv), "dqacc_dqpos": (B, nv, nv), "dqacc_dqvel": (B, nv, nv), "dqacc_dctrl": (B, nu, nv)}
+    res = {k: np.full(shapes[k], np.nan, np.float32) for k in want}
+    out = product_lib.JacoFdOut(*[res[k].ctypes.data_as(ctypes.c_void_p) if k in res else None for k in OUTS])
+    opt = product_lib.JacoFdOptions(**options)
+    rc = L.emu_fd(blob, len(blob), B, None if defaults else ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), fp(qpos), fp(qvel), fp(c),
+                  None if no_out else ctypes.cast(ctypes.pointer(out), ctypes.c_void_p))
+    emu_binding.check(L, rc, "emu_fd")
+    return res
+
+
+# ---- the model as the kernel sees it
+def tables(model):
+    """Actuator and dof tables of the model (fp64): dof / qpos address / servo flag / kp / ctrl and force limits per actuator, the hinge
+    dofs, the joint damping per dof, the timestep, the gravity."""
+    M = ib.load_model(model)
+    j = np.asarray(M["actuator_jntid"], int)
+    hinge = [int(M["jnt_dofadr"][k]) for k in range(int(M["njnt"][0])) if int(M["jnt_type"][k]) == 3]
+    qadr = {int(M["jnt_dofadr"][k]): int(M["jnt_qposadr"][k]) for k in range(int(M["njnt"][0])) if int(M["jnt_type"][k]) == 3}
+    free = [int(M["jnt_dofadr"][k]) for k in range(int(M["njnt"][0])) if int(M["jnt_type"][k]) == 0]
+    return dict(dof=np.asarray(M["jnt_dofadr"], int)[j], qadr=np.asarray(M["jnt_qposadr"], int)[j], position=np.asarray(M["actuator_position"], bool),
+                kp=np.asarray(M["actuator_kp"], float), ctrllimited=np.asarray(M["actuator_ctrllimited"], bool),
+                ctrlrange=np.asarray(M["actuator_ctrlrange"], float).reshape(-1, 2), forcelimited=np.asarray(M["actuator_forcelimited"], bool),
+                forcerange=np.asarray(M["actuator_forcerange"], float).reshape(-1, 2), hinge=hinge, hinge_qadr=qadr, free=free,
+                damping=np.asarray(M["dof_damping"], float), h=float(M["opt_timestep"][0]), gravity=np.asarray(M["opt_gravity"], float))
+
+
+def actuator_state(model, qpos, ctrl):
+    """fp64, per env and actuator: (the force before forcerange, the gate g_a of dqacc_dctrl, the distance of a limited ctrl to the
+    nearer end of its ctrlrange (inf: not limited), the distance of the unclamped force to the nearer forcerange end)."""
+    T = tables(model)
+    q, c = np.asarray(qpos, np.float64), np.asarray(ctrl, np.float64)
+    lo, hi = T["ctrlrange"][:, 0], T["ctrlrange"][:, 1]
+    inside = ~T["ctrllimited"] | ((c >= lo) & (c <= hi))
+    cdist = np.where(T["ctrllimited"], np.minimum(np.abs(c - lo), np.abs(c - hi)), np.inf)
+    cc = np.where(T["ctrllimited"], np.clip(c, lo, hi), c)
+    f = np.where(T["position"], T["kp"] * (cc - q[:, T["qadr"]]), cc)
+    fdist = np.where(T["forcelimited"], np.minimum(np.abs(f - T["forcerange"][:, 0]), np.abs(f - T["forcerange"][:, 1])), np.inf)
+    unsat = ~T["forcelimited"] | ((f > T["forcerange"][:, 0]) & (f < T["forcerange"][:, 1]))
+    gate = np.where(inside & unsat, np.where(T["position"], T["kp"], 1.0), 0.0)
+    return f, gate, cdist, fdist
+
+
+def off_the_knife_edges(model, qpos, ctrl, eps_qpos=DEFAULTS["eps_qpos"]):
+    """Every limited ctrl at least CTRL_MARGIN inside or outside its ctrlrange; every servo force further from a forcerange end than
+    1.25 kp eps_qpos (no difference straddles a clamp), every motor force further than 0.05."""
+    T = tables(model)
+    _, _, cdist, fdist = actuator_state(model, qpos, ctrl)
+    need = np.where(T["position"], 1.25 * T["kp"] * eps_qpos, 0.05)
+    return bool((cdist >= CTRL_MARGIN).all() and (fdist > need).all())
+
+
+# ---- the fp64 references
+def _acc(o, T, implicit):
+    """(acceleration, qfrc_smooth, qM) of the oracle's current forward pass."""
+    qs = o.get("qfrc_smooth")
+    qM = o.get("qM").reshape(o.nv, o.nv)
+    if not implicit:
+        return o.get("qacc_smooth"), qs, qM
+    return np.linalg.solve(qM + T["h"] * np.diag(T["damping"]), qs), qs, qM
+
+
+def reference(model, qpos, qvel, ctrl=None, implicit=False, derivs=False, dofs=None):
+    """fp64 at the fp32 inputs: {"qacc", "qfrc_smooth" [B, nv]} and, with derivs, {"dqacc_dqpos", "dqacc_dqvel" [B, nv, nv],
+    "dqacc_dctrl" [B, nu, nv]} in the C ABI's layout (row = perturbation; rows outside `dofs` (default: every hinge dof) zero)."""
+    from oracle_binding import Oracle
+    o, T = Oracle(model), tables(model)
+    B, nv, nu = qpos.shape[0], o.nv, o.nu
+    ctrl = np.zeros((B, nu), np.float32) if ctrl is None else ctrl
+    out = dict(qacc=np.zeros((B, nv)), qfrc_smooth=np.zeros((B, nv)))
+    if derivs:
+        out.update(dqacc_dqpos=np.zeros((B, nv, nv)), dqacc_dqvel=np.zeros((B, nv, nv)), dqacc_dctrl=np.zeros((B, nu, nv)))
+        gate = actuator_state(model, qpos, ctrl)[1]
+    sel = T["hinge"] if dofs is None else list(dofs)
+    for k in range(B):
+        q, v = qpos[k].astype(np.float64), qvel[k].astype(np.float64)
+        o.set("ctrl", ctrl[k].astype(np.float64))
+
+        def at(q_, v_):
+            o.set("qpos", q_); o.set("qvel", v_)
+            o.forward()
+            return _acc(o, T, implicit)
+        out["qacc"][k], out["qfrc_smooth"][k], qM = at(q, v)
+        if not derivs:
+            continue
+        Minv = np.linalg.inv(qM + (T["h"] * np.diag(T["damping"]) if implicit else 0.0))
+        for a in range(nu):
+            out["dqacc_dctrl"][k, a] = gate[k, a] * Minv[:, T["dof"][a]]
+        for c in sel:
+            for name, which in (("dqacc_dqpos", 0), ("dqacc_dqvel", 1)):
+                hi, lo = [q.copy(), v.copy()], [q.copy(), v.copy()]
+                i = T["hinge_qadr"][c] if which == 0 else c
+                hi[which][i] += REF_EPS; lo[which][i] -= REF_EPS
+                out[name][k, c] = (at(*hi)[0] - at(*lo)[0]) / (2 * REF_EPS)
+    return out
+
+
+def verr(x, ref):
+    """Vectors: max |x - ref| / (1 + |ref|)."""
+    x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
+    return float((np.abs(x - ref) / (1.0 + np.abs(ref))).max())
+
+
+def merr(x, ref):
+    """Matrices [B, r, c]: the largest element error of an env divided by (1 + that env's largest |ref| element), max over the envs."""
+    x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
+    B = ref.shape[0]
+    return float((np.abs(x - ref).reshape(B, -1).max(1) / (1.0 + np.abs(ref).reshape(B, -1).max(1))).max())
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---- inputs
+def inputs(model, B, seed=21, servo="mixed", states=None):
+    """(qpos, qvel, ctrl) fp32: the picking reset states with qvel uniform in +-0.5 (osc_binding.states) or `states`, the servo-driven
+    (finger) joints moved to uniform 0.2 .. 1.2 rad (ctrlrange 0 .. 1.51: room for a command on either side); motor commands uniform in
+    +-5 (force ranges +-15 / +-30); servo commands = the finger angle + delta with kp delta = +-(0.02 .. 0.16): inside the force range
+    +-0.3 by more than 1.25 kp eps_qpos.  servo="saturated": kp |delta| = 0.5 .. 1 instead (the force range clamps)."""
+    q, v = ob.states(model, B) if states is None else states
+    q = q.copy()
+    T = tables(model)
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-5, 5, (B, len(T["dof"])))
+    for a in np.flatnonzero(T["position"]):
+        q[:, T["qadr"][a]] = rng.uniform(0.2, 1.2, B)
+        f = rng.uniform(0.02, 0.16, B) if servo == "mixed" else rng.uniform(0.5, 1.0, B)
+        c[:, a] = q[:, T["qadr"][a]].astype(np.float64) + rng.choice([-1.0, 1.0], B) * f / T["kp"][a]
+    return q, v, c.astype(np.float32)
+
+
+# ---- the cases, shared by the CPU tier (run = the emulated call) and the GPU tier (run = jaco_fd through the C ABI on device tensors):
+# run(model, qpos, qvel, ctrl, want=OUTS, defaults=False, **options) -> {output: array}.  Each returns what it measured; the caller prints
+# it and holds it to its bound.
+MODEL, B = "jaco2_curtain_torque", 67
+SMALL = ("jaco2_dual_torque", "jaco2_curtain_torque_old", "jaco2_reaching_torque")
+SMALL_B = 9
+_shared = {}
+
+
+def shared(model):
+    """The regular inputs of a model and their fp64 references (both implicit_damping values; the derivatives of the default
+    linearisation: implicit_damping = 1), computed once per process."""
+    if model not in _shared:
+        n = B if model == MODEL else SMALL_B
+        q, v, c = inputs(model, n)
+        assert off_the_knife_edges(model, q, c)
+        _shared[model] = dict(q=q, v=v, c=c, ref0=reference(model, q, v, c), ref1=None, lin=None)
+    return _shared[model]
+
+
+def ref_implicit(model):
+    g = shared(model)
+    if g["ref1"] is None:
+        g["ref1"] = reference(model, g["q"], g["v"], g["c"], implicit=True)
+    return g["ref1"]
+
+
+LIN_B = {MODEL: B}    # envs of the derivative cases (the default model's full linearisation is 37 forward passes per env)
+
+
+def ref_linear(model):
+    g = shared(model)
+    if g["lin"] is None:
+        n = LIN_B.get(model, SMALL_B)
+        g["lin"] = reference(model, g["q"][:n], g["v"][:n], g["c"][:n], implicit=True, derivs=True)
+    return g["lin"]
+
+
+def case_values(run, model):
+    """Case 1: qacc and qfrc_smooth, both implicit_damping values; ctrl NULL = a zero ctrl and a NULL options pointer = the defaults,
+    bit for bit.  Returns (qacc error, qfrc_smooth error, qacc error with implicit damping)."""
+    g = shared(model)
+    r0 = run(model, g["q"], g["v"], g["c"], want=("qacc", "qfrc_smooth"))
+    r1 = run(model, g["q"], g["v"], g["c"], want=("qacc", "qfrc_smooth"), implicit_damping=1)
+    assert (bits(r0["qfrc_smooth"]) == bits(r1["qfrc_smooth"])).all()
+    T = tables(model)
+    damped = T["damping"] > 0
+    assert np.abs(ref_implicit(model)["qacc"][:, damped] - g["ref0"]["qacc"][:, damped]).max() > 1.0   # (the damping matters)
+    z = run(model, g["q"], g["v"], None, want=("qacc", "qfrc_smooth"))
+    z0 = run(model, g["q"], g["v"], np.zeros_like(g["c"]), want=("qacc", "qfrc_smooth"))
+    d = run(model, g["q"], g["v"], g["c"], want=("qacc", "qfrc_smooth"), defaults=True)
+    for k in ("qacc", "qfrc_smooth"):
+        assert (bits(z[k]) == bits(z0[k])).all() and (bits(d[k]) == bits(r0[k])).all(), k
+    return verr(r0["qacc"], g["ref0"]["qacc"]), verr(r0["qfrc_smooth"], g["ref0"]["qfrc_smooth"]), verr(r1["qacc"], ref_implicit(model)["qacc"])
+
+
+def case_actuator_model(run, model=MODEL, n=SMALL_B):
+    """Case 2: servo ctrl beyond the ctrlrange, servos driven into the forcerange, motor ctrl beyond the forcerange: values against the
+    reference, the held actuators' dqacc_dctrl rows exactly 0.0, the others' against the reference.  Returns (qacc error, qfrc_smooth
+    error, dqacc_dctrl measure)."""
+    T = tables(model)
+    q, v, c = inputs(model, n, seed=23, servo="saturated")
+    servos, motors = np.flatnonzero(T["position"]), np.flatnonzero(~T["position"])
+    c[: n // 3, servos[0]] = T["ctrlrange"][servos[0], 1] + 0.3     # beyond the ctrlrange (and, clamped, saturated or not as it falls)
+    c[n // 3: 2 * (n // 3), servos[-1]] = T["ctrlrange"][servos[-1], 0] - 0.3
+    c[::2, motors[0]] = T["forcerange"][motors[0], 1] + 4.0        # motors beyond their forcerange
+    c[1::2, motors[-1]] = T["forcerange"][motors[-1], 0] - 4.0
+    assert off_the_knife_edges(model, q, c)
+    ref = reference(model, q, v, c, derivs=False)
+    _, gate, _, _ = actuator_state(model, q, c)
+    assert (gate[:, servos] == 0).all() and (gate[::2, motors[0]] == 0).all() and (gate[:, motors[1]] == 1).all()
+    r = run(model, q, v, c, want=("qacc", "qfrc_smooth", "dqacc_dctrl"))
+    assert (bits(r["dqacc_dctrl"])[gate == 0] == 0).all()   # exactly +0.0
+    from oracle_binding import Oracle
+    o = Oracle(model)
+    du = np.zeros(r["dqacc_dctrl"].shape)
+    for k in range(n):
+        o.set("qpos", q[k].astype(np.float64)); o.set("qvel", v[k].astype(np.float64)); o.forward()
+        Minv = np.linalg.inv(o.get("qM").reshape(o.nv, o.nv))
+        for a in range(o.nu):
+            du[k, a] = gate[k, a] * Minv[:, T["dof"][a]]
+    return verr(r["qacc"], ref["qacc"]), verr(r["qfrc_smooth"], ref["qfrc_smooth"]), merr(r["dqacc_dctrl"], du)
+
+
+def case_free_body_at_rest(run, model=MODEL, n=SMALL_B):
+    """Case 3: the free bodies at rest in the air (the picking states spawn the object inside its holder: contacts do not enter):
+    translational accelerations = the model's gravity, rotational ones 0.  Returns the vector measure over the free dofs."""
+    T = tables(model)
+    q, v, c = inputs(model, n, seed=25)
+    v[:, T["free"][0]:] = 0.0
+    ref = np.zeros((n, v.shape[1]))
+    for d0 in T["free"]:
+        ref[:, d0:d0 + 3] = T["gravity"]
+    r = run(model, q, v, c, want=("qacc",))
+    fr = [d for d0 in T["free"] for d in range(d0, d0 + 6)]
+    return verr(r["qacc"][:, fr], ref[:, fr])
+
+
+def case_linearisation(run, model):
+    """Case 4: the three derivative outputs with the default mask and steps (implicit_damping = 1), and dqacc_dqvel at eps 0.125 against
+    eps 0.5.  Returns (dqacc_dqpos, dqacc_dqvel, dqacc_dctrl measures, the measure of dqvel(0.125) against dqvel(0.5))."""
+    g, n = shared(model), LIN_B.get(model, SMALL_B)
+    ref = ref_linear(model)
+    T = tables(model)
+    r = run(model, g["q"][:n], g["v"][:n], g["c"][:n], implicit_damping=1)
+    rest = [d for d in range(g["v"].shape[1]) if d not in T["hinge"]]
+    assert (bits(r["dqacc_dqpos"][:, rest]) == 0).all() and (bits(r["dqacc_dqvel"][:, rest]) == 0).all()   # free-joint dofs: zero rows
+    wide = run(model, g["q"][:n], g["v"][:n], g["c"][:n], want=("dqacc_dqvel",), implicit_damping=1, eps_qvel=0.5)
+    return (merr(r["dqacc_dqpos"], ref["dqacc_dqpos"]), merr(r["dqacc_dqvel"], ref["dqacc_dqvel"]), merr(r["dqacc_dctrl"], ref["dqacc_dctrl"]),
+            merr(r["dqacc_dqvel"], wide["dqacc_dqvel"]))
+
+
+MASKS = (0b000100, 0b001111, 0b101001)   # one dof, dofs 0-3, a non-contiguous set
+SUB_B = 5
+
+
+def case_masks(run, model=MODEL):
+    """Case 5: dof_mask subsets: unselected rows exactly zero, selected rows bit-identical to the full-mask call."""
+    g = shared(model)
+    a = (g["q"][:SUB_B], g["v"][:SUB_B], g["c"][:SUB_B])
+    full = run(model, *a, want=("dqacc_dqpos", "dqacc_dqvel"))
+    for mask in MASKS:
+        r = run(model, *a, want=("dqacc_dqpos", "dqacc_dqvel"), dof_mask=mask)
+        on = [d for d in range(a[1].shape[1]) if (mask >> d) & 1]
+        off = [d for d in range(a[1].shape[1]) if not (mask >> d) & 1]
+        for k in ("dqacc_dqpos", "dqacc_dqvel"):
+            assert (bits(r[k][:, off]) == 0).all() and (bits(r[k][:, on]) == bits(full[k][:, on])).all(), (mask, k)
+            assert np.abs(full[k][:, on]).max() > 0
+
+
+def case_output_subsets(run, model=MODEL):
+    """Case 6: each output pointer alone gives the bits of the all-outputs call."""
+    g = shared(model)
+    a = (g["q"][:SUB_B], g["v"][:SUB_B], g["c"][:SUB_B])
+    full = run(model, *a, dof_mask=MASKS[2])
+    for k in OUTS:
+        r = run(model, *a, want=(k,), dof_mask=MASKS[2])
+        assert set(r) == {k} and (bits(r[k]) == bits(full[k])).all(), k
+
+
+# ---- case 7: against the stepper
+STEP_MODEL, STEP_B = "jaco2_reaching_torque", 32
+
+
+def stepper_inputs():
+    """(qpos, qvel, ctrl) of STEP_MODEL: arm angles qpos0 +- 0.5 rad (query_binding.hold_states: mid-range), qvel uniform in +-0.5."""
+    q = qb.hold_states(STEP_B, seed=41)
+    v = np.random.default_rng(42).uniform(-0.5, 0.5, q.shape).astype(np.float32)
+    return inputs(STEP_MODEL, STEP_B, seed=43, states=(q, v))
+
+
+def oracle_substep(model, qpos, qvel, ctrl, disable_contact=False):
+    """fp64: (qvel after one substep [B, nv], qpos after it [B, nq], nefc of that substep [B]) from the fp32-rounded inputs."""
+    from oracle_binding import Oracle
+    o = Oracle(model)
+    if disable_contact:
+        o.option("disable_contact", 1)
+    n = qpos.shape[0]
+    v1, q1, nefc = np.zeros((n, o.nv)), np.zeros((n, o.nq)), np.zeros(n, int)
+    for k in range(n):
+        o.set("qpos", np.asarray(qpos[k], np.float64)); o.set("qvel", np.asarray(qvel[k], np.float64)); o.set("qacc_warmstart", np.zeros(o.nv))
+        o.step(np.asarray(ctrl[k], np.float64))
+        v1[k], q1[k], nefc[k] = o.get("qvel"), o.get("qpos"), o.nefc
+    return v1, q1, nefc
+
+
+def case_stepper(run):
+    """qvel + h qacc (implicit_damping = 1) against one oracle substep, on the envs the oracle reports with nefc == 0 (at least 90 %).
+    Returns (the vector measure, the inputs, the qualifying envs)."""
+    q, v, c = stepper_inputs()
+    assert off_the_knife_edges(STEP_MODEL, q, c)
+    v1, _, nefc = oracle_substep(STEP_MODEL, q, v, c)
+    ok = nefc == 0
+    assert ok.mean() >= 0.9, ok.mean()
+    r = run(STEP_MODEL, q, v, c, want=("qacc",), implicit_damping=1)
+    pred = v.astype(np.float64) + tables(STEP_MODEL)["h"] * r["qacc"]
+    return verr(pred[ok], v1[ok]), (q, v, c), ok
+
+
+# ---- case 8: robot_config.linearize / forward_dynamics.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or EmuFdSim.
+LIN_STEP = 1e-3
+
+
+def case_config_linearize(make_sim):
+    """A x + B u + c of BatchedMujocoConfig.linearize on the arm-only model, at points LIN_STEP away (state and ctrl, uniform in
+    +-LIN_STEP per entry) against the oracle's substep from there.  Returns the vector measure over [q', dq'] of the arm."""
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
+    q, v, c = stepper_inputs()
+    sim = make_sim(STEP_MODEL, q, v)
+    cfg = BatchedMujocoConfig(sim)
+    A, Bm, cc = [t.cpu().numpy().astype(np.float64) for t in cfg.linearize(ctrl=torch.as_tensor(c, device=sim.device))]
+    n = 6
+    assert A.shape == (STEP_B, 2 * n, 2 * n) and Bm.shape == (STEP_B, 2 * n, n) and cc.shape == (STEP_B, 2 * n)
+    rng = np.random.default_rng(44)
+    x2 = (np.concatenate([q[:, :n], v[:, :n]], 1).astype(np.float64) + rng.uniform(-LIN_STEP, LIN_STEP, (STEP_B, 2 * n))).astype(np.float32)
+    u2 = (c[:, :n].astype(np.float64) + rng.uniform(-LIN_STEP, LIN_STEP, (STEP_B, n))).astype(np.float32)
+    pred = (A @ x2.astype(np.float64)[:, :, None])[:, :, 0] + (Bm @ u2.astype(np.float64)[:, :, None])[:, :, 0] + cc
+    q2, v2, c2 = q.copy(), v.copy(), c.copy()
+    q2[:, :n], v2[:, :n], c2[:, :n] = x2[:, :n], x2[:, n:], u2
+    assert off_the_knife_edges(STEP_MODEL, q2, c2)
+    v1, q1, nefc = oracle_substep(STEP_MODEL, q2, v2, c2)
+    ok = nefc == 0
+    assert ok.mean() >= 0.9
+    return verr(pred[ok], np.concatenate([q1[:, :n], v1[:, :n]], 1)[ok])
+
+
+def case_config_two_arms(make_sim):
+    """n_robots = 2: BatchedMujocoConfig(ee="EE_1").forward_dynamics on jaco2_dual_torque: dq + h qacc of that arm's joints against the
+    oracle's contact-free substep (envs with nefc == 0); linearize there has the shapes of one arm and reproduces that prediction at
+    its own point.  Returns (the vector measure of the prediction, the largest residual of A x + B u + c at the point)."""
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
+    model = "jaco2_dual_torque"
+    g, T = shared(model), tables(model)
+    sim = make_sim(model, g["q"], g["v"])
+    cfg = BatchedMujocoConfig(sim, ee="EE_1")
+    ctrl = torch.as_tensor(g["c"], device=sim.device)
+    arm, qadr = list(cfg.arm), list(cfg.arm_qadr)
+    assert len(arm) == 6
+    a = cfg.forward_dynamics(ctrl, implicit_damping=True).cpu().numpy().astype(np.float64)
+    pred = g["v"][:, arm].astype(np.float64) + T["h"] * a
+    v1, _, nefc = oracle_substep(model, g["q"], g["v"], g["c"], disable_contact=True)
+    ok = nefc == 0
+    assert ok.sum() >= 5, nefc
+    A, Bm, cc = [t.cpu().numpy().astype(np.float64) for t in cfg.linearize(joints=["joint%d_1" % i for i in range(6)], ctrl=ctrl)]
+    assert A.shape == (SMALL_B, 12, 12) and Bm.shape == (SMALL_B, 12, 6) and cc.shape == (SMALL_B, 12)
+    x = np.concatenate([g["q"][:, qadr], g["v"][:, arm]], 1).astype(np.float64)
+    u = g["c"][:, [int(np.flatnonzero(T["dof"] == d)[0]) for d in arm]].astype(np.float64)
+    x1 = (A @ x[:, :, None])[:, :, 0] + (Bm @ u[:, :, None])[:, :, 0] + cc
+    same = np.concatenate([x[:, :6] + T["h"] * pred, pred], 1)
+    return verr(pred[ok], v1[ok][:, arm]), float(np.abs(x1 - same).max())
+
+
+# ---- the refusals: one argument set per JACO_EINVAL case of include/jaco_env.h, for the emulator's entry and the library's alike
+REFUSAL_MODEL = "jaco2_curtain_torque"   # dofs 0-8 hinges, 9-20 free joints
+REFUSALS = {
+    "null_out": "the output record is required",
+    "no_outputs": "at least one output is required",
+    "eps_qpos_zero": "eps_qpos and eps_qvel must be finite and positive",
+    "eps_qpos_nan": "eps_qpos and eps_qvel must be finite and positive",
+    "eps_qvel_negative": "eps_qpos and eps_qvel must be finite and positive",
+    "eps_qvel_inf": "eps_qpos and eps_qvel must be finite and positive",
+    "beyond_nv": "dof_mask bit 21 is at or beyond nv = 21",
+    "free_dof": "perturbed dof 9 belongs to a free joint",
+    "implicit_2": "implicit_damping must be 0 or 1",
+}
+
+
+def refusal_args(case):
+    """(want, no_out, options) of one refused call on REFUSAL_MODEL."""
+    opts = {"eps_qpos_zero": dict(eps_qpos=0.0), "eps_qpos_nan": dict(eps_qpos=float("nan")), "eps_qvel_negative": dict(eps_qvel=-0.125),
+            "eps_qvel_inf": dict(eps_qvel=float("inf")), "beyond_nv": dict(dof_mask=(1 << 21) | 1), "free_dof": dict(dof_mask=(1 << 9) | 1),
+            "implicit_2": dict(implicit_damping=2)}.get(case, {})
+    return (() if case == "no_outputs" else ("qacc",)), case == "null_out", opts
+
+
+class EmuFdSim(ib.EmuIkSim):
+    """EmuIkSim plus BatchedMujoco.forward_dynamics / linearize on the emulator (CPU tensors), through the product's own methods: only
+    the one launch (_fd) is replaced."""
+    device = "cpu"
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.nu = ob._model_info(self.model)[2]
+        self.launches_fd = 0
+
+    def _fd(self, ctrl, qpos, qvel, want, **options):
+        import torch
+        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
+        self.launches_fd += 1
+        r = fd(self.model, (self.qpos if qpos is None else torch.as_tensor(qpos)).numpy(), (self.qvel if qvel is None else torch.as_tensor(qvel)).numpy(),
+               n(ctrl), want=tuple(want), **options)
+        return {k: torch.from_numpy(x) for k, x in r.items()}
+
+    from mujoco_jaco_amd.physics import BatchedMujoco as _B
+    forward_dynamics, linearize = _B.forward_dynamics, _B.linearize
+    del _B
