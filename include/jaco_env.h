@@ -392,6 +392,47 @@ typedef struct JacoFdOut { float* qacc; float* qfrc_smooth; float* dqacc_dqpos; 
 int jaco_fd(JacoHandle* h, const JacoFdOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
             const JacoFdOut* out, void* stream);
 
+/* ---- open-loop rollouts: what happens over the next nknots * hold substeps if this ctrl sequence is applied from this state?
+ * mujoco.rollout.rollout(model, data, initial_state, control), contact-free, for n rollouts in ONE kernel launch
+ * (mujoco_jaco_amd/csrc/rollout.h): one wavefront per rollout runs the whole loop with the state in LDS and registers.
+ * Rollout i starts from state row state_idx_dev[i] (int32 [n]; NULL = row i, so n <= nstates) of qpos0_dev [nstates][nq] / qvel0_dev
+ * [nstates][nv] (both given, or both NULL = the handle's fp32 state with nstates = num_envs).  The state is exactly the floats handed
+ * in (low-order words zero, as in jaco_query) and qacc_warmstart starts at zero.  K candidate sequences per env share one state row
+ * through the index; n is NOT tied to num_envs, and nothing of the handle is read but the model (and its state when no override is
+ * given).  Knot k holds the row ctrl_dev[i][k][:] ([n][nknots][nu]) for `hold` substeps.
+ * Every substep is the contact-free substep of jaco_physics_step -- what a real step does under option "disable_contact", the same
+ * stages in the same order: tree walk, mass matrix and bias, the actuators (ctrlrange, the fingers' position servos, forcerange), the
+ * joint-limit rows and their Newton solve warm-started from the previous substep's qacc, Euler with implicit joint damping on the
+ * compensated pair (option "compensated"), the position update.  Joint limits are in, CONTACTS ARE NOT; free bodies are integrated like
+ * everything else, so they fall.  The solver options are the model's, as the handle has them at the call.
+ * Outputs (device, fp32; each pointer of JacoRolloutOut may be NULL, at least one of the first four is required), written after the last
+ * substep of knot k into row k:
+ *   qpos [n][nknots][nq], qvel [n][nknots][nv]: the fp32 state, as jaco_get_state would return it;
+ *   xpos [n][nknots][3], xmat [n][nknots][9]: the pose of the one frame frame_host (NULL: no pose outputs) at that state, composed as
+ *                 jaco_query composes frames -- the EE trajectory a sampling planner costs;
+ *   status [n] uint32: JACO_FLAG_NAN / JACO_FLAG_SOLVER_MAXITER, sticky over the rollout with the step kernel's rules (the rollout
+ *                 goes on, as the step does), or JACO_ROLLOUT_BAD_INDEX.
+ * final_only = 1: the arrays have ONE knot row ([n][1][..]) holding the last knot (terminal-cost planners).
+ * A state_idx entry outside [0, nstates) is handled as jaco_load_envs handles one: that rollout writes only its status word, with
+ * JACO_ROLLOUT_BAD_INDEX set, and leaves its output rows untouched.
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch (none for n == 0, which returns JACO_OK), no
+ * allocation, no synchronisation, no host copy; the options and the frame travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for NULL options; nknots < 1, hold < 1 or nknots * hold > JACO_ROLLOUT_MAX_SUBSTEPS; final_only
+ * not 0 / 1; n < 0; a NULL ctrl_dev; a NULL out or all four state / pose outputs NULL; xpos or xmat without a frame; a frame body
+ * outside [-1, fused bodies); only one of qpos0_dev / qvel0_dev; nstates != num_envs with the handle's state; nstates < 1 with an
+ * override; n > nstates with a NULL state_idx_dev. */
+#define JACO_ROLLOUT_MAX_SUBSTEPS 16384        /* nknots * hold */
+#define JACO_ROLLOUT_BAD_INDEX 0x80000u
+typedef struct JacoRolloutOptions {
+  int32_t nknots;       /* >= 1 */
+  int32_t hold;         /* substeps per knot, >= 1; 1 */
+  int32_t final_only;   /* 0 / 1 */
+  int32_t reserved;
+} JacoRolloutOptions;
+typedef struct JacoRolloutOut { float* qpos; float* qvel; float* xpos; float* xmat; uint32_t* status; } JacoRolloutOut;
+int jaco_rollout(JacoHandle* h, const JacoRolloutOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                 const float* qpos0_dev, const float* qvel0_dev, const float* ctrl_dev, const JacoRolloutOut* out, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

@@ -102,6 +102,27 @@ class JacoFdOut(ctypes.Structure):
                 ("dqacc_dctrl", ctypes.c_void_p)]
 
 
+JACO_ROLLOUT_MAX_SUBSTEPS = 16384
+JACO_ROLLOUT_BAD_INDEX = 0x80000   # jaco_rollout: the rollout's state index was outside [0, nstates); its output rows were left untouched
+
+
+class JacoRolloutOptions(ctypes.Structure):
+    """JacoRolloutOptions of include/jaco_env.h; a fresh instance holds hold = 1 and final_only = 0 (nknots has no default: it is the
+    ctrl tensor's knot count)."""
+    _fields_ = [("nknots", ctypes.c_int32), ("hold", ctypes.c_int32), ("final_only", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+    DEFAULTS = dict(nknots=0, hold=1, final_only=0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown rollout option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
+class JacoRolloutOut(ctypes.Structure):
+    _fields_ = [("qpos", ctypes.c_void_p), ("qvel", ctypes.c_void_p), ("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 def osc_axes(axes, nframes):
     """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
     or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
@@ -192,6 +213,7 @@ SYMBOLS = {
     "jaco_osc_task": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_joint": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_fd": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_rollout": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

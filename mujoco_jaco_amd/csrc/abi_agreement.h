@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h and fd.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h and rollout.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -38,3 +38,7 @@ static_assert(sizeof(JacoFdOptions) == sizeof(JacoFdOpts) && offsetof(JacoFdOpti
                   offsetof(JacoFdOptions, eps_qvel) == offsetof(JacoFdOpts, eps_qvel) && offsetof(JacoFdOptions, implicit_damping) == offsetof(JacoFdOpts, implicit_damping) &&
                   offsetof(JacoFdOptions, dof_mask) == offsetof(JacoFdOpts, dof_mask),
               "JacoFdOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoRolloutOptions) == sizeof(JacoRolloutOpts) && offsetof(JacoRolloutOptions, nknots) == offsetof(JacoRolloutOpts, nknots) &&
+                  offsetof(JacoRolloutOptions, hold) == offsetof(JacoRolloutOpts, hold) && offsetof(JacoRolloutOptions, final_only) == offsetof(JacoRolloutOpts, final_only) &&
+                  JACO_ROLLOUT_MAX_SUBSTEPS == JROLLOUT_MAX_SUBSTEPS && JACO_ROLLOUT_BAD_INDEX == JROLLOUT_BAD_INDEX,
+              "JacoRolloutOptions of the public header and the kernel's option record must agree");

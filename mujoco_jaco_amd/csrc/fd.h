@@ -209,3 +209,6 @@ void jaco_launch_fd(unsigned grid, hipStream_t st, const JacoFdArgs& Q);
 void jaco_launch_fd(unsigned grid, hipStream_t st, const JacoFdArgs& Q) { hipLaunchKernelGGL(jaco_fd_kernel, dim3(grid), dim3(64), 0, st, Q); }
 #endif
 #endif
+
+// the open-loop rollout kernel (jaco_rollout): translation unit 15
+#include "rollout.h"

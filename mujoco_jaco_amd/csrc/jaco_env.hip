@@ -1069,3 +1069,23 @@ extern "C" int jaco_fd(JacoHandle* h, const JacoFdOptions* opt_host, const float
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- open-loop rollouts (rollout.h): one wavefront per rollout, the whole knot x hold loop in one launch, nothing of the handle written ----
+extern "C" int jaco_rollout(JacoHandle* h, const JacoRolloutOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                            const float* qpos0_dev, const float* qvel0_dev, const float* ctrl_dev, const JacoRolloutOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoRolloutArgs Q{};
+  Q.state_idx = state_idx_dev; Q.qpos0 = qpos0_dev; Q.qvel0 = qvel0_dev; Q.ctrl = ctrl_dev;
+  if (out) { Q.qpos = out->qpos; Q.qvel = out->qvel; Q.xpos = out->xpos; Q.xmat = out->xmat; Q.status = out->status; }
+  const std::string why = jaco_rollout_resolve(h->model_host, reinterpret_cast<const JacoRolloutOpts*>(opt_host), reinterpret_cast<const JacoQueryFrame*>(frame_host), n,
+                                               nstates, h->num_envs, out != nullptr, &Q);
+  if (!why.empty()) { h->err = "jaco_rollout: " + why; return JACO_EINVAL; }
+  if (n == 0) return JACO_OK;
+  ENTER(h);
+  Q.model = h->model_dev;
+  if (!Q.qpos0) { Q.qpos0 = h->env.qpos; Q.qvel0 = h->env.qvel; }
+  jaco_launch_rollout((unsigned)n, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

@@ -1,0 +1,232 @@
+// Batched open-loop rollouts (jaco_rollout, include/jaco_env.h): what happens over the next nknots * hold substeps if this ctrl sequence
+// is applied from this state?  mujoco.rollout.rollout(model, data, initial_state, control), contact-free.
+//
+// One 64-lane wavefront per rollout on the contact-free LDS type (JacoLDS<JacoArm>); the whole knot x hold loop runs inside the one
+// launch with the state in LDS and registers.  The initial state is exactly the floats handed in (low words zero, as run_query), the
+// warm start is zero and stage_model runs once.  Every substep (rollout_substep) is the contact-free substep of jaco_physics_step --
+// what run_env<JacoArm> does for a real step under option disable_contact -- made of the step kernel's own stages, called as they are
+// and in the same order:
+//   stage_walk (no markers) and the zeroing of s.M, act_fetch / stage_prefetch, stage_accumulate, stage_mass_bias, stage_actuation,
+//   stage_limit_rows, row `lane` of M into registers, stage_newton_limits (warm-started from the previous substep's qacc), the Euler
+//   stage with implicit joint damping on the compensated pair (honouring m->compensated), stage_integrate_pos.
+// Joint-limit rows are in, contacts are not; free bodies are integrated like everything else.  The status word collects JFLAG_NAN and
+// JFLAG_SOLVER_MAXITER with the step kernel's rules and the rollout goes on, as the step does.
+// Mapping: lane d owns dof d, position coordinate d and row d of M.  After the last substep of a knot the lanes store the fp32 (hi)
+// state into that knot's contiguous output row, lane = word.  The frame pose of knot k is composed (as run_query composes frames) from
+// the tree walk that the next substep runs anyway; only the last knot costs a walk of its own.  Lanes 0 .. 8 store the pose row's words.
+// Fan-out: rollout i starts from state row state_idx[i] (NULL: row i); an index outside [0, nstates) writes the status word
+// JROLLOUT_BAD_INDEX and nothing else.
+// No LDS beyond the step's, no scratch memory.  Nothing of a handle is read but the model (and its fp32 state when no override is given).
+// Included at the end of fd.h; the kernel is translation unit 15 (kernels.hip -DJACO_TU=15).
+#pragma once
+#include <string>
+
+#define JROLLOUT_MAX_SUBSTEPS 16384   // = JACO_ROLLOUT_MAX_SUBSTEPS
+#define JROLLOUT_BAD_INDEX 0x80000u   // = JACO_ROLLOUT_BAD_INDEX
+struct JacoRolloutOpts {   // = JacoRolloutOptions of include/jaco_env.h (static_assert in abi_agreement.h)
+  int nknots, hold, final_only, reserved;
+};
+struct JacoRolloutArgs {
+  const JacoModelDev* model;
+  const int* state_idx;       // [n] or nullptr: rollout i starts from state row i
+  const float* qpos0;         // [nstates][nq]  (the handle's hi words, or the caller's override)
+  const float* qvel0;         // [nstates][nv]
+  const float* ctrl;          // [n][nknots][nu]
+  float* qpos;                // [n][rows][nq] or nullptr; rows = final_only ? 1 : nknots
+  float* qvel;                // [n][rows][nv] or nullptr
+  float* xpos;                // [n][rows][3] or nullptr
+  float* xmat;                // [n][rows][9] or nullptr
+  unsigned* status;           // [n] or nullptr
+  int n, nstates, nknots, hold, final_only;
+  JacoQueryFrame fr;          // by value: no device buffer, no upload (read only when xpos or xmat is wanted)
+};
+
+// The host half shared by jaco_rollout (jaco_env.hip) and the emulator's entry: every argument check, then the options and the frame
+// into the argument block, whose pointers the caller has filled in as they were handed over (qpos0 / qvel0 nullptr: the handle's state
+// of num_envs rows, which the caller puts in afterwards; have_out: the output record was not NULL).  Returns an empty string, or what
+// is wrong.
+static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const JacoRolloutOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
+                                               bool have_out, JacoRolloutArgs* Q) {
+  if (!o) return "the options are required";
+  if (o->nknots < 1 || o->hold < 1 || (long long)o->nknots * o->hold > JROLLOUT_MAX_SUBSTEPS)
+    return "nknots " + std::to_string(o->nknots) + " x hold " + std::to_string(o->hold) + ": both must be at least 1 and their product at most " + std::to_string(JROLLOUT_MAX_SUBSTEPS);
+  if (o->final_only != 0 && o->final_only != 1) return "final_only must be 0 or 1";
+  if (n < 0) return "n " + std::to_string(n) + " is negative";
+  if (!Q->ctrl) return "the ctrl sequences are required";
+  if (!have_out) return "the output record is required";
+  if (!Q->qpos && !Q->qvel && !Q->xpos && !Q->xmat) return "at least one of the outputs qpos, qvel, xpos and xmat is required";
+  if ((Q->xpos || Q->xmat) && !frame) return "xpos and xmat need a frame";
+  if (frame && (frame->body < -1 || frame->body >= m.nbody)) return "frame body " + std::to_string(frame->body) + " outside [-1, " + std::to_string(m.nbody) + ")";
+  if ((Q->qpos0 != nullptr) != (Q->qvel0 != nullptr)) return "qpos0 and qvel0 are given together or not at all";
+  if (!Q->qpos0 && nstates != num_envs) return "nstates " + std::to_string(nstates) + " with the handle's state of " + std::to_string(num_envs) + " envs";
+  if (Q->qpos0 && nstates < 1) return "nstates " + std::to_string(nstates) + " with a state override";
+  if (!Q->state_idx && n > nstates) return "n " + std::to_string(n) + " rollouts from " + std::to_string(nstates) + " states without a state index";
+  Q->n = n; Q->nstates = nstates;
+  Q->nknots = o->nknots; Q->hold = o->hold; Q->final_only = o->final_only;
+  if (frame) Q->fr = *frame;
+  return std::string();
+}
+
+// (as fd_args_view)
+#ifdef JACO_EMULATED
+JDEV const JacoRolloutArgs* rollout_args_view(const JacoRolloutArgs& Q) { return &Q; }
+#else
+JDEV const JacoRolloutArgs* rollout_args_view(const JacoRolloutArgs&) {
+  typedef const JacoRolloutArgs __attribute__((address_space(4))) * KP;
+  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+  return (const JacoRolloutArgs*)p;
+}
+#endif
+
+// The first half of a substep: the tree walk and the zeroing of s.M.  Leaves the body poses of the current state in s.xpos / s.xmat.
+template <class L>
+JDEV void rollout_walk(const JacoModelDev* m, L& s, int lane) {
+  stage_walk(m, s, lane, false);
+  for (int i = lane; i < JMBLK; i += 64) s.M[i] = 0.f;
+  wave_sync();
+}
+
+// The rest of the substep, from the subtree sums to the position update: run_env's contact-free substep body, stage by stage.
+template <class L>
+JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags) {
+  const int nv = m->nv;
+  const ActParams actp = act_fetch(m, lane);
+  const StagePrefetch pf = stage_prefetch(m, lane);
+  stage_accumulate(m, s, lane);
+  wave_sync();
+  stage_mass_bias(m, s, lane, pf);
+  wave_sync();
+  stage_actuation(m, s, lane, actp);
+  stage_limit_rows(m, s, lane, pf);
+  wave_sync();
+  float mrow[JNV], h[JNV];   // row `lane` of the block-diagonal mass matrix (as run_env loads it: zero rows for lanes >= nv)
+  {
+    const int blo = lane < JB0 ? 0 : (lane < JB1 ? JB0 : JB1), bn = lane < JB0 ? JB0 : (lane < JB1 ? JB1 - JB0 : JNV - JB1);
+    const int rbase = lane < nv ? m_index(lane, blo) : 0;
+#pragma unroll
+    for (int j = 0; j < JNV; j++) { const bool in = lane < nv && j >= blo && j < blo + bn; mrow[j] = in ? s.M[in ? rbase + j - blo : 0] : 0.f; }
+  }
+  const float smooth = lane < nv ? s.smooth[lane] : 0.f;
+  wave_sync();
+  const float hdamp = (m->has_damping && lane < nv) ? m->timestep * pf.damping : 0.f;
+  const NewtonOut nw = stage_newton_limits(m, s, mrow, smooth, hdamp, lane);
+  if ((nw.iters & 255) >= m->iterations) flags |= JFLAG_SOLVER_MAXITER;
+  wave_sync();
+  // Euler with implicit joint damping: (M + h D) qacc = total on the damped block, the solver's qacc elsewhere
+  const float total = smooth + nw.qfrc_con;
+  float qacc_e = nw.qacc;
+  if (m->has_damping) {
+    float qd;
+    if (nw.have_qdamped) qd = nw.qdamped;
+    else {
+#pragma unroll
+      for (int j = 0; j < JNV; j++) h[j] = (lane < nv ? mrow[j] : 0.f) + (lane == j ? (lane < nv ? hdamp : 1.f) : 0.f);
+      qd = ldl_solve_blocks(h, total, lane, JDAMPED_BLOCKS);
+    }
+    qacc_e = lane < JB0 ? qd : nw.qacc;
+  }
+  wave_sync();
+  if (lane < nv) {
+    float v;
+    if (m->compensated) {
+      const f2 nvl = comp_advance(s.qvel[lane], s.qvel_lo[lane], m->timestep, m->timestep_lo, qacc_e, 0.f);
+      v = nvl.hi; s.qvel_lo[lane] = nvl.lo;
+    } else v = s.qvel[lane] + m->timestep * qacc_e;
+    s.qvel[lane] = v;
+    s.qacc_ws[lane] = nw.qacc;
+    if (!(v == v) || fabsf(v) > 1e10f) flags |= JFLAG_NAN;
+  }
+  wave_sync();
+  stage_integrate_pos(m, s, lane);
+  wave_sync();
+}
+
+// The frame's pose at the body poses in s.xpos / s.xmat (run_query's composition: xpos_b + R_b p, R_b R_f) into row `row` of the pose
+// outputs: every lane composes it, lane k stores word k.
+template <class L>
+JDEV void rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lane) {
+  const JacoQueryFrame& F = Q.fr;
+  const int b = F.body;
+  v3 p = ld3(F.pos);
+  m3 R = ldm(F.mat);
+  if (b >= 0) {   // (wave-uniform)
+    const m3 Rb = ldm(s.xmat[b]);
+    p = ld3(s.xpos[b]) + mul(Rb, ld3(F.pos));
+    R = mul(Rb, ldm(F.mat));
+  }
+  float w = lane == 0 ? p.x : (lane == 1 ? p.y : p.z), r = 0.f;
+#pragma unroll
+  for (int k = 0; k < 9; k++) if (lane == k) r = R.m[k];
+  if (Q.xpos && lane < 3) Q.xpos[row * 3 + lane] = w;
+  if (Q.xmat && lane < 9) Q.xmat[row * 9 + lane] = r;
+}
+
+template <class L>
+JDEV void run_rollout(const JacoRolloutArgs& Q_, L& s, int i, int lane) {
+  const JacoRolloutArgs* Qp = rollout_args_view(Q_);
+  const JacoModelDev* m = opaque_ptr(Qp->model);
+  const int nq = m->nq, nv = m->nv, nu = m->nu;
+  const int src = wave_uniform_i(Qp->state_idx ? Qp->state_idx[i] : i);
+  if (src < 0 || src >= Qp->nstates) {   // (as jaco_load_envs: neither a fault nor silence)
+    if (lane == 0 && Qp->status) Qp->status[i] = JROLLOUT_BAD_INDEX;
+    return;
+  }
+  // the prologue of run_query: the state is exactly the floats handed in (low-order words zero); the warm start is zero
+  if (lane < nq) { s.qpos[lane] = Qp->qpos0[(size_t)src * nq + lane]; s.qpos_lo[lane] = 0.f; }
+  if (lane < nv) { s.qvel[lane] = Qp->qvel0[(size_t)src * nv + lane]; s.qvel_lo[lane] = 0.f; s.qacc_ws[lane] = 0.f; }
+  stage_model(m, s, lane);
+  if (lane == 0) { s.ncon = 0; s.nefc = 0; s.ncand = 0; s.nlimit = 0; s.nsphere = 0; s.nside = 0; s.nside_cand = 0; }   // (LDS is not zeroed between workgroups)
+  wave_sync();
+  unsigned flags = 0u;
+  const int nknots = Qp->nknots, hold = Qp->hold;
+  const bool every = Qp->final_only == 0, pose = Qp->xpos != nullptr || Qp->xmat != nullptr;
+#pragma nounroll
+  for (int k = 0; k < nknots; k++) {
+    if (lane < nu) s.ctrl[lane] = Qp->ctrl[((size_t)i * nknots + k) * nu + lane];
+    wave_sync();
+#pragma nounroll
+    for (int sub = 0; sub < hold; sub++) {
+      // (as run_env's substep loop and fd_pass: the argument block is read afresh, and with the pointer's provenance and the lane id
+      // hidden the optimiser cannot hoist the substep's model loads and lane-derived addresses out of the loop and keep them alive,
+      // spilled, across all of it)
+      Qp = rollout_args_view(Q_);
+      m = opaque_ptr(Qp->model);
+      lane = wave_opaque_i(lane);
+      rollout_walk(m, s, lane);
+      if (pose && every && sub == 0 && k > 0) rollout_pose(*Qp, s, (size_t)i * nknots + (k - 1), lane);   // the previous knot's pose: this walk's
+      rollout_substep(m, s, lane, flags);
+    }
+    if (every || k == nknots - 1) {
+      const size_t row = every ? (size_t)i * nknots + k : (size_t)i;
+      if (Qp->qpos && lane < nq) Qp->qpos[row * nq + lane] = s.qpos[lane];
+      if (Qp->qvel && lane < nv) Qp->qvel[row * nv + lane] = s.qvel[lane];
+    }
+  }
+  Qp = rollout_args_view(Q_);
+  if (pose) {   // the last knot's pose needs a walk of its own
+    stage_walk(opaque_ptr(Qp->model), s, lane, false);
+    wave_sync();
+    rollout_pose(*Qp, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
+  }
+  if (Qp->status) {
+    unsigned f = flags;
+    for (int o = 1; o < 64; o <<= 1) f |= (unsigned)wave_shfl_i((int)f, lane ^ o);
+    if (lane == 0) Qp->status[i] = f;
+  }
+}
+
+#if JACO_TU_HAS(15)
+__global__ __launch_bounds__(64, 4) void jaco_rollout_kernel(JacoRolloutArgs Q) {
+  __shared__ JacoLDS<JacoArm> s;
+  const int i = (int)blockIdx.x;
+  if (i >= Q.n) return;
+  run_rollout(Q, s, i, (int)threadIdx.x);
+}
+#endif
+
+#ifndef JACO_EMULATED
+void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q);
+#if defined(JACO_TU) && JACO_TU == 15
+void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q) { hipLaunchKernelGGL(jaco_rollout_kernel, dim3(grid), dim3(64), 0, st, Q); }
+#endif
+#endif

@@ -311,6 +311,51 @@ class BatchedMujoco:
                      implicit_damping=int(bool(implicit_damping)), dof_mask=mask)
         return {"qacc": r["qacc"], "dq": r["dqacc_dqpos"].transpose(1, 2), "dv": r["dqacc_dqvel"].transpose(1, 2), "du": r["dqacc_dctrl"].transpose(1, 2)}
 
+    # ---- open-loop rollouts (jaco_rollout: n rollouts of T knots x hold contact-free substeps, one launch)
+    def _rollout(self, ctrl, qpos, qvel, state_index, nstates, frame, want, **options):
+        """One jaco_rollout launch: {name: tensor} of the outputs in `want` (names of JacoRolloutOut), in the C ABI's layout.  ctrl
+        [n, nknots, nu] fp32, qpos / qvel [nstates, ..] fp32 or None, state_index [n] int32 or None: contiguous device tensors."""
+        n, dev = ctrl.shape[0], self.device
+        rows = 1 if options.get("final_only") else options["nknots"]
+        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
+        if n == 0:   # (no launch: jaco_rollout returns JACO_OK for n == 0)
+            return res
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        out = _lib.JacoRolloutOut(*[ptr(res.get(k)) for k in shapes])
+        opt = _lib.JacoRolloutOptions(**options)
+        self._chk(self.L.jaco_rollout(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
+                                      None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, ptr(state_index), int(nstates),
+                                      ptr(qpos), ptr(qvel), ptr(ctrl), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        return res
+
+    def rollout(self, ctrl, qpos=None, qvel=None, state_index=None, hold=1, frame=None, final_only=False):
+        """What happens over the next T x hold substeps if the ctrl sequences ctrl [n, T, nu] are applied?  mujoco.rollout.rollout,
+        contact-free: rollout i starts from row state_index[i] ([n] integers; None: row i) of qpos [nstates, nq] / qvel [nstates, nv]
+        (both, or neither: the current state of the num_envs envs) with a zero warm start, and holds ctrl[i, k] for `hold` substeps in
+        knot k.  Every substep is the one send_forces runs under option "disable_contact": joint limits are in, contacts are not, free
+        bodies fall.  n is not tied to num_envs: K sequences per env share a state row through state_index.
+        {"qpos": [n, T, nq], "qvel": [n, T, nv]: the state after each knot;  "status": [n] int32, JACO_FLAG_NAN / JACO_FLAG_SOLVER_MAXITER
+        of the rollout, or _lib.JACO_ROLLOUT_BAD_INDEX where state_index was outside [0, nstates): those rollouts' rows are left
+        unwritten} plus, with frame (_lib.JacoFrame; FrameTable.jaco_frame), {"xpos": [n, T, 3], "xmat": [n, T, 9]}: the frame's pose
+        after each knot.  final_only=True: the arrays have one knot row, the last.  One launch on the current stream, no
+        synchronisation; the sim's state is not touched."""
+        dev = self.device
+        ctrl = torch.as_tensor(ctrl, dtype=torch.float32, device=dev)
+        if ctrl.dim() != 3 or ctrl.shape[2] != self.nu:
+            raise ValueError("rollout: ctrl has shape %s, not [n, T, %d]" % (tuple(ctrl.shape), self.nu))
+        n = ctrl.shape[0]
+        prep = lambda t, w: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, w).contiguous()
+        q, v = prep(qpos, self.nq), prep(qvel, self.nv)
+        if q is not None and v is not None and q.shape[0] != v.shape[0]:
+            raise ValueError("rollout: %d qpos rows but %d qvel rows" % (q.shape[0], v.shape[0]))
+        nstates = self.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
+        idx = self._index(state_index)
+        if idx is not None and idx.numel() != n:
+            raise ValueError("rollout: %d ctrl sequences but %d state indices" % (n, idx.numel()))
+        want = ("qpos", "qvel", "status") + (("xpos", "xmat") if frame is not None else ())
+        return self._rollout(ctrl.contiguous(), q, v, idx, nstates, frame, want, nknots=int(ctrl.shape[1]), hold=int(hold), final_only=int(bool(final_only)))
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

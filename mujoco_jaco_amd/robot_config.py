@@ -310,6 +310,29 @@ class BatchedMujocoConfig:
         c = x1 - (A @ x[:, :, None])[:, :, 0] - (Bm @ u[:, :, None])[:, :, 0]
         return A, Bm, c
 
+    def rollout(self, ctrl, hold=1, q=None, dq=None, final_only=False):
+        """Open-loop prediction of this config's arm and end effector: ctrl [num_envs, T, nu] (one sequence per env) or [num_envs, K, T,
+        nu] (K candidate sequences per env, all started from that env's state through a state index -- the states are not copied), each
+        row held for `hold` substeps, from the current state (or q / dq, arm angles / velocities spliced into it).  Contact-free, with
+        joint limits (BatchedMujoco.rollout).  {"q": [num_envs, K, T, n_arm], "dq": likewise, "ee_pos": [num_envs, K, T, 3], "ee_mat":
+        [num_envs, K, T, 9]: the arm's joints and the pose of `ee` after each knot; "status": [num_envs, K]}; without K the K axis is
+        squeezed; final_only=True: T = 1, the last knot.  One jaco_rollout launch; the sim's state is not touched."""
+        import torch
+        B = self.sim.num_envs
+        ctrl = torch.as_tensor(ctrl, dtype=torch.float32, device=self.sim.device)
+        if ctrl.dim() not in (3, 4) or ctrl.shape[0] != B:
+            raise ValueError("rollout: ctrl has shape %s, not [%d, T, nu] or [%d, K, T, nu]" % (tuple(ctrl.shape), B, B))
+        squeeze = ctrl.dim() == 3
+        K, T = (1 if squeeze else ctrl.shape[1]), ctrl.shape[-2]
+        qpos, qvel = self._spliced(q, dq)
+        index = torch.arange(B, dtype=torch.int32, device=ctrl.device).repeat_interleave(K)
+        r = self.sim.rollout(ctrl.reshape(B * K, T, ctrl.shape[-1]), qpos, qvel, state_index=index, hold=hold, frame=self._frames[0], final_only=final_only)
+        rows = 1 if final_only else T
+        out = {"q": r["qpos"][..., self.arm_qadr], "dq": r["qvel"][..., self.arm], "ee_pos": r["xpos"], "ee_mat": r["xmat"]}
+        out = {k: t.reshape(B, K, rows, t.shape[-1]) for k, t in out.items()}
+        out["status"] = r["status"].reshape(B, K)
+        return {k: t[:, 0] for k, t in out.items()} if squeeze else out
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
