@@ -433,6 +433,56 @@ typedef struct JacoRolloutOut { float* qpos; float* qvel; float* xpos; float* xm
 int jaco_rollout(JacoHandle* h, const JacoRolloutOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
                  const float* qpos0_dev, const float* qvel0_dev, const float* ctrl_dev, const JacoRolloutOut* out, void* stream);
 
+/* ---- closed-loop rollouts: jaco_rollout with the ctrl of knot k computed inside the kernel from the state at knot k -- the forward
+ * pass of iLQR and its line search (u_k = ubar_k + alpha k_k + K_k (x_k - xbar_k)), a plan tracked with TVLQR gains, PD tracking of a joint
+ * trajectory, a feedback plan tried from many perturbed starts -- for n rollouts in ONE kernel launch
+ * (mujoco_jaco_amd/csrc/rollout_fb.h).  The state arguments (state_idx_dev, nstates, qpos0_dev, qvel0_dev), the substep, the outputs
+ * qpos / qvel / xpos / xmat / status, final_only and n == 0 are those of jaco_rollout, word for word.
+ * Plans (JacoRolloutPlan, a host record of device pointers): rollout i follows plan p = plan_idx[i] (int32 [n]; NULL = plan i, so
+ * n <= nplans); many rollouts share one plan through the index, as they share states.  With nd = ndofs and nx = 2 nd:
+ *   ctrl  [nplans][nknots][nu]      the nominal ctrl rows (required);
+ *   kff   [nplans][nknots][nu]      the feed-forward step, or NULL;
+ *   gain  [nplans][nknots][nu][nx]  the feedback gains, row a = actuator a, or NULL;
+ *   xref  [nplans][nknots][nx]      the reference states (required with gain);
+ *   alpha [n]                       the line-search step of rollout i, or NULL = 1.0f (needs kff).
+ * THE LAW, at an evaluation in knot k; this order of fp32 operations is part of the interface:
+ *   x_j = qpos[qposadr(dofs[j])] for j < nd, qvel[dofs[j - nd]] for nd <= j < nx   (the fp32 state, as jaco_get_state would return it)
+ *   d_j = x_j - xref[p][k][j]                                                       (one subtraction; NOT wrapped: the law is a local
+ *                                                                                    one about a continuous reference)
+ *   u_a = kff ? fmaf(alpha_i, kff[p][k][a], ctrl[p][k][a]) : ctrl[p][k][a]
+ *   u_a = fmaf(gain[p][k][a][j], d_j, u_a)   for j = 0 .. nx-1, ascending           (gain NULL: skipped)
+ * for every actuator a = 0 .. nu-1.  u is the commanded ctrl; the actuator stage clamps it to ctrlrange afterwards, as it clamps any
+ * ctrl.  per_substep = 0: the law is evaluated before the first substep of a knot and held for the knot (zero-order hold);
+ * per_substep = 1: before every substep, against the same knot's rows.  dofs: ndofs distinct hinge dofs (used only when gain is given).
+ * Output ctrl [n][E][nu], E = nknots (per_substep = 0) or nknots * hold: the u of every evaluation, as commanded (before the clamp) --
+ * iLQR's new nominal.  It has all E rows whether or not final_only is set.  ctrl counts as an output: at least one of the six pointers
+ * of JacoRolloutFbOut is required.
+ * A state_idx or plan_idx entry out of range: that rollout writes only its status word, with JACO_ROLLOUT_BAD_INDEX set.
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch (none for n == 0, which returns JACO_OK), no
+ * allocation, no synchronisation, no host copy; the options (the dof list included) and the frame travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for everything jaco_rollout refuses (the ctrl sequences being plan->ctrl, the outputs the six)
+ * and for a NULL plan; nplans < 1; n > nplans with a NULL plan_idx; gain without xref; alpha without kff; per_substep not 0 / 1; with
+ * gain: ndofs outside [1, JACO_ROLLOUT_FB_MAX_DOFS], a dof outside [0, nv), a dof of a free joint, a dof listed twice. */
+#define JACO_ROLLOUT_FB_MAX_DOFS 18
+typedef struct JacoRolloutFbOptions {
+  int32_t nknots, hold, final_only, per_substep;  /* as JacoRolloutOptions; per_substep 0 / 1 */
+  int32_t ndofs;                                  /* 1 .. MAX_DOFS; used only when gain is given */
+  int32_t dofs[JACO_ROLLOUT_FB_MAX_DOFS];         /* distinct hinge dofs */
+  int32_t reserved;
+} JacoRolloutFbOptions;
+typedef struct JacoRolloutPlan {                  /* device pointers */
+  const float* ctrl;   /* [nplans][nknots][nu]       required */
+  const float* kff;    /* [nplans][nknots][nu]       or NULL */
+  const float* gain;   /* [nplans][nknots][nu][nx]   or NULL */
+  const float* xref;   /* [nplans][nknots][nx]       required with gain */
+  const float* alpha;  /* [n]                        or NULL (needs kff) */
+  const int32_t* plan_idx; /* [n] or NULL: plan i, so n <= nplans */
+  int32_t nplans;
+} JacoRolloutPlan;
+typedef struct JacoRolloutFbOut { float* qpos; float* qvel; float* xpos; float* xmat; uint32_t* status; float* ctrl; } JacoRolloutFbOut;
+int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                    const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutFbOut* out, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

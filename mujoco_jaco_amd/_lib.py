@@ -123,6 +123,38 @@ class JacoRolloutOut(ctypes.Structure):
     _fields_ = [("qpos", ctypes.c_void_p), ("qvel", ctypes.c_void_p), ("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+JACO_ROLLOUT_FB_MAX_DOFS = 18
+
+
+class JacoRolloutFbOptions(ctypes.Structure):
+    """JacoRolloutFbOptions of include/jaco_env.h; a fresh instance holds hold = 1, final_only = 0, per_substep = 0 and no dofs.  dofs: a
+    list of at most JACO_ROLLOUT_FB_MAX_DOFS hinge dofs (ndofs is its length; the library checks the dofs themselves)."""
+    _fields_ = [("nknots", ctypes.c_int32), ("hold", ctypes.c_int32), ("final_only", ctypes.c_int32), ("per_substep", ctypes.c_int32),
+                ("ndofs", ctypes.c_int32), ("dofs", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS), ("reserved", ctypes.c_int32)]
+    DEFAULTS = dict(nknots=0, hold=1, final_only=0, per_substep=0, dofs=())
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown closed-loop rollout option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        o = {**self.DEFAULTS, **options}
+        dofs = [int(d) for d in o.pop("dofs")]
+        if len(dofs) > JACO_ROLLOUT_FB_MAX_DOFS:
+            raise ValueError("%d dofs: a closed-loop rollout takes at most %d" % (len(dofs), JACO_ROLLOUT_FB_MAX_DOFS))
+        super().__init__(ndofs=len(dofs), **o)
+        self.dofs[:len(dofs)] = dofs
+
+
+class JacoRolloutPlan(ctypes.Structure):
+    _fields_ = [("ctrl", ctypes.c_void_p), ("kff", ctypes.c_void_p), ("gain", ctypes.c_void_p), ("xref", ctypes.c_void_p), ("alpha", ctypes.c_void_p),
+                ("plan_idx", ctypes.c_void_p), ("nplans", ctypes.c_int32)]
+
+
+class JacoRolloutFbOut(ctypes.Structure):
+    _fields_ = [("qpos", ctypes.c_void_p), ("qvel", ctypes.c_void_p), ("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("ctrl", ctypes.c_void_p)]
+
+
 def osc_axes(axes, nframes):
     """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
     or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
@@ -214,6 +246,7 @@ SYMBOLS = {
     "jaco_joint": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_fd": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_rollout_fb": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

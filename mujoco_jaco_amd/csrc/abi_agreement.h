@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h and rollout.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h and rollout_fb.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -42,3 +42,13 @@ static_assert(sizeof(JacoRolloutOptions) == sizeof(JacoRolloutOpts) && offsetof(
                   offsetof(JacoRolloutOptions, hold) == offsetof(JacoRolloutOpts, hold) && offsetof(JacoRolloutOptions, final_only) == offsetof(JacoRolloutOpts, final_only) &&
                   JACO_ROLLOUT_MAX_SUBSTEPS == JROLLOUT_MAX_SUBSTEPS && JACO_ROLLOUT_BAD_INDEX == JROLLOUT_BAD_INDEX,
               "JacoRolloutOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoRolloutFbOptions) == sizeof(JacoRolloutFbOpts) && offsetof(JacoRolloutFbOptions, nknots) == offsetof(JacoRolloutFbOpts, nknots) &&
+                  offsetof(JacoRolloutFbOptions, hold) == offsetof(JacoRolloutFbOpts, hold) && offsetof(JacoRolloutFbOptions, final_only) == offsetof(JacoRolloutFbOpts, final_only) &&
+                  offsetof(JacoRolloutFbOptions, per_substep) == offsetof(JacoRolloutFbOpts, per_substep) && offsetof(JacoRolloutFbOptions, ndofs) == offsetof(JacoRolloutFbOpts, ndofs) &&
+                  offsetof(JacoRolloutFbOptions, dofs) == offsetof(JacoRolloutFbOpts, dofs) && JACO_ROLLOUT_FB_MAX_DOFS == JROLLOUT_FB_MAX_DOFS,
+              "JacoRolloutFbOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoRolloutPlan) == sizeof(JacoRolloutFbPlan) && offsetof(JacoRolloutPlan, ctrl) == offsetof(JacoRolloutFbPlan, ctrl) &&
+                  offsetof(JacoRolloutPlan, kff) == offsetof(JacoRolloutFbPlan, kff) && offsetof(JacoRolloutPlan, gain) == offsetof(JacoRolloutFbPlan, gain) &&
+                  offsetof(JacoRolloutPlan, xref) == offsetof(JacoRolloutFbPlan, xref) && offsetof(JacoRolloutPlan, alpha) == offsetof(JacoRolloutFbPlan, alpha) &&
+                  offsetof(JacoRolloutPlan, plan_idx) == offsetof(JacoRolloutFbPlan, plan_idx) && offsetof(JacoRolloutPlan, nplans) == offsetof(JacoRolloutFbPlan, nplans),
+              "JacoRolloutPlan of the public header and the kernel's plan record must agree");

@@ -1089,3 +1089,23 @@ extern "C" int jaco_rollout(JacoHandle* h, const JacoRolloutOptions* opt_host, c
   HIPCHK(h, hipGetLastError());
   return JACO_OK;
 }
+
+// ---- closed-loop rollouts (rollout_fb.h): jaco_rollout with the feedback law evaluated inside the kernel, nothing of the handle written ----
+extern "C" int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                               const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutFbOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoRolloutFbArgs Q{};
+  Q.R.state_idx = state_idx_dev; Q.R.qpos0 = qpos0_dev; Q.R.qvel0 = qvel0_dev;
+  if (out) { Q.R.qpos = out->qpos; Q.R.qvel = out->qvel; Q.R.xpos = out->xpos; Q.R.xmat = out->xmat; Q.R.status = out->status; Q.ctrl_out = out->ctrl; }
+  const std::string why = jaco_rollout_fb_resolve(h->model_host, reinterpret_cast<const JacoRolloutFbOpts*>(opt_host), reinterpret_cast<const JacoQueryFrame*>(frame_host), n,
+                                                  nstates, h->num_envs, reinterpret_cast<const JacoRolloutFbPlan*>(plan_host), out != nullptr, &Q);
+  if (!why.empty()) { h->err = "jaco_rollout_fb: " + why; return JACO_EINVAL; }
+  if (n == 0) return JACO_OK;
+  ENTER(h);
+  Q.R.model = h->model_dev;
+  if (!Q.R.qpos0) { Q.R.qpos0 = h->env.qpos; Q.R.qvel0 = h->env.qvel; }
+  jaco_launch_rollout_fb((unsigned)n, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}

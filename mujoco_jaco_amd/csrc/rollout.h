@@ -41,12 +41,13 @@ struct JacoRolloutArgs {
   JacoQueryFrame fr;          // by value: no device buffer, no upload (read only when xpos or xmat is wanted)
 };
 
-// The host half shared by jaco_rollout (jaco_env.hip) and the emulator's entry: every argument check, then the options and the frame
+// The host half shared by jaco_rollout (jaco_env.hip), the emulator's entry and, with its own rule for which outputs count
+// (any_output, and the message when none is there), jaco_rollout_fb_resolve: every argument check, then the options and the frame
 // into the argument block, whose pointers the caller has filled in as they were handed over (qpos0 / qvel0 nullptr: the handle's state
 // of num_envs rows, which the caller puts in afterwards; have_out: the output record was not NULL).  Returns an empty string, or what
 // is wrong.
-static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const JacoRolloutOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
-                                               bool have_out, JacoRolloutArgs* Q) {
+static inline std::string jaco_rollout_resolve_outputs(const JacoModelDev& m, const JacoRolloutOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
+                                                       bool have_out, bool any_output, const char* no_output, JacoRolloutArgs* Q) {
   if (!o) return "the options are required";
   if (o->nknots < 1 || o->hold < 1 || (long long)o->nknots * o->hold > JROLLOUT_MAX_SUBSTEPS)
     return "nknots " + std::to_string(o->nknots) + " x hold " + std::to_string(o->hold) + ": both must be at least 1 and their product at most " + std::to_string(JROLLOUT_MAX_SUBSTEPS);
@@ -54,7 +55,7 @@ static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const Jaco
   if (n < 0) return "n " + std::to_string(n) + " is negative";
   if (!Q->ctrl) return "the ctrl sequences are required";
   if (!have_out) return "the output record is required";
-  if (!Q->qpos && !Q->qvel && !Q->xpos && !Q->xmat) return "at least one of the outputs qpos, qvel, xpos and xmat is required";
+  if (!any_output) return no_output;
   if ((Q->xpos || Q->xmat) && !frame) return "xpos and xmat need a frame";
   if (frame && (frame->body < -1 || frame->body >= m.nbody)) return "frame body " + std::to_string(frame->body) + " outside [-1, " + std::to_string(m.nbody) + ")";
   if ((Q->qpos0 != nullptr) != (Q->qvel0 != nullptr)) return "qpos0 and qvel0 are given together or not at all";
@@ -65,6 +66,13 @@ static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const Jaco
   Q->nknots = o->nknots; Q->hold = o->hold; Q->final_only = o->final_only;
   if (frame) Q->fr = *frame;
   return std::string();
+}
+
+// jaco_rollout's own: one of the four state / pose outputs is required.
+static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const JacoRolloutOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
+                                               bool have_out, JacoRolloutArgs* Q) {
+  return jaco_rollout_resolve_outputs(m, o, frame, n, nstates, num_envs, have_out, Q->qpos || Q->qvel || Q->xpos || Q->xmat,
+                                      "at least one of the outputs qpos, qvel, xpos and xmat is required", Q);
 }
 
 // (as fd_args_view)
@@ -161,6 +169,27 @@ JDEV void rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lan
   if (Q.xmat && lane < 9) Q.xmat[row * 9 + lane] = r;
 }
 
+// The prologue of a rollout (run_query's): state row `src` into LDS exactly as the floats handed in (low-order words zero), a zero warm
+// start, the model staged once.
+template <class L>
+JDEV void rollout_prologue(const JacoRolloutArgs* Qp, const JacoModelDev* m, L& s, int src, int lane) {
+  const int nq = m->nq, nv = m->nv;
+  if (lane < nq) { s.qpos[lane] = Qp->qpos0[(size_t)src * nq + lane]; s.qpos_lo[lane] = 0.f; }
+  if (lane < nv) { s.qvel[lane] = Qp->qvel0[(size_t)src * nv + lane]; s.qvel_lo[lane] = 0.f; s.qacc_ws[lane] = 0.f; }
+  stage_model(m, s, lane);
+  if (lane == 0) { s.ncon = 0; s.nefc = 0; s.ncand = 0; s.nlimit = 0; s.nsphere = 0; s.nside = 0; s.nside_cand = 0; }   // (LDS is not zeroed between workgroups)
+  wave_sync();
+}
+
+// The lanes' sticky flags, or-reduced over the wavefront into rollout i's status word.
+JDEV void rollout_status(const JacoRolloutArgs* Qp, unsigned flags, int i, int lane) {
+  if (Qp->status) {
+    unsigned f = flags;
+    for (int o = 1; o < 64; o <<= 1) f |= (unsigned)wave_shfl_i((int)f, lane ^ o);
+    if (lane == 0) Qp->status[i] = f;
+  }
+}
+
 template <class L>
 JDEV void run_rollout(const JacoRolloutArgs& Q_, L& s, int i, int lane) {
   const JacoRolloutArgs* Qp = rollout_args_view(Q_);
@@ -171,12 +200,7 @@ JDEV void run_rollout(const JacoRolloutArgs& Q_, L& s, int i, int lane) {
     if (lane == 0 && Qp->status) Qp->status[i] = JROLLOUT_BAD_INDEX;
     return;
   }
-  // the prologue of run_query: the state is exactly the floats handed in (low-order words zero); the warm start is zero
-  if (lane < nq) { s.qpos[lane] = Qp->qpos0[(size_t)src * nq + lane]; s.qpos_lo[lane] = 0.f; }
-  if (lane < nv) { s.qvel[lane] = Qp->qvel0[(size_t)src * nv + lane]; s.qvel_lo[lane] = 0.f; s.qacc_ws[lane] = 0.f; }
-  stage_model(m, s, lane);
-  if (lane == 0) { s.ncon = 0; s.nefc = 0; s.ncand = 0; s.nlimit = 0; s.nsphere = 0; s.nside = 0; s.nside_cand = 0; }   // (LDS is not zeroed between workgroups)
-  wave_sync();
+  rollout_prologue(Qp, m, s, src, lane);
   unsigned flags = 0u;
   const int nknots = Qp->nknots, hold = Qp->hold;
   const bool every = Qp->final_only == 0, pose = Qp->xpos != nullptr || Qp->xmat != nullptr;
@@ -208,11 +232,7 @@ JDEV void run_rollout(const JacoRolloutArgs& Q_, L& s, int i, int lane) {
     wave_sync();
     rollout_pose(*Qp, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
   }
-  if (Qp->status) {
-    unsigned f = flags;
-    for (int o = 1; o < 64; o <<= 1) f |= (unsigned)wave_shfl_i((int)f, lane ^ o);
-    if (lane == 0) Qp->status[i] = f;
-  }
+  rollout_status(Qp, flags, i, lane);
 }
 
 #if JACO_TU_HAS(15)
@@ -230,3 +250,6 @@ void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q
 void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q) { hipLaunchKernelGGL(jaco_rollout_kernel, dim3(grid), dim3(64), 0, st, Q); }
 #endif
 #endif
+
+// the closed-loop rollout kernel (jaco_rollout_fb): translation unit 16
+#include "rollout_fb.h"

@@ -356,6 +356,80 @@ class BatchedMujoco:
         want = ("qpos", "qvel", "status") + (("xpos", "xmat") if frame is not None else ())
         return self._rollout(ctrl.contiguous(), q, v, idx, nstates, frame, want, nknots=int(ctrl.shape[1]), hold=int(hold), final_only=int(bool(final_only)))
 
+    # ---- closed-loop rollouts (jaco_rollout_fb: jaco_rollout with the feedback law evaluated inside the kernel, one launch)
+    def _rollout_fb(self, plan, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        """One jaco_rollout_fb launch: {name: tensor} of the outputs in `want` (names of JacoRolloutFbOut), in the C ABI's layout.  plan:
+        {"ctrl": [P, nknots, nu], "kff", "gain", "xref": tensors or None}; alpha [n] fp32, plan_index / state_index [n] int32, qpos / qvel
+        [nstates, ..] fp32, each or None: contiguous device tensors."""
+        dev = self.device
+        rows = 1 if options.get("final_only") else options["nknots"]
+        evals = options["nknots"] * (options["hold"] if options.get("per_substep") else 1)
+        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
+                  "ctrl": (n, max(evals, 0), self.nu)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
+        if n == 0:   # (no launch: jaco_rollout_fb returns JACO_OK for n == 0)
+            return res
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        out = _lib.JacoRolloutFbOut(*[ptr(res.get(k)) for k in shapes])
+        rec = _lib.JacoRolloutPlan(ptr(plan["ctrl"]), ptr(plan.get("kff")), ptr(plan.get("gain")), ptr(plan.get("xref")), ptr(alpha), ptr(plan_index),
+                                   int(plan["ctrl"].shape[0]))
+        opt = _lib.JacoRolloutFbOptions(**options)
+        self._chk(self.L.jaco_rollout_fb(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
+                                         None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, ptr(state_index), int(nstates),
+                                         ptr(qpos), ptr(qvel), ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p),
+                                         ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        return res
+
+    def rollout_feedback(self, ctrl, qpos=None, qvel=None, gain=None, x_ref=None, dofs=None, feedforward=None, alpha=None, plan_index=None,
+                         state_index=None, hold=1, per_substep=False, frame=None, final_only=False):
+        """rollout() in closed loop: the ctrl of knot k is computed inside the kernel from the state at knot k,
+            u = ctrl[p, k] + alpha[i] * feedforward[p, k] + gain[p, k] @ (x - x_ref[p, k]),   x = [qpos at the hinge dofs `dofs`, qvel at them]
+        (include/jaco_env.h states the exact fp32 order; the difference is not wrapped; u is clamped to ctrlrange by the actuators as any
+        ctrl is) -- the forward pass of iLQR and its line search, a plan tracked with TVLQR gains, PD tracking.  Plans: ctrl [P, T, nu],
+        gain [P, T, nu, 2 nd] with x_ref [P, T, 2 nd] and dofs (nd <= 18 hinge dofs), feedforward [P, T, nu]; each of gain and feedforward
+        may be None.  Rollout i follows plan plan_index[i] (None: plan i) from state row state_index[i] (None: row i) of qpos / qvel (as
+        rollout()) with the step alpha[i] (None: 1; needs feedforward): n is the length of whichever of plan_index, state_index and alpha
+        is given (all the same), else P.  per_substep=False: the law is evaluated at the start of a knot and held for its `hold`
+        substeps; True: before every substep, against the same knot's rows.
+        Returns rollout()'s dict plus "ctrl" [n, E, nu]: the u of every evaluation as commanded (E = T, or T * hold with per_substep),
+        all E rows also with final_only.  status: _lib.JACO_ROLLOUT_BAD_INDEX where plan_index or state_index was out of range.  One
+        launch on the current stream, no synchronisation; the sim's state is not touched."""
+        dev = self.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+        ctrl, gain, x_ref, kff, alpha = f32(ctrl), f32(gain), f32(x_ref), f32(feedforward), f32(alpha)
+        if ctrl.dim() != 3 or ctrl.shape[2] != self.nu:
+            raise ValueError("rollout_feedback: ctrl has shape %s, not [P, T, %d]" % (tuple(ctrl.shape), self.nu))
+        P, T = int(ctrl.shape[0]), int(ctrl.shape[1])
+        if kff is not None and kff.shape != ctrl.shape:
+            raise ValueError("rollout_feedback: feedforward has shape %s, not ctrl's %s" % (tuple(kff.shape), tuple(ctrl.shape)))
+        dofs = [] if dofs is None else [int(d) for d in dofs]
+        if gain is not None:
+            nx = 2 * len(dofs)
+            if not dofs:
+                raise ValueError("rollout_feedback: a gain needs dofs")
+            if gain.shape != (P, T, self.nu, nx):
+                raise ValueError("rollout_feedback: gain has shape %s, not [%d, %d, %d, %d] (2 x %d dofs)" % (tuple(gain.shape), P, T, self.nu, nx, len(dofs)))
+            if x_ref is None or x_ref.shape != (P, T, nx):
+                raise ValueError("rollout_feedback: x_ref has shape %s, not [%d, %d, %d]" % (None if x_ref is None else tuple(x_ref.shape), P, T, nx))
+        if alpha is not None and kff is None:
+            raise ValueError("rollout_feedback: alpha needs feedforward")
+        prep = lambda t, w: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, w).contiguous()
+        q, v = prep(qpos, self.nq), prep(qvel, self.nv)
+        if q is not None and v is not None and q.shape[0] != v.shape[0]:
+            raise ValueError("rollout_feedback: %d qpos rows but %d qvel rows" % (q.shape[0], v.shape[0]))
+        nstates = self.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
+        pidx, sidx = self._index(plan_index), self._index(state_index)
+        alpha = None if alpha is None else alpha.reshape(-1).contiguous()
+        counts = {k: t.numel() for k, t in (("plan_index", pidx), ("state_index", sidx), ("alpha", alpha)) if t is not None}
+        if len(set(counts.values())) > 1:
+            raise ValueError("rollout_feedback: %s" % " but ".join("%d entries of %s" % (c, k) for k, c in counts.items()))
+        n = next(iter(counts.values())) if counts else P
+        want = ("qpos", "qvel", "status", "ctrl") + (("xpos", "xmat") if frame is not None else ())
+        c = lambda t: None if t is None else t.contiguous()
+        plan = {"ctrl": ctrl.contiguous(), "kff": c(kff), "gain": c(gain), "xref": c(x_ref) if gain is not None else None}
+        return self._rollout_fb(plan, alpha, pidx, q, v, sidx, nstates, frame, want, n, nknots=T, hold=int(hold), final_only=int(bool(final_only)),
+                                per_substep=int(bool(per_substep)), dofs=dofs if gain is not None else ())
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

@@ -264,14 +264,9 @@ class BatchedMujocoConfig:
         qpos, qvel = self._spliced(q, dq)
         return self._cols(self.sim.forward_dynamics(ctrl, qpos, qvel, implicit_damping=implicit_damping), full)
 
-    def linearize(self, joints=None, ctrl=None, q=None, dq=None, **steps):
-        """(A [num_envs, 2 n, 2 n], B [num_envs, 2 n, m], c [num_envs, 2 n]) of the discrete contact-free transition of one substep on
-        the hinge joints `joints` (MJCF names; default: this config's arm), around the current state (or q / dq spliced into it) and
-        ctrl [num_envs, nu] (None: zeros):  x' ~ A x + B u + c  with the state x = [q_J, dq_J], u the ctrl words of the motor actuators
-        of those joints (in the joints' order; B.shape[-1] of them), and the integrator's order: dq' = dq + h qacc, q' = q + h dq'
-        (h the model's timestep, qacc with the implicit joint damping of the step).  The other dofs and ctrl words are held at their
-        values.  One jaco_fd launch (BatchedMujoco.linearize) plus the assembly in torch; steps: eps_qpos, eps_qvel."""
-        import torch
+    def _joint_subset(self, joints, what):
+        """(dofs, qpos addresses, motor actuators) of the hinge joints `joints` (MJCF names; default: this config's arm), the actuators in
+        the joints' order -- the x = [q_J, dq_J] and u of linearize and rollout_feedback."""
         M, names = self.table.M, self.table.names["joint"]
         if joints is None:
             dofs, qadr = list(self.arm), list(self.arm_qadr)
@@ -287,9 +282,20 @@ class BatchedMujocoConfig:
                     raise ValueError("joint %r is listed twice" % n)
                 dofs.append(int(M["jnt_dofadr"][j])); qadr.append(int(M["jnt_qposadr"][j]))
         if not dofs:
-            raise ValueError("linearize: no joint chosen")
+            raise ValueError("%s: no joint chosen" % what)
         motor = {int(M["jnt_dofadr"][int(j)]): a for a, (j, pos) in enumerate(zip(M["actuator_jntid"], M["actuator_position"])) if not pos}
-        acts = [motor[d] for d in dofs if d in motor]
+        return dofs, qadr, [motor[d] for d in dofs if d in motor]
+
+    def linearize(self, joints=None, ctrl=None, q=None, dq=None, **steps):
+        """(A [num_envs, 2 n, 2 n], B [num_envs, 2 n, m], c [num_envs, 2 n]) of the discrete contact-free transition of one substep on
+        the hinge joints `joints` (MJCF names; default: this config's arm), around the current state (or q / dq spliced into it) and
+        ctrl [num_envs, nu] (None: zeros):  x' ~ A x + B u + c  with the state x = [q_J, dq_J], u the ctrl words of the motor actuators
+        of those joints (in the joints' order; B.shape[-1] of them), and the integrator's order: dq' = dq + h qacc, q' = q + h dq'
+        (h the model's timestep, qacc with the implicit joint damping of the step).  The other dofs and ctrl words are held at their
+        values.  One jaco_fd launch (BatchedMujoco.linearize) plus the assembly in torch; steps: eps_qpos, eps_qvel."""
+        import torch
+        M = self.table.M
+        dofs, qadr, acts = self._joint_subset(joints, "linearize")
         h = float(M["opt_timestep"][0])
         qpos, qvel = self._spliced(q, dq)
         r = self.sim.linearize(ctrl, qpos, qvel, dofs=dofs, implicit_damping=True, **steps)
@@ -333,6 +339,62 @@ class BatchedMujocoConfig:
         out["status"] = r["status"].reshape(B, K)
         return {k: t[:, 0] for k, t in out.items()} if squeeze else out
 
+    def rollout_feedback(self, u, K=None, x_ref=None, k=None, alphas=None, joints=None, ctrl=None, hold=1, per_substep=False, q=None, dq=None,
+                         final_only=False):
+        """Closed-loop prediction on the joints and actuators that linearize(joints=...) uses: x = [q_J, dq_J], u the motor words of
+        those joints in the same order (m of them).  Env b follows its plan  u_t = u[b, t] + alpha k[b, t] + K[b, t] (x_t - x_ref[b, t])
+        -- u [B, T, m], K [B, T, m, 2 n] with x_ref [B, T, 2 n] (lqr_gains' sign convention), k [B, T, m]; K and k may be None -- from the
+        current state (or q / dq, arm angles / velocities spliced into it); the law is evaluated inside the kernel at the start of each
+        knot and held for `hold` substeps (per_substep=True: before every substep).  The other ctrl words are those of ctrl [B, nu]
+        (None: zeros), held over the horizon.  alphas [A]: every env runs its plan once per step size -- iLQR's line search; the A
+        rollouts of an env share its plan and its state through indices, nothing is copied.
+        {"q": [B, A, T, n_arm], "dq": likewise, "ee_pos": [B, A, T, 3], "ee_mat": [B, A, T, 9]: as rollout(); "u": [B, A, E, m]: the
+        applied motor words of every evaluation as commanded (E = T, or T * hold with per_substep; all of them also with final_only);
+        "status": [B, A]}; without alphas the A axis is squeezed.  One jaco_rollout_fb launch (BatchedMujoco.rollout_feedback); the
+        sim's state is not touched."""
+        import torch
+        B, dev, nu = self.sim.num_envs, self.sim.device, self.sim.nu
+        dofs, qadr, acts = self._joint_subset(joints, "rollout_feedback")
+        n, m = len(dofs), len(acts)
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+        u, K, x_ref, k = f32(u), f32(K), f32(x_ref), f32(k)
+        if u.dim() != 3 or u.shape[0] != B or u.shape[2] != m:
+            raise ValueError("rollout_feedback: u has shape %s, not [%d, T, %d]" % (tuple(u.shape), B, m))
+        T = int(u.shape[1])
+        if k is not None and k.shape != u.shape:
+            raise ValueError("rollout_feedback: k has shape %s, not u's %s" % (tuple(k.shape), tuple(u.shape)))
+        if K is not None:
+            if K.shape != (B, T, m, 2 * n):
+                raise ValueError("rollout_feedback: K has shape %s, not [%d, %d, %d, %d]" % (tuple(K.shape), B, T, m, 2 * n))
+            if x_ref is None or x_ref.shape != (B, T, 2 * n):
+                raise ValueError("rollout_feedback: x_ref has shape %s, not [%d, %d, %d]" % (None if x_ref is None else tuple(x_ref.shape), B, T, 2 * n))
+        if alphas is not None and k is None:
+            raise ValueError("rollout_feedback: alphas need k")
+        base = torch.zeros(B, nu, dtype=torch.float32, device=dev) if ctrl is None else f32(ctrl).reshape(B, nu)
+        full = base[:, None, :].repeat(1, T, 1)
+        full[:, :, acts] = u
+        kff = gain = None
+        if k is not None:
+            kff = torch.zeros_like(full)
+            kff[:, :, acts] = k
+        if K is not None:
+            gain = torch.zeros(B, T, nu, 2 * n, dtype=torch.float32, device=dev)
+            gain[:, :, acts] = K
+        index = alpha = None
+        A = 1
+        if alphas is not None:
+            alphas = f32(alphas).reshape(-1)
+            A = int(alphas.numel())
+            index = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(A)
+            alpha = alphas.repeat(B)
+        qpos, qvel = self._spliced(q, dq)
+        r = self.sim.rollout_feedback(full, qpos, qvel, gain=gain, x_ref=x_ref, dofs=dofs, feedforward=kff, alpha=alpha, plan_index=index, state_index=index,
+                                      hold=hold, per_substep=per_substep, frame=self._frames[0], final_only=final_only)
+        out = {"q": r["qpos"][..., self.arm_qadr], "dq": r["qvel"][..., self.arm], "ee_pos": r["xpos"], "ee_mat": r["xmat"], "u": r["ctrl"][..., acts]}
+        out = {key: t.reshape(B, A, t.shape[-2], t.shape[-1]) for key, t in out.items()}
+        out["status"] = r["status"].reshape(B, A)
+        return {key: t[:, 0] for key, t in out.items()} if alphas is None else out
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
@@ -343,6 +405,26 @@ class BatchedMujocoConfig:
         import torch
         x = torch.as_tensor(x, dtype=p.dtype, device=p.device).reshape(3)
         return p + (r["xmat"][:, i].reshape(-1, 3, 3) @ x)
+
+
+def lqr_gains(A, B, Q, R, Qf=None):
+    """K [..., T, m, nx]: the finite-horizon LQR gains of  x_{t+1} = A_t x_t + B_t u_t  (A [..., T, nx, nx], B [..., T, nx, m], as
+    linearize returns them, stacked over the knots) under the cost  sum_t (dx' Q dx + du' R du) + dx_T' Qf dx_T  (Q, Qf [nx, nx], R
+    [m, m], or batched like A; Qf None: Q), in rollout_feedback's sign convention: u = u_ref + K (x - x_ref).  The backward Riccati
+    recursion in batched torch, in the tensors' dtype."""
+    import torch
+    T = A.shape[-3]
+    Q, R = torch.as_tensor(Q, dtype=A.dtype, device=A.device), torch.as_tensor(R, dtype=A.dtype, device=A.device)
+    P = Q if Qf is None else torch.as_tensor(Qf, dtype=A.dtype, device=A.device)
+    Ks = []
+    for t in range(T - 1, -1, -1):
+        At, Bt = A[..., t, :, :], B[..., t, :, :]
+        BtP = Bt.transpose(-1, -2) @ P
+        Kt = -torch.linalg.solve(R + BtP @ Bt, BtP @ At)
+        P = Q + At.transpose(-1, -2) @ P @ (At + Bt @ Kt)
+        P = 0.5 * (P + P.transpose(-1, -2))
+        Ks.append(Kt)
+    return torch.stack(Ks[::-1], -3)
 
 
 def quat_from_euler_rxyz(e):

@@ -1,0 +1,497 @@
+"""The closed-loop rollout kernel (mujoco_jaco_amd/csrc/rollout_fb.h, jaco_rollout_fb) under the wavefront emulator (emu_rollout_fb of
+tests/emu_rollout_fb/libjaco_emu_rollout_fb{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+
+Also: the fp64 reference (the oracle with contacts disabled, the law evaluated in fp64 on the oracle's own state at each evaluation),
+the input sets -- rollout_binding's states and ctrl rows plus seeded gains and a reference trajectory -- with the conditions they must
+meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier, the refusals and a stand-in for
+BatchedMujoco.rollout_feedback backed by the emulator (CPU tests of robot_config).
+
+A tier hands the cases two calls:
+  run(model, ctrl [P, T, nu], qpos0=None, qvel0=None, kff=None, gain=None, xref=None, dofs=(), alpha=None, plan_index=None,
+      state_index=None, nstates=None, frame=None, want=OUTS, hold=1, final_only=0, per_substep=0, handle=None) -> {output: array}
+  run_open(model, ctrl [n, T, nu], qpos0, qvel0, state_index=None, frame=None, want=rollout_binding.OUTS, hold=1) -> {output: array}:
+      jaco_rollout on the same tier.
+Every output array is handed in filled with SENTINEL (status: STATUS_SENTINEL), so what a call leaves untouched shows.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import emu_binding
+import fd_binding as fb
+import ik_binding as ib
+import joint_binding as jb
+import osc_binding as ob
+import rollout_binding as rb
+from emu_binding import ROOT
+from fd_binding import bits, verr
+from mujoco_jaco_amd import _lib as product_lib
+from rollout_binding import BAD_INDEX, SENTINEL, STATUS_SENTINEL, same
+
+EMU_DIR = os.path.join(ROOT, "tests", "emu_rollout_fb")
+OUTS = ("qpos", "qvel", "xpos", "xmat", "status", "ctrl")
+STATE = ("qpos", "qvel", "status")
+_libs = {}
+
+
+def lib(layout=""):
+    """libjaco_emu_rollout_fb<layout>.so: the emulator library of that layout with the emu_rollout_fb entry (built on first use)."""
+    if layout not in _libs:
+        name = "libjaco_emu_rollout_fb%s.so" % layout
+        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
+        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.emu_rollout_fb.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.emu_last_error.restype = ctypes.c_char_p
+        _libs[layout] = L
+    return _libs[layout]
+
+
+def count(ctrl, alpha=None, plan_index=None, state_index=None, n=None):
+    """n of a call: given, or the length of whichever per-rollout array is there, or the number of plans."""
+    if n is not None:
+        return n
+    for a in (plan_index, state_index, alpha):
+        if a is not None:
+            return len(a)
+    return ctrl.shape[0]
+
+
+def shapes(n, rows, evals, nq, nv, nu):
+    return dict(rb.shapes(n, rows, nq, nv), ctrl=(n, evals, nu))
+
+
+def rollout_fb(model, ctrl, qpos0=None, qvel0=None, kff=None, gain=None, xref=None, dofs=(), alpha=None, plan_index=None, state_index=None,
+               nstates=None, frame=None, want=OUTS, hold=1, final_only=0, per_substep=0, handle=None, n=None, nknots=None, nplans=None, ndofs=None,
+               no_opt=False, no_out=False, no_ctrl=False, no_plan=False):
+    """Emulated jaco_rollout_fb: {output: array} in the C ABI's layout.  n / nknots / nplans / ndofs: override what the arrays say
+    (refusals); no_opt / no_out / no_ctrl / no_plan hand NULL pointers.  Raises ValueError with the library's message when the call is
+    refused, with the outputs it was handed in .outputs."""
+    blob, layout, nu = ob._model_info(model)
+    M = ib.load_model(model)
+    nq, nv = int(M["nq"][0]), int(M["nv"][0])
+    L = lib(layout)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+    ctrl, kff, gain, xref, alpha, q0, v0 = [f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0)]
+    pidx, sidx = i32(plan_index), i32(state_index)
+    n = count(ctrl, alpha, pidx, sidx, n)
+    nknots = ctrl.shape[1] if nknots is None else nknots
+    hq, hv = (None, None) if handle is None else (f32(handle[0]), f32(handle[1]))
+    num_envs = 0 if hq is None else hq.shape[0]
+    if nstates is None:
+        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else num_envs)
+    rows = 1 if final_only == 1 else max(nknots, 1)
+    sh = shapes(max(n, 0), rows, max(nknots, 1) * (max(hold, 1) if per_substep == 1 else 1), nq, nv, nu)
+    res = {k: rb.blank(sh[k], k == "status") for k in want}
+    p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+    out = product_lib.JacoRolloutFbOut(*[p(res.get(k)) for k in OUTS])
+    opt = product_lib.JacoRolloutFbOptions(nknots=nknots, hold=hold, final_only=final_only, per_substep=per_substep, dofs=dofs)
+    if ndofs is not None:
+        opt.ndofs = ndofs
+    plan = product_lib.JacoRolloutPlan(None if no_ctrl else p(ctrl), p(kff), p(gain), p(xref), p(alpha), p(pidx), ctrl.shape[0] if nplans is None else nplans)
+    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
+    rc = L.emu_rollout_fb(blob, len(blob), None if no_opt else cast(opt), None if frame is None else cast(frame), n, p(sidx), nstates, p(q0), p(v0),
+                          None if no_plan else cast(plan), None if no_out else cast(out), num_envs, p(hq), p(hv))
+    try:
+        emu_binding.check(L, rc, "emu_rollout_fb")
+    except ValueError as e:
+        e.outputs = res
+        raise
+    return res
+
+
+# ---- the fp64 reference
+def hinge_dofs(model):
+    """(every hinge dof of the model, their qpos addresses)."""
+    T = fb.tables(model)
+    dofs = sorted(T["hinge"])
+    return dofs, [T["hinge_qadr"][d] for d in dofs]
+
+
+def law64(ctrl, kff, alpha, gain, xref, x):
+    """The law in fp64 at the fp32 inputs, one evaluation: (u [nu], the feedback term [nu], the bound's magnitude per word
+    |ctrl| + |alpha kff| + sum_j |gain_aj| |d_j|)."""
+    c = np.asarray(ctrl, np.float64)
+    ff = np.zeros_like(c) if kff is None else float(alpha) * np.asarray(kff, np.float64)
+    if gain is None:
+        return c + ff, np.zeros_like(c), np.abs(c) + np.abs(ff)
+    G, d = np.asarray(gain, np.float64), np.asarray(x, np.float64) - np.asarray(xref, np.float64)
+    return c + ff + G @ d, G @ d, np.abs(c) + np.abs(ff) + np.abs(G) @ np.abs(d)
+
+
+def oracle_closed_loop(model, q, v, ctrl, gain=None, xref=None, dofs=(), kff=None, alpha=None, plan_index=None, state_index=None, hold=1, per_substep=0):
+    """fp64, contacts disabled, the law in fp64 on the oracle's own state at each evaluation: rollout_binding.oracle_rollout's record
+    (qpos / qvel per knot, "before" and "nefc" per substep) plus "u" [n, E, nu], the commanded ctrl of every evaluation, "usub"
+    [n, T * hold, nu], the one applied in each substep, and "fb" [n], the largest |feedback term| of any word at any evaluation."""
+    from oracle_binding import Oracle
+    o = Oracle(model)
+    o.option("disable_contact", 1)
+    T = ctrl.shape[1]
+    n = count(ctrl, alpha, plan_index, state_index)
+    T_ = fb.tables(model)
+    qadr = [T_["hinge_qadr"][d] for d in dofs]
+    E = T * (hold if per_substep else 1)
+    r = dict(qpos=np.zeros((n, T, o.nq)), qvel=np.zeros((n, T, o.nv)), before=np.zeros((n, T * hold, o.nq)), nefc=np.zeros((n, T * hold), int),
+             u=np.zeros((n, E, o.nu)), usub=np.zeros((n, T * hold, o.nu)), fb=np.zeros(n))
+    for i in range(n):
+        p = i if plan_index is None else int(plan_index[i])
+        s = i if state_index is None else int(state_index[i])
+        o.set("qpos", np.asarray(q[s], np.float64)); o.set("qvel", np.asarray(v[s], np.float64)); o.set("qacc_warmstart", np.zeros(o.nv))
+        for k in range(T):
+            for sub in range(hold):
+                if per_substep or sub == 0:
+                    x = np.concatenate([o.get("qpos")[qadr], o.get("qvel")[list(dofs)]])
+                    u, term, _ = law64(ctrl[p, k], None if kff is None else kff[p, k], 1.0 if alpha is None else alpha[i],
+                                       None if gain is None else gain[p, k], None if gain is None else xref[p, k], x)
+                    r["u"][i, k * hold + sub if per_substep else k] = u
+                    r["fb"][i] = max(r["fb"][i], np.abs(term).max())
+                r["before"][i, k * hold + sub] = o.get("qpos")
+                r["usub"][i, k * hold + sub] = u
+                o.step(u)
+                r["nefc"][i, k * hold + sub] = o.nefc
+            r["qpos"][i, k], r["qvel"][i, k] = o.get("qpos"), o.get("qvel")
+    return r
+
+
+# ---- inputs: rollout_binding's, plus gains and a reference trajectory
+DQ, DV = 0.02, 0.05     # rad, rad/s: the displacement of the start the reference trajectory is rolled out from
+KP, KV, DENSE, SERVO_SCALE = 20.0, 2.0, 0.5, 1e-4
+FB_MIN = 0.1            # every rollout's feedback term moves some ctrl word by at least this much at some knot
+_shared = {}
+
+
+def gains(model, n, T, seed=71):
+    """gain [n, T, nu, 2 nd] fp32 over every hinge dof of the model: a dense part uniform in +-DENSE plus, on the motor-driven hinge
+    dofs, a PD part on the diagonal pairs: -kp on the angle, -kv on the velocity, kp = KP (1 +- 0.1), kv = KV (1 +- 0.1), drawn per plan
+    and knot.  The rows of the fingers' position servos carry the dense part times SERVO_SCALE: a servo's force range (+-0.3 at kp = 20)
+    is 0.015 rad of command wide, so that feedback of any size on its command lands every rollout on the actuator model's knife edges,
+    which check_inputs forbids; the motor rows carry the gains in full."""
+    Tm = fb.tables(model)
+    dofs, _ = hinge_dofs(model)
+    nd, nu = len(dofs), len(Tm["dof"])
+    rng = np.random.default_rng(seed)
+    G = rng.uniform(-DENSE, DENSE, (n, T, nu, 2 * nd))
+    G[:, :, Tm["position"]] *= SERVO_SCALE
+    for a in np.flatnonzero(~Tm["position"]):
+        j = dofs.index(int(Tm["dof"][a]))
+        G[:, :, a, j] -= KP * rng.uniform(0.9, 1.1, (n, T))
+        G[:, :, a, nd + j] -= KV * rng.uniform(0.9, 1.1, (n, T))
+    return G.astype(np.float32)
+
+
+def reference_states(model, q, v, c, hold, seed=72):
+    """x_ref [n, T, 2 nd] fp32: the fp64 open-loop trajectory of the same ctrl from a start displaced by +-DQ / +-DV on every motor-driven
+    hinge dof -- what knot k's evaluation would see on it (the displaced start for k = 0, the state after knot k - 1 then).  The
+    servo-driven finger joints start where the rollout's do: the undamped proximal finger joints of the 12-hinge model swing about their
+    command at several rad/s, and a displaced swing runs out of phase by more than any servo row's force range takes."""
+    dofs, qadr = hinge_dofs(model)
+    Tm = fb.tables(model)
+    motor = np.isin(dofs, Tm["dof"][~Tm["position"]])
+    rng = np.random.default_rng(seed)
+    qd, vd = q.astype(np.float64), v.astype(np.float64)
+    qd[:, qadr] += DQ * rng.choice([-1.0, 1.0], (len(q), len(dofs))) * motor
+    vd[:, dofs] += DV * rng.choice([-1.0, 1.0], (len(q), len(dofs))) * motor
+    o = rb.oracle_rollout(model, qd, vd, c, hold)
+    x = np.concatenate([np.concatenate([qd[:, None, qadr], o["qpos"][:, :-1, qadr]], 1), np.concatenate([vd[:, None, dofs], o["qvel"][:, :-1, dofs]], 1)], 2)
+    return x.astype(np.float32)
+
+
+def shared(model, long=False):
+    """rollout_binding.shared(model, long) plus the dofs, the gains, x_ref and the fp64 closed-loop references of both modes ("ref":
+    [zero-order hold, per substep]), computed once per process, with the issue's conditions asserted on the closed loop and its
+    applied ctrl: rollout_binding.check_inputs', and a feedback term of at least FB_MIN in every rollout."""
+    key = (model, long)
+    if key not in _shared:
+        g = dict(rb.shared(model, long))
+        n, T = g["c"].shape[:2]
+        g["dofs"], g["qadr"] = hinge_dofs(model)
+        g["gain"] = gains(model, n, T)
+        g["xref"] = reference_states(model, g["q"], g["v"], g["c"], g["hold"])
+        g["ref"], g["active"] = [], []
+        for mode in ((0,) if g["hold"] == 1 else (0, 1)):
+            r = oracle_closed_loop(model, g["q"], g["v"], g["c"], g["gain"], g["xref"], g["dofs"], hold=g["hold"], per_substep=mode)
+            assert (r["fb"] >= FB_MIN).all(), (model, mode, r["fb"].min())
+            g["active"].append(rb.check_inputs(model, r["usub"], 1, r))
+            g["ref"].append(r)
+        _shared[key] = g
+    return _shared[key]
+
+
+def plan_args(g, sl=slice(None)):
+    return dict(gain=g["gain"][sl], xref=g["xref"][sl], dofs=g["dofs"])
+
+
+def kff_alpha(model, shape, seed=73):
+    """(kff [n, T, nu] fp32 uniform in +-0.3 on the motor words, zero on the servos'; alpha [n] fp32 uniform in 0.25 .. 1)."""
+    rng = np.random.default_rng(seed)
+    k = rng.uniform(-0.3, 0.3, shape) * ~fb.tables(model)["position"]
+    return k.astype(np.float32), rng.uniform(0.25, 1.0, shape[0]).astype(np.float32)
+
+
+# ---- the cases.  Each returns what it measured, or asserts bit-equality itself.
+def case_degenerate(run, run_open, model, long=False):
+    """Case 1: without gain, kff and plan_idx the closed-loop entry is jaco_rollout: qpos, qvel, pose and status bit for bit, and the ctrl
+    output is the ctrl handed in."""
+    g = rb.shared(model, long)
+    ee = rb.frames(model)[1]
+    r = run(model, g["c"], g["q"], g["v"], frame=ee, hold=g["hold"])
+    same(run_open(model, g["c"], g["q"], g["v"], frame=ee, hold=g["hold"]), r, rb.OUTS)
+    assert (bits(r["ctrl"]) == bits(g["c"])).all()
+
+
+def closed(run, model, per_substep=0, long=False):
+    """The closed-loop call on shared(model, long) in one mode, made once per tier (kept on the tier's `run`): cases 2 and 4 read it."""
+    memo = run.__dict__.setdefault("_closed", {})
+    key = (model, per_substep, long)
+    if key not in memo:
+        g = shared(model, long)
+        memo[key] = run(model, g["c"], g["q"], g["v"], hold=g["hold"], per_substep=per_substep, want=STATE + ("ctrl",), **plan_args(g))
+    return memo[key]
+
+
+def case_own_commands(run, run_open, model, per_substep, long=False):
+    """Case 2: a closed loop is an open loop on its own commands -- feeding the returned ctrl to jaco_rollout from the same states
+    reproduces qpos, qvel and status bit for bit (per_substep: nknots * hold knots of hold 1, rows hold-1, 2 hold-1 ...)."""
+    g = shared(model, long)
+    hold = g["hold"]
+    r = closed(run, model, per_substep, long)
+    assert (r["status"] == 0).all() and not (bits(r["ctrl"]) == bits(g["c"] if not per_substep else np.repeat(g["c"], hold, 1))).all()
+    if per_substep:
+        o = run_open(model, r["ctrl"], g["q"], g["v"], want=STATE, hold=1)
+        o = {k: (x if k == "status" else x[:, hold - 1::hold]) for k, x in o.items()}
+    else:
+        o = run_open(model, r["ctrl"], g["q"], g["v"], want=STATE, hold=hold)
+    same(o, r, STATE)
+
+
+def law_bound(nx, mag):
+    """Case 3's bound per word, derived: u is nx + 1 fused multiply-adds, each rounding a partial sum no larger than `mag` = |ctrl| +
+    |alpha kff| + sum |gain| |d| (up to its own roundings) to half a unit in the last place, 2^-24 relative; the one subtraction that
+    forms d_j is another 2^-24 |d_j| under |gain_aj|; the partial sums' own growth by (1 + 2^-24)^nx is covered by the + 3."""
+    return (nx + 3) * 2.0 ** -24 * mag
+
+
+def case_law(run, model, long=False):
+    """Case 3: the returned ctrl against the law recomputed in fp64 from the fp32 inputs and the returned state rows (knot 0 sees the
+    initial state, knot k row k - 1), with kff and alpha in; per_substep = 0.  Returns the largest |u - u_ref| / bound over all words."""
+    g = shared(model, long)
+    n, T = g["c"].shape[:2]
+    kff, alpha = kff_alpha(model, g["c"].shape)
+    r = run(model, g["c"], g["q"], g["v"], kff=kff, alpha=alpha, hold=g["hold"], want=STATE + ("ctrl",), **plan_args(g))
+    assert (r["status"] == 0).all()
+    worst, nx = 0.0, 2 * len(g["dofs"])
+    for i in range(n):
+        for k in range(T):
+            qk, vk = (g["q"][i], g["v"][i]) if k == 0 else (r["qpos"][i, k - 1], r["qvel"][i, k - 1])
+            u, _, mag = law64(g["c"][i, k], kff[i, k], alpha[i], g["gain"][i, k], g["xref"][i, k], np.concatenate([qk[g["qadr"]], vk[g["dofs"]]]))
+            worst = max(worst, float((np.abs(r["ctrl"][i, k].astype(np.float64) - u) / law_bound(nx, mag)).max()))
+    return worst
+
+
+def case_oracle(run, model, per_substep=0, long=False):
+    """Case 4: every knot's qpos and qvel, and the commanded ctrl, of the closed loop against the fp64 closed loop.  Returns (qpos
+    measure, qvel measure, ctrl measure, the call's result)."""
+    g = shared(model, long)
+    ref = g["ref"][per_substep]
+    r = closed(run, model, per_substep, long)
+    assert (r["status"] == 0).all(), r["status"]
+    return verr(r["qpos"], ref["qpos"]), verr(r["qvel"], ref["qvel"]), verr(r["ctrl"], ref["u"]), r
+
+
+def case_zero_deviation(run, run_open, model, long=False):
+    """Case 5: x_ref = the rollout's own open-loop states (the start for knot 0, row k - 1 then), finite random gains, kff given with
+    alpha = 0, per_substep = 0: bit for bit the open-loop rollout, and the ctrl output the ctrl handed in."""
+    g = shared(model, long)
+    o = run_open(model, g["c"], g["q"], g["v"], want=STATE, hold=g["hold"])
+    dofs, qadr = g["dofs"], g["qadr"]
+    xref = np.concatenate([np.concatenate([g["q"][:, None, qadr], o["qpos"][:, :-1, qadr]], 1), np.concatenate([g["v"][:, None, dofs], o["qvel"][:, :-1, dofs]], 1)], 2)
+    kff, _ = kff_alpha(model, g["c"].shape)
+    r = run(model, g["c"], g["q"], g["v"], kff=kff, alpha=np.zeros(len(g["c"]), np.float32), gain=g["gain"], xref=xref, dofs=dofs, hold=g["hold"],
+            want=STATE + ("ctrl",))
+    same(o, r, STATE)
+    assert (bits(r["ctrl"]) == bits(g["c"])).all()
+
+
+FAN = (3, 4, 2)   # plans x alphas x states
+
+
+def case_fan_out(run, model=rb.MODEL):
+    """Case 6: 3 plans x 4 alphas x 2 states through plan_idx, alpha and state_idx against the same rollouts with materialised
+    per-rollout plans and states, bit for bit; shuffling the rollouts permutes the rows.  Both modes."""
+    g = shared(model)
+    P, A, S = FAN
+    kff, _ = kff_alpha(model, g["c"].shape)
+    pi, ai, si = [x.reshape(-1) for x in np.meshgrid(np.arange(P), np.arange(A), np.arange(S), indexing="ij")]
+    alpha = np.array([0.0, 0.25, 0.5, 1.0], np.float32)[ai]
+    ee = rb.frames(model)[1]
+    for mode in (0, 1):
+        k = dict(frame=ee, hold=g["hold"], per_substep=mode, dofs=g["dofs"])
+        r = run(model, g["c"][:P], g["q"][:S], g["v"][:S], kff=kff[:P], gain=g["gain"][:P], xref=g["xref"][:P], alpha=alpha, plan_index=pi, state_index=si, **k)
+        assert (r["status"] == 0).all() and len(np.unique(bits(r["qpos"][:, -1]), axis=0)) == P * A * S
+        m = run(model, g["c"][pi], g["q"][si], g["v"][si], kff=kff[pi], gain=g["gain"][pi], xref=g["xref"][pi], alpha=alpha, **k)
+        same(r, m)
+        perm = np.random.default_rng(5).permutation(len(pi))
+        s = run(model, g["c"][:P], g["q"][:S], g["v"][:S], kff=kff[:P], gain=g["gain"][:P], xref=g["xref"][:P], alpha=alpha[perm], plan_index=pi[perm],
+                state_index=si[perm], **k)
+        same(s, {key: x[perm] for key, x in r.items()})
+
+
+def case_bad_index(run, model=rb.MODEL):
+    """Case 7: plan_idx and state_idx entries -1 and one past the end among valid ones: JACO_ROLLOUT_BAD_INDEX in their status words,
+    their rows untouched (ctrl included), every other rollout bitwise what it is without the bad entries."""
+    g = shared(model)
+    m, P, ee = 7, 4, rb.frames(model)[1]
+    sidx = np.array([0, 3, -1, 6, m, 2, 2, 5, 1, 4], np.int32)
+    pidx = np.array([0, 1, 2, P, 3, -1, 2, 0, 3, 1], np.int32)
+    bad = (sidx < 0) | (sidx >= m) | (pidx < 0) | (pidx >= P)
+    assert bad.sum() == 4
+    k = dict(frame=ee, hold=g["hold"], gain=g["gain"][:P], xref=g["xref"][:P], dofs=g["dofs"])
+    r = run(model, g["c"][:P], g["q"][:m], g["v"][:m], plan_index=pidx, state_index=sidx, **k)
+    ok = run(model, g["c"][:P], g["q"][:m], g["v"][:m], plan_index=pidx[~bad], state_index=sidx[~bad], **k)
+    assert (r["status"][bad] == BAD_INDEX).all() and (r["status"][~bad] == 0).all()
+    for key in OUTS:
+        if key != "status":
+            assert (bits(r[key][bad]) == bits(np.float32(SENTINEL))).all(), key
+            assert (bits(r[key][~bad]) == bits(ok[key])).all(), key
+
+
+# ---- the refusals: one argument set per JACO_EINVAL case of include/jaco_env.h, for the emulator's entry and the library's alike
+REFUSAL_MODEL = rb.REFUSAL_MODEL   # dofs 0-8 hinges, 9-20 free joints
+REFUSALS = {k: v for k, v in rb.REFUSALS.items() if k != "status_only"}   # (here status alone is an output)
+REFUSALS.update({
+    "no_outputs": "at least one of the outputs qpos, qvel, xpos, xmat, status and ctrl is required",
+    "null_plan": "the plan is required",
+    "nplans_0": "nplans 0: at least one plan is required",
+    "n_beyond_nplans": "n 4 rollouts from 3 plans without a plan index",
+    "gain_without_xref": "a gain needs xref",
+    "alpha_without_kff": "alpha needs kff",
+    "per_substep_2": "per_substep must be 0 or 1",
+    "ndofs_0": "ndofs 0 outside [1, 18]",
+    "ndofs_19": "ndofs 19 outside [1, 18]",
+    "dof_negative": "dof -1 outside [0, 21)",
+    "dof_beyond_nv": "dof 21 outside [0, 21)",
+    "dof_free": "dof 9 belongs to a free joint",
+    "dof_twice": "dof 4 is listed twice",
+})
+
+
+def refusal_args(case):
+    """Keyword arguments of one refused call of `rollout_fb` / the GPU tier's twin on REFUSAL_MODEL: REFUSAL_N plans of 2 knots."""
+    if case in rb.REFUSALS:
+        return dict(rb.refusal_args(case), want=rb.refusal_args(case)["want"] + ("ctrl",))
+    g = shared(REFUSAL_MODEL)
+    n = rb.REFUSAL_N
+    k = dict(ctrl=g["c"][:n, :2], qpos0=g["q"][:n], qvel0=g["v"][:n], want=("qpos", "status", "ctrl"))
+    G, X = g["gain"][:n, :2], g["xref"][:n, :2]
+    fed = lambda dofs: dict(gain=np.ascontiguousarray(G[..., :2 * len(dofs)]), xref=np.ascontiguousarray(X[..., :2 * len(dofs)]), dofs=dofs)
+    k.update({"no_outputs": dict(want=()), "null_plan": dict(no_plan=True), "nplans_0": dict(nplans=0),
+              "n_beyond_nplans": dict(ctrl=g["c"][:3, :2], n=n), "gain_without_xref": dict(gain=G, dofs=g["dofs"]),
+              "alpha_without_kff": dict(alpha=np.ones(n, np.float32)), "per_substep_2": dict(per_substep=2),
+              "ndofs_0": dict(gain=G, xref=X, dofs=()), "ndofs_19": dict(gain=G, xref=X, dofs=g["dofs"], ndofs=19),
+              "dof_negative": fed([0, -1, 2]), "dof_beyond_nv": fed([0, 21]), "dof_free": fed([3, 9]), "dof_twice": fed([4, 1, 4])}[case])
+    return k
+
+
+# ---- case 10: the robot_config tier.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or EmuFbSim.
+HOLD_MODELS = {"jaco2_reaching_torque": "EE", "jaco2_dual_torque": "EE_1"}
+HOLD_B, HOLD_OFF, HOLD_HORIZON, HOLD_KNOTS, HOLD_SUBSTEPS = 4, 0.05, 12, 40, 5
+HOLD_Q, HOLD_QV, HOLD_R = 1e4, 10.0, 1e-3  # LQR weights: joint angles, joint velocities, torques
+
+
+def hold_postures(model):
+    """(qpos [HOLD_B, nq], qvel zeros): the model's first reset states with the arm at rest."""
+    q, v = ob.states(model, HOLD_B)
+    return q.astype(np.float32), np.zeros_like(v, dtype=np.float32)
+
+
+def case_hold_posture(make_sim, model):
+    """Case 10: hold a posture with rollout_feedback + linearize + lqr_gains.  u_ref = joint().gravity_compensation() at the posture, the
+    gains from the linearisation there over a 12-knot horizon, run over 40 knots (the last gain held) of 5 substeps with the law
+    evaluated every substep, from HOLD_OFF rad off on every joint of the arm.  Asserted, first on an fp64 restatement (the oracle's
+    closed loop with the same fp32 plan) and then on the result: the joint deviation at the last knot is smaller than at the start
+    and smaller than that of the same rollout without gains.  Returns the first knot's |u - (u_ref + K (x0 - x_ref))| / case 3's bound."""
+    import torch
+    from mujoco_jaco_amd.robot_config import BatchedMujocoConfig, lqr_gains
+    ee = HOLD_MODELS[model]
+    q, v = hold_postures(model)
+    sim = make_sim(model, q, v)
+    cfg = BatchedMujocoConfig(sim, ee=ee)
+    arm, qadr = list(cfg.arm), list(cfg.arm_qadr)
+    n = len(arm)
+    ubar_full = cfg.joint(joints=None).gravity_compensation()
+    A, Bm, _ = cfg.linearize(ctrl=ubar_full)
+    Tm = fb.tables(model)
+    acts = [int(np.flatnonzero(Tm["dof"] == d)[0]) for d in arm]
+    m = len(acts)
+    assert A.shape == (HOLD_B, 2 * n, 2 * n) and Bm.shape == (HOLD_B, 2 * n, m)
+    Q = torch.diag(torch.tensor([HOLD_Q] * n + [HOLD_QV] * n, dtype=torch.float64))
+    R = HOLD_R * torch.eye(m, dtype=torch.float64)
+    K12 = lqr_gains(A.double()[:, None].expand(-1, HOLD_HORIZON, -1, -1), Bm.double()[:, None].expand(-1, HOLD_HORIZON, -1, -1), Q, R, Q)
+    assert K12.shape == (HOLD_B, HOLD_HORIZON, m, 2 * n)
+    K = torch.cat([K12, K12[:, -1:].expand(-1, HOLD_KNOTS - HOLD_HORIZON, -1, -1)], 1).float().to(sim.device)
+    ubar = ubar_full[:, acts]
+    u = ubar[:, None].expand(-1, HOLD_KNOTS, -1).contiguous()
+    xbar = torch.cat([torch.as_tensor(q[:, qadr]), torch.as_tensor(v[:, arm])], 1).to(sim.device)
+    x_ref = xbar[:, None].expand(-1, HOLD_KNOTS, -1).contiguous()
+    q0 = torch.as_tensor(q[:, qadr] + np.float32(HOLD_OFF)).to(sim.device)
+    k = dict(ctrl=ubar_full, hold=HOLD_SUBSTEPS, per_substep=True, q=q0)
+    # the fp64 restatement: the same fp32 plan on the oracle
+    N = lambda t: t.cpu().numpy()
+    full = np.repeat(N(ubar_full)[:, None], HOLD_KNOTS, 1)
+    G = np.zeros((HOLD_B, HOLD_KNOTS, full.shape[2], 2 * n), np.float32)
+    G[:, :, acts] = N(K)
+    qs = q.copy()
+    qs[:, qadr] = N(q0)
+    dev = lambda Qk: np.abs(Qk[:, qadr].astype(np.float64) - q[:, qadr]).max(1)
+    o1 = oracle_closed_loop(model, qs, v, full, G, N(x_ref), arm, hold=HOLD_SUBSTEPS, per_substep=1)
+    o0 = oracle_closed_loop(model, qs, v, full, hold=HOLD_SUBSTEPS)
+    assert (dev(o1["qpos"][:, -1]) < dev(qs)).all() and (dev(o1["qpos"][:, -1]) < dev(o0["qpos"][:, -1])).all(), (dev(o1["qpos"][:, -1]), dev(o0["qpos"][:, -1]))
+    # the product
+    r = cfg.rollout_feedback(u, K=K, x_ref=x_ref, **k)
+    r0 = cfg.rollout_feedback(u, **k)
+    E = HOLD_KNOTS * HOLD_SUBSTEPS
+    assert r["q"].shape == (HOLD_B, HOLD_KNOTS, n) and r["dq"].shape == (HOLD_B, HOLD_KNOTS, n) and r["u"].shape == (HOLD_B, E, m)
+    assert r["ee_pos"].shape == (HOLD_B, HOLD_KNOTS, 3) and r["ee_mat"].shape == (HOLD_B, HOLD_KNOTS, 9) and r["status"].shape == (HOLD_B,)
+    assert (N(r["status"]) == 0).all() and (N(r0["status"]) == 0).all()
+    last, last0 = [np.abs(N(t["q"])[:, -1].astype(np.float64) - q[:, qadr]).max(1) for t in (r, r0)]
+    assert (last < HOLD_OFF).all() and (last < last0).all(), (last, last0)
+    assert (bits(N(r0["u"])) == bits(N(ubar)[:, None])).all()
+    # the first evaluation, and the line search's fan-out: alpha = 0 reproduces the plain plan, every alpha shares plan and state
+    x0 = np.concatenate([N(q0), v[:, arm]], 1)
+    worst = 0.0
+    for b in range(HOLD_B):
+        uu, _, mag = law64(N(ubar)[b], None, 1.0, N(K)[b, 0], N(x_ref)[b, 0], x0[b])
+        worst = max(worst, float((np.abs(N(r["u"])[b, 0].astype(np.float64) - uu) / law_bound(2 * n, mag)).max()))
+    kk = torch.full_like(u, 0.125)
+    ra = cfg.rollout_feedback(u, K=K, x_ref=x_ref, k=kk, alphas=[0.0, 0.5, 1.0], final_only=True, **k)
+    assert ra["q"].shape == (HOLD_B, 3, 1, n) and ra["u"].shape == (HOLD_B, 3, E, m) and ra["status"].shape == (HOLD_B, 3)
+    assert (bits(N(ra["q"])[:, 0, 0]) == bits(N(r["q"])[:, -1])).all() and (bits(N(ra["u"])[:, 0]) == bits(N(r["u"]))).all()
+    assert not (bits(N(ra["u"])[:, 1]) == bits(N(ra["u"])[:, 2])).all()
+    return worst
+
+
+class EmuFbSim(rb.EmuRolloutSim):
+    """EmuRolloutSim plus BatchedMujoco.joint and BatchedMujoco.rollout_feedback on the emulator (CPU tensors), the latter through the
+    product's own method: only the one launch (_rollout_fb) is replaced."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.calls, self.launches_rollout_fb = [], 0
+
+    joint = jb.EmuJointSim.joint
+
+    def _rollout_fb(self, plan, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        import torch
+        N = lambda t: None if t is None else t.numpy()
+        self.launches_rollout_fb += 1
+        r = rollout_fb(self.model, N(plan["ctrl"]), N(qpos), N(qvel), N(plan.get("kff")), N(plan.get("gain")), N(plan.get("xref")), options["dofs"],
+                       N(alpha), N(plan_index), N(state_index), nstates, frame, tuple(want), options["hold"], options["final_only"],
+                       options["per_substep"], handle=(self.qpos.numpy(), self.qvel.numpy()), n=n)
+        return {k: torch.from_numpy(x.view(np.int32) if k == "status" else x) for k, x in r.items()}
+
+    from mujoco_jaco_amd.physics import BatchedMujoco as _B
+    rollout_feedback = _B.rollout_feedback
+    del _B
