@@ -15,6 +15,7 @@
 #include "physics_kernel.h"
 #include "snapshot.h"
 #include "abi_agreement.h"
+#include "entry_args.h"
 
 // the physics kernels live in their own translation units (kernels.hip, one per kernel)
 typedef void JacoLauncher(unsigned grid, hipStream_t st, const JacoStepArgs& A);
@@ -934,178 +935,110 @@ extern "C" int jaco_step_time_ms(JacoHandle* h, double* avg_ms) {
   return event_mean(h, h->events, avg_ms);
 }
 
-// ---- robot-configuration queries (query.h): one wavefront per env, nothing of the handle written --------------------------------
+// ---- the query-style entries: one wavefront per env (per rollout), nothing of the handle written.  From the arguments to the kernel's
+// block, every check included, is jaco_<entry>_bind of entry_args.h (shared with the CPU tests' host build); what is left here is the
+// handle: its state rows as the fall-back, the refusal into jaco_last_error, the model's device copy and the launch.
+static bool refused(JacoHandle* h, const std::string& why) {
+  if (!why.empty()) h->err = why;
+  return !why.empty();
+}
+template <class Args>
+static int launch_entry(JacoHandle* h, void (*launch)(unsigned, hipStream_t, const Args&), int grid, void* stream, const Args& Q) {
+  ENTER(h);
+  launch((unsigned)grid, (hipStream_t)stream, Q);
+  h->nlaunch++;
+  HIPCHK(h, hipGetLastError());
+  return JACO_OK;
+}
+
+// robot-configuration queries (query.h)
 extern "C" int jaco_query(JacoHandle* h, const JacoFrame* frames_host, int nframes, const float* qpos_dev, const float* qvel_dev,
                           const JacoQueryOut* out, void* stream) {
   if (!h) return JACO_EINVAL;
-  JacoQueryArgs Q{};
-  const std::string why = jaco_query_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, &Q);
-  if (!why.empty()) { h->err = "jaco_query: " + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoQueryArgs Q;
+  if (refused(h, jaco_query_bind(h->model_host, frames_host, nframes, qpos_dev, qvel_dev, out, h->num_envs, h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
   Q.model = h->model_dev;
-  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
-  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
-  if (out) { Q.xpos = out->xpos; Q.xmat = out->xmat; Q.jac = out->jac; Q.qM = out->qM; Q.bias = out->qfrc_bias; }
-  Q.nenv = h->num_envs;
-  jaco_launch_query((unsigned)h->num_envs, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_query, h->num_envs, stream, Q);
 }
 
-// ---- inverse kinematics (ik.h): one wavefront per env, nothing of the handle written ---------------------------------------------
+// inverse kinematics (ik.h)
 extern "C" int jaco_ik(JacoHandle* h, const JacoFrame* frame_host, const JacoIkOptions* opt_host, const float* qpos_seed_dev,
                        const float* target_pos_dev, const float* target_quat_dev, float* qpos_out_dev, float* resid_dev, int32_t* status_dev, void* stream) {
   if (!h) return JACO_EINVAL;
-  if (!frame_host || !target_pos_dev || !qpos_out_dev) { h->err = "jaco_ik: the frame, the target positions and the output qpos are required"; return JACO_EINVAL; }
-  const JacoIkOptions defaults = JACO_IK_DEFAULTS;
-  JacoIkArgs Q{};
-  memcpy(&Q.fr, frame_host, sizeof(JacoFrame));
-  memcpy(&Q.opt, opt_host ? opt_host : &defaults, sizeof(JacoIkOptions));
-  if (const char* why = jaco_ik_resolve(h->model_host, Q.fr, Q.opt, &Q.active)) { h->err = std::string("jaco_ik: ") + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoIkArgs Q;
+  if (refused(h, jaco_ik_bind(h->model_host, frame_host, opt_host, qpos_seed_dev, target_pos_dev, target_quat_dev, qpos_out_dev, resid_dev, status_dev, h->num_envs,
+                              h->env.qpos, &Q))) return JACO_EINVAL;
   Q.model = h->model_dev;
-  Q.qpos = qpos_seed_dev ? qpos_seed_dev : h->env.qpos;
-  Q.target_pos = target_pos_dev; Q.target_quat = target_quat_dev;
-  Q.qpos_out = qpos_out_dev; Q.resid = resid_dev; Q.status = status_dev;
-  Q.nenv = h->num_envs;
-  jaco_launch_ik((unsigned)h->num_envs, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_ik, h->num_envs, stream, Q);
 }
 
-// ---- operational-space controller (osc.h): one wavefront per env, nothing of the handle written -----------------------------------
+// operational-space controller (osc.h)
 extern "C" int jaco_osc(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const float* qpos_dev,
                         const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev, const float* ctrl_in_dev, float* ctrl_out_dev,
                         int32_t* status_dev, void* stream) {
   if (!h) return JACO_EINVAL;
-  const JacoOscOptions defaults = JACO_OSC_DEFAULTS;
-  JacoOscOpts opt;
-  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoOscOptions));
-  JacoOscArgs Q{};
-  Q.target_pos = target_pos_dev; Q.target_quat = target_quat_dev; Q.ctrl_in = ctrl_in_dev; Q.ctrl_out = ctrl_out_dev; Q.status = status_dev;
-  const std::string why = jaco_osc_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, opt, &Q);
-  if (!why.empty()) { h->err = "jaco_osc: " + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoOscArgs Q;
+  if (refused(h, jaco_osc_bind(h->model_host, frames_host, nframes, opt_host, qpos_dev, qvel_dev, target_pos_dev, target_quat_dev, ctrl_in_dev, ctrl_out_dev, status_dev,
+                               h->num_envs, h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
   Q.model = h->model_dev;
-  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
-  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
-  Q.nenv = h->num_envs;
-  jaco_launch_osc((unsigned)h->num_envs, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_osc, h->num_envs, stream, Q);
 }
 
-// ---- ... on task axes, with null-space terms (osc_task.h): task_host NULL is jaco_osc itself -------------------------------------
+// ... on task axes, with null-space terms (osc_task.h): task_host NULL is jaco_osc itself
 extern "C" int jaco_osc_task(JacoHandle* h, const JacoFrame* frames_host, int nframes, const JacoOscOptions* opt_host, const JacoOscTask* task_host,
                              const float* qpos_dev, const float* qvel_dev, const float* target_pos_dev, const float* target_quat_dev,
                              const float* rest_qpos_dev, const float* ctrl_in_dev, float* ctrl_out_dev, int32_t* status_dev, void* stream) {
   if (!task_host) return jaco_osc(h, frames_host, nframes, opt_host, qpos_dev, qvel_dev, target_pos_dev, target_quat_dev, ctrl_in_dev, ctrl_out_dev, status_dev, stream);
   if (!h) return JACO_EINVAL;
-  const JacoOscOptions defaults = JACO_OSC_DEFAULTS;
-  JacoOscOpts opt;
-  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoOscOptions));
-  JacoOscTaskOpts task;
-  memcpy(&task, task_host, sizeof(JacoOscTask));
-  JacoOscTaskArgs T{};
-  T.o.target_pos = target_pos_dev; T.o.target_quat = target_quat_dev; T.o.ctrl_in = ctrl_in_dev; T.o.ctrl_out = ctrl_out_dev; T.o.status = status_dev;
-  T.rest_qpos = rest_qpos_dev;
-  const std::string why = jaco_osc_task_resolve(h->model_host, reinterpret_cast<const JacoQueryFrame*>(frames_host), nframes, opt, task, &T);
-  if (!why.empty()) { h->err = "jaco_osc_task: " + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoOscTaskArgs T;
+  if (refused(h, jaco_osc_task_bind(h->model_host, frames_host, nframes, opt_host, task_host, qpos_dev, qvel_dev, target_pos_dev, target_quat_dev, rest_qpos_dev,
+                                    ctrl_in_dev, ctrl_out_dev, status_dev, h->num_envs, h->env.qpos, h->env.qvel, &T))) return JACO_EINVAL;
   T.o.model = h->model_dev;
-  T.o.qpos = qpos_dev ? qpos_dev : h->env.qpos;
-  T.o.qvel = qvel_dev ? qvel_dev : h->env.qvel;
-  T.o.nenv = h->num_envs;
-  jaco_launch_osc_task((unsigned)h->num_envs, (hipStream_t)stream, T);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_osc_task, h->num_envs, stream, T);
 }
 
-// ---- joint-space controller and inverse dynamics (joint.h): one wavefront per env, nothing of the handle written -------------------
+// joint-space controller and inverse dynamics (joint.h)
 extern "C" int jaco_joint(JacoHandle* h, const JacoJointOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* target_qpos_dev,
                           const float* target_qvel_dev, const float* qacc_ff_dev, const float* ctrl_in_dev, float* ctrl_out_dev, void* stream) {
   if (!h) return JACO_EINVAL;
-  const JacoJointOptions defaults = JACO_JOINT_DEFAULTS;
-  JacoJointOpts opt;
-  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoJointOptions));
-  JacoJointArgs Q{};
-  Q.target_qpos = target_qpos_dev; Q.target_qvel = target_qvel_dev; Q.qacc_ff = qacc_ff_dev; Q.ctrl_in = ctrl_in_dev; Q.ctrl_out = ctrl_out_dev;
-  const std::string why = jaco_joint_resolve(h->model_host, opt, &Q);
-  if (!why.empty()) { h->err = "jaco_joint: " + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoJointArgs Q;
+  if (refused(h, jaco_joint_bind(h->model_host, opt_host, qpos_dev, qvel_dev, target_qpos_dev, target_qvel_dev, qacc_ff_dev, ctrl_in_dev, ctrl_out_dev, h->num_envs,
+                                 h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
   Q.model = h->model_dev;
-  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
-  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
-  Q.nenv = h->num_envs;
-  jaco_launch_joint((unsigned)h->num_envs, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_joint, h->num_envs, stream, Q);
 }
 
-// ---- forward dynamics and its linearisation (fd.h): one wavefront per env, nothing of the handle written ----------------------------
+// forward dynamics and its linearisation (fd.h)
 extern "C" int jaco_fd(JacoHandle* h, const JacoFdOptions* opt_host, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
                        const JacoFdOut* out, void* stream) {
   if (!h) return JACO_EINVAL;
-  const JacoFdOptions defaults = JACO_FD_DEFAULTS;
-  JacoFdOpts opt;
-  memcpy(&opt, opt_host ? opt_host : &defaults, sizeof(JacoFdOptions));
-  JacoFdArgs Q{};
-  if (out) { Q.qacc = out->qacc; Q.qfrc_smooth = out->qfrc_smooth; Q.dqacc_dqpos = out->dqacc_dqpos; Q.dqacc_dqvel = out->dqacc_dqvel; Q.dqacc_dctrl = out->dqacc_dctrl; }
-  const std::string why = jaco_fd_resolve(h->model_host, opt, out != nullptr, &Q);
-  if (!why.empty()) { h->err = "jaco_fd: " + why; return JACO_EINVAL; }
-  ENTER(h);
+  JacoFdArgs Q;
+  if (refused(h, jaco_fd_bind(h->model_host, opt_host, qpos_dev, qvel_dev, ctrl_dev, out, h->num_envs, h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
   Q.model = h->model_dev;
-  Q.qpos = qpos_dev ? qpos_dev : h->env.qpos;
-  Q.qvel = qvel_dev ? qvel_dev : h->env.qvel;
-  Q.ctrl = ctrl_dev;
-  Q.nenv = h->num_envs;
-  jaco_launch_fd((unsigned)h->num_envs, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_fd, h->num_envs, stream, Q);
 }
 
-// ---- open-loop rollouts (rollout.h): one wavefront per rollout, the whole knot x hold loop in one launch, nothing of the handle written ----
+// open-loop rollouts (rollout.h): the whole knot x hold loop in one launch
 extern "C" int jaco_rollout(JacoHandle* h, const JacoRolloutOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
                             const float* qpos0_dev, const float* qvel0_dev, const float* ctrl_dev, const JacoRolloutOut* out, void* stream) {
   if (!h) return JACO_EINVAL;
-  JacoRolloutArgs Q{};
-  Q.state_idx = state_idx_dev; Q.qpos0 = qpos0_dev; Q.qvel0 = qvel0_dev; Q.ctrl = ctrl_dev;
-  if (out) { Q.qpos = out->qpos; Q.qvel = out->qvel; Q.xpos = out->xpos; Q.xmat = out->xmat; Q.status = out->status; }
-  const std::string why = jaco_rollout_resolve(h->model_host, reinterpret_cast<const JacoRolloutOpts*>(opt_host), reinterpret_cast<const JacoQueryFrame*>(frame_host), n,
-                                               nstates, h->num_envs, out != nullptr, &Q);
-  if (!why.empty()) { h->err = "jaco_rollout: " + why; return JACO_EINVAL; }
+  JacoRolloutArgs Q;
+  if (refused(h, jaco_rollout_bind(h->model_host, opt_host, frame_host, n, state_idx_dev, nstates, qpos0_dev, qvel0_dev, ctrl_dev, out, h->num_envs, h->env.qpos,
+                                   h->env.qvel, &Q))) return JACO_EINVAL;
   if (n == 0) return JACO_OK;
-  ENTER(h);
   Q.model = h->model_dev;
-  if (!Q.qpos0) { Q.qpos0 = h->env.qpos; Q.qvel0 = h->env.qvel; }
-  jaco_launch_rollout((unsigned)n, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_rollout, n, stream, Q);
 }
 
-// ---- closed-loop rollouts (rollout_fb.h): jaco_rollout with the feedback law evaluated inside the kernel, nothing of the handle written ----
+// closed-loop rollouts (rollout_fb.h): jaco_rollout with the feedback law evaluated inside the kernel
 extern "C" int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
                                const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutFbOut* out, void* stream) {
   if (!h) return JACO_EINVAL;
-  JacoRolloutFbArgs Q{};
-  Q.R.state_idx = state_idx_dev; Q.R.qpos0 = qpos0_dev; Q.R.qvel0 = qvel0_dev;
-  if (out) { Q.R.qpos = out->qpos; Q.R.qvel = out->qvel; Q.R.xpos = out->xpos; Q.R.xmat = out->xmat; Q.R.status = out->status; Q.ctrl_out = out->ctrl; }
-  const std::string why = jaco_rollout_fb_resolve(h->model_host, reinterpret_cast<const JacoRolloutFbOpts*>(opt_host), reinterpret_cast<const JacoQueryFrame*>(frame_host), n,
-                                                  nstates, h->num_envs, reinterpret_cast<const JacoRolloutFbPlan*>(plan_host), out != nullptr, &Q);
-  if (!why.empty()) { h->err = "jaco_rollout_fb: " + why; return JACO_EINVAL; }
+  JacoRolloutFbArgs Q;
+  if (refused(h, jaco_rollout_fb_bind(h->model_host, opt_host, frame_host, n, state_idx_dev, nstates, qpos0_dev, qvel0_dev, plan_host, out, h->num_envs, h->env.qpos,
+                                      h->env.qvel, &Q))) return JACO_EINVAL;
   if (n == 0) return JACO_OK;
-  ENTER(h);
   Q.R.model = h->model_dev;
-  if (!Q.R.qpos0) { Q.R.qpos0 = h->env.qpos; Q.R.qvel0 = h->env.qvel; }
-  jaco_launch_rollout_fb((unsigned)n, (hipStream_t)stream, Q);
-  h->nlaunch++;
-  HIPCHK(h, hipGetLastError());
-  return JACO_OK;
+  return launch_entry(h, jaco_launch_rollout_fb, n, stream, Q);
 }
+

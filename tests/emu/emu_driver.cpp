@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE: runs the unmodified kernel source under the lockstep wavefront emulator.
 // Built by tests/emu/Makefile into every libjaco_emu*.so; used by CPU-side (-m "not gpu") kernel checks: ctrl-level steps (with the
-// contact record of jaco_set_contact_record), env-level calls, robot-configuration queries (jaco_query), inverse kinematics (jaco_ik) and the
-// host build of the env snapshots (jaco_save_envs / jaco_load_envs).  The argument checks and the reset of one env are the library's own
-// host halves (query.h, ik.h, physics_kernel.h, env_logic.h, model_blob.cpp), called here as jaco_env.hip calls them.
+// contact record of jaco_set_contact_record, or with the low words a handle keeps), env-level calls, the eight query-style entries
+// (jaco_query, jaco_ik, jaco_osc, jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb) and the host build of the env
+// snapshots (jaco_save_envs / jaco_load_envs).  The argument checks and the reset of one env are the library's own host halves
+// (entry_args.h over query.h ... rollout_fb.h, physics_kernel.h, env_logic.h, model_blob.cpp), called here as jaco_env.hip calls them.
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -14,6 +15,7 @@
 #include "../../mujoco_jaco_amd/csrc/physics_kernel.h"
 #include "../../mujoco_jaco_amd/csrc/snapshot.h"
 #include "../../mujoco_jaco_amd/csrc/abi_agreement.h"
+#include "../../mujoco_jaco_amd/csrc/entry_args.h"
 
 void emu_run_wave(int block, std::function<void()> body);
 
@@ -31,7 +33,7 @@ extern "C" int emu_task_nact(int task_id) { return jaco_task_nact(task_id); }   
 // the message of the last refusal (JACO_EINVAL from an argument check, -1 from the model loader): the text jaco_last_error gives
 static std::string g_error;
 extern "C" const char* emu_last_error() { return g_error.c_str(); }
-static int refuse(const char* who, const std::string& why) { g_error = std::string(who) + ": " + why; return JACO_EINVAL; }
+static int refuse(const std::string& why) { g_error = why; return JACO_EINVAL; }
 
 // the model of the last call: every entry loads its blob into it (the loader starts from a zeroed model and a fresh hull table)
 static JacoModelDev g_model;
@@ -163,7 +165,7 @@ extern "C" int emu_marker_rest(const void* blob, long blob_size, float* out) {
 extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int nsub, int disable_contact, float* qpos, float* qvel, float* qacc_ws,
                                 const float* ctrl, float* sensordata, unsigned* flags, int* stats, JacoContact* rec, int* ncon, int cap,
                                 float* dbg, int dbg_env, int* heavy_envs) {
-  if (const char* why = rec ? jaco_contact_record_check(rec, ncon, cap) : nullptr) return refuse("jaco_set_contact_record", why);
+  if (const char* why = rec ? jaco_contact_record_check(rec, ncon, cap) : nullptr) return refuse(std::string("jaco_set_contact_record: ") + why);
   if (load_model(blob, blob_size)) return -1;
   JacoStepArgs A{};
   A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.ctrl = ctrl; A.sensordata = sensordata;
@@ -172,35 +174,115 @@ extern "C" int emu_physics_step(const void* blob, long blob_size, int nenv, int 
   return emu_launch(A, heavy_envs);
 }
 
-// the host half of jaco_query (jaco_query_resolve of query.h: argument checks, frame table by value) and the grid of the kernel: one wavefront per env
-extern "C" int emu_query(const void* blob, long blob_size, int nenv, const float* qpos, const float* qvel, const JacoFrame* frames, int nframes,
-                         float* xpos, float* xmat, float* jac, float* qM, float* qfrc_bias) {
+// A contact-free ctrl-level step as a handle runs it (jaco_physics_step under option "disable_contact"): like emu_physics_step, with the
+// compensated low words the library keeps between calls (qpos_lo / qvel_lo, zeroed by jaco_set_state).
+extern "C" int emu_step_lo(const void* blob, long blob_size, int nenv, int nsub, float* qpos, float* qvel, float* qacc_ws, float* qpos_lo, float* qvel_lo,
+                           const float* ctrl, unsigned* flags) {
   if (load_model(blob, blob_size)) return -1;
-  JacoQueryArgs Q{};
-  const std::string why = jaco_query_resolve(g_model, reinterpret_cast<const JacoQueryFrame*>(frames), nframes, &Q);
-  if (!why.empty()) return refuse("jaco_query", why);
-  Q.model = &g_model; Q.qpos = qpos; Q.qvel = qvel; Q.xpos = xpos; Q.xmat = xmat; Q.jac = jac; Q.qM = qM; Q.bias = qfrc_bias;
-  Q.nenv = nenv;
-  emu_grid = nenv;   // (the kernel reads only blockIdx; the grid jaco_query launches)
-  for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_query_kernel(Q); });
+  JacoStepArgs A{};
+  A.model = &g_model; A.hull = g_hull.data(); A.qpos = qpos; A.qvel = qvel; A.qacc_ws = qacc_ws; A.qpos_lo = qpos_lo; A.qvel_lo = qvel_lo; A.ctrl = ctrl;
+  A.flags = flags; A.nenv = nenv; A.nsub = nsub; A.disable_contact = 1; A.dbg_env = -1;
+  return emu_launch(A, nullptr);
+}
+
+// ---- the eight query-style entries.  Each is its library entry with the handle taken away: jaco_<entry>_bind of entry_args.h, the very
+// function jaco_env.hip calls, turns the arguments into the kernel's block (every check, the defaults, the records by value) or refuses;
+// the block gets the host copy of the model and the kernel runs over the grid the library launches, one wavefront per env (per rollout).
+// Where the library falls back to the handle's fp32 state, the two rollouts are handed it as handle_qpos / handle_qvel [num_envs][..];
+// the other entries are always called with their state.
+template <class Kernel>
+static int run_grid(int grid, Kernel kernel) {   // (the kernels read only blockIdx)
+  emu_grid = grid;
+  for (int e = 0; e < grid; e++) emu_run_wave(e, kernel);
   return 0;
 }
 
-// the host half of jaco_ik (argument checks, active dof set: jaco_ik_resolve of ik.h) and the grid of jaco_ik_kernel, one wavefront per env
+extern "C" int emu_query(const void* blob, long blob_size, int nenv, const float* qpos, const float* qvel, const JacoFrame* frames, int nframes,
+                         float* xpos, float* xmat, float* jac, float* qM, float* qfrc_bias) {
+  if (load_model(blob, blob_size)) return -1;
+  const JacoQueryOut out = {xpos, xmat, jac, qM, qfrc_bias};
+  JacoQueryArgs Q;
+  const std::string why = jaco_query_bind(g_model, frames, nframes, qpos, qvel, &out, nenv, nullptr, nullptr, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_query_kernel(Q); });
+}
+
 extern "C" int emu_ik(const void* blob, long blob_size, int nenv, const JacoFrame* frame, const JacoIkOptions* opt, const float* qpos_seed,
                       const float* target_pos, const float* target_quat, float* qpos_out, float* resid, int* status) {
   if (load_model(blob, blob_size)) return -1;
-  if (!frame || !qpos_seed || !target_pos || !qpos_out) return refuse("jaco_ik", "the frame, the target positions and the output qpos are required");
-  const JacoIkOptions defaults = JACO_IK_DEFAULTS;
-  JacoIkArgs Q{};
-  memcpy(&Q.fr, frame, sizeof(JacoFrame));
-  memcpy(&Q.opt, opt ? opt : &defaults, sizeof(JacoIkOptions));
-  if (const char* why = jaco_ik_resolve(g_model, Q.fr, Q.opt, &Q.active)) return refuse("jaco_ik", why);
-  Q.model = &g_model; Q.qpos = qpos_seed; Q.target_pos = target_pos; Q.target_quat = target_quat;
-  Q.qpos_out = qpos_out; Q.resid = resid; Q.status = status; Q.nenv = nenv;
-  emu_grid = nenv;
-  for (int e = 0; e < nenv; e++) emu_run_wave(e, [&]() { jaco_ik_kernel(Q); });
-  return 0;
+  JacoIkArgs Q;
+  const std::string why = jaco_ik_bind(g_model, frame, opt, qpos_seed, target_pos, target_quat, qpos_out, resid, status, nenv, nullptr, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_ik_kernel(Q); });
+}
+
+extern "C" int emu_osc(const void* blob, long blob_size, int nenv, const JacoFrame* frames, int nframes, const JacoOscOptions* opt,
+                       const float* qpos, const float* qvel, const float* target_pos, const float* target_quat, const float* ctrl_in,
+                       float* ctrl_out, int* status) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoOscArgs Q;
+  const std::string why = jaco_osc_bind(g_model, frames, nframes, opt, qpos, qvel, target_pos, target_quat, ctrl_in, ctrl_out, status, nenv, nullptr, nullptr, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_osc_kernel(Q); });
+}
+
+// (a NULL task record forwards to emu_osc, as jaco_osc_task forwards to jaco_osc)
+extern "C" int emu_osc_task(const void* blob, long blob_size, int nenv, const JacoFrame* frames, int nframes, const JacoOscOptions* opt,
+                            const JacoOscTask* task, const float* qpos, const float* qvel, const float* target_pos, const float* target_quat,
+                            const float* rest_qpos, const float* ctrl_in, float* ctrl_out, int* status) {
+  if (!task) return emu_osc(blob, blob_size, nenv, frames, nframes, opt, qpos, qvel, target_pos, target_quat, ctrl_in, ctrl_out, status);
+  if (load_model(blob, blob_size)) return -1;
+  JacoOscTaskArgs T;
+  const std::string why = jaco_osc_task_bind(g_model, frames, nframes, opt, task, qpos, qvel, target_pos, target_quat, rest_qpos, ctrl_in, ctrl_out, status, nenv,
+                                             nullptr, nullptr, &T);
+  if (!why.empty()) return refuse(why);
+  T.o.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_osc_task_kernel(T); });
+}
+
+extern "C" int emu_joint(const void* blob, long blob_size, int nenv, const JacoJointOptions* opt, const float* qpos, const float* qvel,
+                         const float* target_qpos, const float* target_qvel, const float* qacc_ff, const float* ctrl_in, float* ctrl_out) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoJointArgs Q;
+  const std::string why = jaco_joint_bind(g_model, opt, qpos, qvel, target_qpos, target_qvel, qacc_ff, ctrl_in, ctrl_out, nenv, nullptr, nullptr, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_joint_kernel(Q); });
+}
+
+extern "C" int emu_fd(const void* blob, long blob_size, int nenv, const JacoFdOptions* opt, const float* qpos, const float* qvel, const float* ctrl,
+                      const JacoFdOut* out) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoFdArgs Q;
+  const std::string why = jaco_fd_bind(g_model, opt, qpos, qvel, ctrl, out, nenv, nullptr, nullptr, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(nenv, [&]() { jaco_fd_kernel(Q); });
+}
+
+extern "C" int emu_rollout(const void* blob, long blob_size, const JacoRolloutOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx, int nstates,
+                           const float* qpos0, const float* qvel0, const float* ctrl, const JacoRolloutOut* out, int num_envs, const float* handle_qpos,
+                           const float* handle_qvel) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoRolloutArgs Q;
+  const std::string why = jaco_rollout_bind(g_model, opt, frame, n, state_idx, nstates, qpos0, qvel0, ctrl, out, num_envs, handle_qpos, handle_qvel, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.model = &g_model;
+  return run_grid(n, [&]() { jaco_rollout_kernel(Q); });
+}
+
+extern "C" int emu_rollout_fb(const void* blob, long blob_size, const JacoRolloutFbOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx, int nstates,
+                              const float* qpos0, const float* qvel0, const JacoRolloutPlan* plan, const JacoRolloutFbOut* out, int num_envs,
+                              const float* handle_qpos, const float* handle_qvel) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoRolloutFbArgs Q;
+  const std::string why = jaco_rollout_fb_bind(g_model, opt, frame, n, state_idx, nstates, qpos0, qvel0, plan, out, num_envs, handle_qpos, handle_qvel, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.R.model = &g_model;
+  return run_grid(n, [&]() { jaco_rollout_fb_kernel(Q); });
 }
 
 // ---- env snapshots: the table and the save / load routines of snapshot.h -- the very header the GPU kernels jaco_save_envs_kernel /

@@ -4,8 +4,12 @@ Runs the *unmodified* HIP kernel source (mujoco_jaco_amd/csrc/physics_kernel.h) 
 against a lockstep 64-lane wavefront emulator, so kernel logic can be checked against the oracle
 without a GPU.  Not a product path: the product library refuses to run without a HIP device.
 One library per layout / build option holds every entry: ctrl-level steps (with the contact record),
-env-level calls, robot-configuration queries (tests/query_binding.py) and inverse kinematics (tests/ik_binding.py), and one set of
-option switches.  A refused call raises ValueError with the text the library would leave in jaco_last_error.
+env-level calls, the eight query-style entries (tests/query_binding.py, ik_binding.py, osc_binding.py, osc_task_binding.py,
+joint_binding.py, fd_binding.py, rollout_binding.py, rollout_fb_binding.py), and one set of option switches.  lib() is the only
+place that builds and loads such a library and declares the argument types of its emu_* entries.  The switches are process-wide
+state of a library that every entry shares: whoever flips one puts it back (try / finally), so that no test depends on what ran
+before it.
+A refused call raises ValueError with the text the library would leave in jaco_last_error.
 """
 import ctypes
 import sys
@@ -36,6 +40,7 @@ def lib(layout=""):
         subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
         L = ctypes.CDLL(os.path.join(EMU_DIR, name))
         fp, ip, up = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint)
+        vp, ci = ctypes.c_void_p, ctypes.c_int
         L.emu_physics_step.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, up, ip,
                                        ctypes.c_void_p, ip, ctypes.c_int, fp, ctypes.c_int, ip]
         L.emu_env_call.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong,
@@ -43,6 +48,13 @@ def lib(layout=""):
         L.emu_query.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, fp, fp, ctypes.c_void_p, ctypes.c_int, fp, fp, fp, fp, fp]
         L.emu_marker_rest.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]
         L.emu_ik.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, fp, fp, fp, fp, fp, ip]
+        L.emu_osc.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, vp, ci, vp, fp, fp, fp, fp, fp, fp, ip]
+        L.emu_osc_task.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, vp, ci, vp, vp, fp, fp, fp, fp, fp, fp, fp, ip]
+        L.emu_joint.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, vp, fp, fp, fp, fp, fp, fp, fp]
+        L.emu_fd.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, vp, fp, fp, fp, vp]
+        L.emu_rollout.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.emu_rollout_fb.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.emu_step_lo.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         L.emu_last_error.restype = ctypes.c_char_p
         L.emu_qpos0.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]
         L.emu_set_auto_reset.argtypes = [ctypes.c_int]
@@ -133,11 +145,14 @@ class EmuJacoEnv(EmuEnv):
         fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if a is not None else None
         hv = ctypes.c_int(0)
         self.L.emu_set_obs_mode(int(getattr(self, "obs_mode", 0)))
-        rc = self.L.emu_env_call(self.blob, len(self.blob), self.nenv, mode, self.frame_skip, self.task_id, self.nact, self.seed,
-                                 fp(self.qpos), fp(self.qvel), fp(self.qacc_ws), fp(self.sensordata),
-                                 self.flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), self.stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                 fp(self.task), fp(self.cache), fp(action), fp(noise), fp(self.obs), fp(self.reward),
-                                 self.done.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), fp(self.marker), ctypes.byref(hv))
+        try:
+            rc = self.L.emu_env_call(self.blob, len(self.blob), self.nenv, mode, self.frame_skip, self.task_id, self.nact, self.seed,
+                                     fp(self.qpos), fp(self.qvel), fp(self.qacc_ws), fp(self.sensordata),
+                                     self.flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), self.stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                     fp(self.task), fp(self.cache), fp(action), fp(noise), fp(self.obs), fp(self.reward),
+                                     self.done.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), fp(self.marker), ctypes.byref(hv))
+        finally:
+            self.L.emu_set_obs_mode(0)   # (the library's switch, not this env's: the next caller finds the default)
         assert rc == 0
         self.heavy_envs = hv.value
 

@@ -1,5 +1,5 @@
 """The forward-dynamics kernel (mujoco_jaco_amd/csrc/fd.h, jaco_fd) under the wavefront emulator (emu_fd of
-tests/emu_fd/libjaco_emu_fd{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 references -- the oracle's qacc_smooth / qfrc_smooth after forward() at the fp32-rounded inputs, (qM + h diag(damping))^-1
 qfrc_smooth from the oracle's quantities for implicit_damping = 1, central differences of the oracle's acceleration with eps 1e-6 for
@@ -8,8 +8,6 @@ actuator model's knife edges, asserted on the fp64 side), the cases shared by th
 for BatchedMujoco.forward_dynamics / linearize backed by the emulator (CPU tests of robot_config).
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -17,28 +15,12 @@ import emu_binding
 import ik_binding as ib
 import osc_binding as ob
 import query_binding as qb
-from emu_binding import ROOT
 from mujoco_jaco_amd import _lib as product_lib
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu_fd")
 DEFAULTS = dict(product_lib.JacoFdOptions.DEFAULTS)
 OUTS = ("qacc", "qfrc_smooth", "dqacc_dqpos", "dqacc_dqvel", "dqacc_dctrl")
 REF_EPS = 1e-6          # the fp64 central differences of the reference
 CTRL_MARGIN = 0.05      # a limited ctrl is at least this far inside or outside its ctrlrange
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_fd<layout>.so: the emulator library of that layout with the emu_fd entry (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_fd%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        fp = ctypes.POINTER(ctypes.c_float)
-        L.emu_fd.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, fp, fp, fp, ctypes.c_void_p]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def fd(model, qpos, qvel, ctrl=None, want=OUTS, defaults=False, no_out=False, **options):
@@ -47,7 +29,7 @@ def fd(model, qpos, qvel, ctrl=None, want=OUTS, defaults=False, no_out=False, **
     NULL).  defaults=True hands a NULL options pointer, no_out=True a NULL output record.  Raises ValueError with the library's message
     when the call is refused."""
     blob, layout, nu = ob._model_info(model)
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
     B, nv = qpos.shape[0], qvel.shape[1]
     c = None if ctrl is None else np.ascontiguousarray(ctrl, np.float32).reshape(B, nu)

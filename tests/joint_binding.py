@@ -1,5 +1,5 @@
 """The joint-space controller kernel (mujoco_jaco_amd/csrc/joint.h, jaco_joint) under the wavefront emulator (emu_joint of
-tests/emu_joint/libjaco_emu_joint{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference -- the formula of include/jaco_env.h ("joint-space controller") written in numpy on the fp64 oracle's qM,
 qfrc_bias and qvel, read as osc_binding.reference reads them --, the input sets of the tests (targets kept off the wrap's and the
@@ -7,36 +7,18 @@ saturation's knife edges by construction), the refusal cases, the closed loops a
 emulator (CPU tests of robot_config.BatchedJoint).
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
 import emu_binding
 import ik_binding as ib
 import osc_binding as ob
-from emu_binding import ROOT
 from mujoco_jaco_amd import _lib as product_lib
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu_joint")
 DEFAULTS = dict(product_lib.JacoJointOptions.DEFAULTS)
 GAINS = dict(kp=30.0, kv=12.0)            # the non-default gains of the tests
 SAT = dict(kp=30.0, kv=12.0, vmax=0.5)    # saturation level vmax * kv / kp = 0.2 rad
 WRAP_MARGIN = 0.05                        # rad: how far a wrapped difference stays from +-pi
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_joint<layout>.so: the emulator library of that layout with the emu_joint entry (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_joint%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        fp = ctypes.POINTER(ctypes.c_float)
-        L.emu_joint.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, fp, fp, fp, fp, fp, fp, fp]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def joint(model, qpos, qvel, target_qpos=None, target_qvel=None, qacc=None, ctrl_in=None, alias=False, defaults=False, no_out=False, **options):
@@ -44,7 +26,7 @@ def joint(model, qpos, qvel, target_qpos=None, target_qvel=None, qacc=None, ctrl
     NULL) and ctrl_in [B, nu] (None: NULL).  alias=True: ctrl_out is the ctrl_in buffer.  defaults=True hands a NULL options pointer,
     no_out=True a NULL ctrl_out.  Raises ValueError with the library's message when the call is refused."""
     blob, layout, nu = ob._model_info(model)
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
     B = qpos.shape[0]
     fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -192,7 +174,7 @@ def servo_only_blob(model=REFUSAL_MODEL):
 
 def joint_on_blob(blob, qpos, qvel, layout=""):
     """emu_joint on raw blob bytes, NULL options and targets, kp from the defaults."""
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
     fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     out = np.zeros((qpos.shape[0], 9), np.float32)

@@ -1,5 +1,5 @@
 """The operational-space controller kernel (mujoco_jaco_amd/csrc/osc.h) under the wavefront emulator (emu_osc of
-tests/emu_osc/libjaco_emu_osc{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference (oracle/glue.py osc_generate on the fp64 oracle's J, M[active, active], qfrc_bias[active], point and
 quaternion), the input sets of the tests (seeds, targets, near-singular configurations), the closed loops and a stand-in for
@@ -7,7 +7,6 @@ BatchedMujoco's osc surface backed by the emulator (CPU tests of robot_config.Ba
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -21,22 +20,7 @@ from mujoco_jaco_amd import _lib as product_lib
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import glue  # noqa: E402
 
-EMU_OSC_DIR = os.path.join(ROOT, "tests", "emu_osc")
 DEFAULTS = dict(product_lib.JacoOscOptions.DEFAULTS)
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_osc<layout>.so: the emulator library of that layout with the emu_osc entry (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_osc%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_OSC_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_OSC_DIR, name))
-        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
-        L.emu_osc.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, fp, fp, fp, fp, fp, fp, ip]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 _info = {}
@@ -57,7 +41,7 @@ def osc(model, frames, qpos, qvel, target_pos, target_quat, ctrl_in=None, status
     buffer.  defaults=True hands a NULL options pointer, no_out=True a NULL ctrl_out.  Raises ValueError with the library's message when
     the call is refused."""
     blob, layout, nu = _model_info(model)
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
     B, nf = qpos.shape[0], 0 if frames is None else len(frames)
     fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))

@@ -1,41 +1,22 @@
 """The task-axis / null-space controller kernel (mujoco_jaco_amd/csrc/osc_task.h, jaco_osc_task) under the wavefront emulator
-(emu_osc_task of tests/emu_osc_task/libjaco_emu_osc_task{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+(emu_osc_task of tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 restatement of abr_control's OSC.generate() with ctrlr_dof and null_controllers = [Damping, RestingConfig] on true
 k x k matrices (generate / reference: the oracle's J, qM, qfrc_bias, point and quaternion, taken as osc_binding.reference takes them),
 the inputs of the tests, the refusal cases, the closed loops and a stand-in for BatchedMujoco's osc surface backed by the emulator.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
 import emu_binding
 import ik_binding as ib
 import osc_binding as ob
-from emu_binding import ROOT
 from mujoco_jaco_amd import _lib as product_lib
 from osc_binding import glue
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu_osc_task")
 POS, ROT, ALL = 0b000111, 0b111000, 0b111111
 NULL = dict(null_kv=10.0, rest_kp=20.0, rest_kv=5.0)   # the gains of the null-space cases
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_osc_task<layout>.so: the emulator library of that layout with the emu_osc and emu_osc_task entries (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_osc_task%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
-        L.emu_osc_task.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                   fp, fp, fp, fp, fp, fp, fp, ip]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def task_record(nf, axes=None, null_kv=0.0, rest_kp=0.0, rest_kv=0.0, rest_mask=0):
@@ -48,7 +29,7 @@ def osc_task(model, frames, qpos, qvel, target_pos, target_quat, ctrl_in=None, r
     task keywords (axes, null_kv, rest_kp, rest_kv, rest_mask; raw_axes: the axes words as they are) and the options (the remaining
     keywords).  no_task=True hands a NULL task record.  Raises ValueError with the library's message when the call is refused."""
     blob, layout, nu = ob._model_info(model)
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     qpos, qvel = np.ascontiguousarray(qpos, np.float32), np.ascontiguousarray(qvel, np.float32)
     B, nf = qpos.shape[0], len(frames)
     tk = {k: kw.pop(k) for k in ("axes", "null_kv", "rest_kp", "rest_kv", "rest_mask") if k in kw}

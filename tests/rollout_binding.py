@@ -1,5 +1,5 @@
 """The rollout kernel (mujoco_jaco_amd/csrc/rollout.h, jaco_rollout) under the wavefront emulator (emu_rollout of
-tests/emu_rollout/libjaco_emu_rollout{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference (the oracle with contacts disabled: per rollout qpos / qvel and a zero warm start, then step(ctrl_k, hold) per
 knot), the input sets with the conditions they must meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier, the
@@ -12,8 +12,6 @@ qpos0 / qvel0 None: the handle's state, which is handle = (qpos [num_envs, nq], 
 filled with SENTINEL (status: STATUS_SENTINEL), so what a call leaves untouched shows.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -21,29 +19,12 @@ import emu_binding
 import fd_binding as fb
 import ik_binding as ib
 import osc_binding as ob
-from emu_binding import ROOT
 from fd_binding import bits, verr
 from mujoco_jaco_amd import _lib as product_lib
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu_rollout")
 OUTS = ("qpos", "qvel", "xpos", "xmat", "status")
 SENTINEL, STATUS_SENTINEL = 7.0, 0x7777
 BAD_INDEX = product_lib.JACO_ROLLOUT_BAD_INDEX
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_rollout<layout>.so: the emulator library of that layout with the emu_rollout and emu_step_lo entries (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_rollout%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.emu_rollout.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
-        L.emu_step_lo.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def shapes(n, rows, nq, nv):
@@ -62,7 +43,7 @@ def rollout(model, ctrl, qpos0=None, qvel0=None, state_index=None, nstates=None,
     blob, layout, nu = ob._model_info(model)
     M = ib.load_model(model)
     nq, nv = int(M["nq"][0]), int(M["nv"][0])
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     ctrl = np.ascontiguousarray(ctrl, np.float32)
     n = ctrl.shape[0] if n is None else n
     nknots = ctrl.shape[1] if nknots is None else nknots
@@ -94,7 +75,7 @@ def emu_steps(model, q, v, ctrl, hold):
     """The emulated contact-free step kernel as a handle runs it -- set_state(q, v, zeros), then send_forces(ctrl_k, hold) + get_state per
     knot, the compensated low words kept between the calls as the library keeps them: (qpos [n, T, nq], qvel [n, T, nv], flags [n])."""
     blob, layout, nu = ob._model_info(model)
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     q, v = np.array(q, np.float32), np.array(v, np.float32)
     n, T = ctrl.shape[0], ctrl.shape[1]
     ws, ql, vl = np.zeros_like(v), np.zeros_like(q), np.zeros_like(v)

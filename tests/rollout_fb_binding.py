@@ -1,5 +1,5 @@
 """The closed-loop rollout kernel (mujoco_jaco_amd/csrc/rollout_fb.h, jaco_rollout_fb) under the wavefront emulator (emu_rollout_fb of
-tests/emu_rollout_fb/libjaco_emu_rollout_fb{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference (the oracle with contacts disabled, the law evaluated in fp64 on the oracle's own state at each evaluation),
 the input sets -- rollout_binding's states and ctrl rows plus seeded gains and a reference trajectory -- with the conditions they must
@@ -14,8 +14,6 @@ A tier hands the cases two calls:
 Every output array is handed in filled with SENTINEL (status: STATUS_SENTINEL), so what a call leaves untouched shows.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -25,28 +23,12 @@ import ik_binding as ib
 import joint_binding as jb
 import osc_binding as ob
 import rollout_binding as rb
-from emu_binding import ROOT
 from fd_binding import bits, verr
 from mujoco_jaco_amd import _lib as product_lib
 from rollout_binding import BAD_INDEX, SENTINEL, STATUS_SENTINEL, same
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu_rollout_fb")
 OUTS = ("qpos", "qvel", "xpos", "xmat", "status", "ctrl")
 STATE = ("qpos", "qvel", "status")
-_libs = {}
-
-
-def lib(layout=""):
-    """libjaco_emu_rollout_fb<layout>.so: the emulator library of that layout with the emu_rollout_fb entry (built on first use)."""
-    if layout not in _libs:
-        name = "libjaco_emu_rollout_fb%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.emu_rollout_fb.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
 
 
 def count(ctrl, alpha=None, plan_index=None, state_index=None, n=None):
@@ -72,7 +54,7 @@ def rollout_fb(model, ctrl, qpos0=None, qvel0=None, kff=None, gain=None, xref=No
     blob, layout, nu = ob._model_info(model)
     M = ib.load_model(model)
     nq, nv = int(M["nq"][0]), int(M["nv"][0])
-    L = lib(layout)
+    L = emu_binding.lib(layout)
     f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
     i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
     ctrl, kff, gain, xref, alpha, q0, v0 = [f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0)]
