@@ -483,6 +483,64 @@ typedef struct JacoRolloutFbOut { float* qpos; float* qvel; float* xpos; float* 
 int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
                     const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutFbOut* out, void* stream);
 
+/* ---- the iLQR / TVLQR backward pass, batched: the feed-forward k_t and the gains K_t that jaco_rollout_fb consumes, from the linearisation
+ * (jaco_fd) and the cost expansion along a trajectory, the whole T-knot recursion of every problem in ONE launch.
+ * Solve i works on problem p = prob_idx[i] and runs t = T-1 .. 0.  Deviations follow dx_{t+1} = A_t dx_t + B_t du_t; the knot cost is
+ * 1/2 dx'lxx dx + 1/2 du'luu du + du'lux dx + lx'dx + lu'du, the terminal cost 1/2 dx'Vxx dx + Vx'dx.  At each knot:
+ *   Qx = lx + A'Vx          Qu = lu + B'Vx
+ *   Qxx = lxx + A'Vxx A     Qux = lux + B'Vxx A     Quu = luu + B'Vxx B
+ *   L L' = Quu + mu_i I                    (Cholesky; a pivot <= 0 or a non-finite number: status = JACO_LQR_NOT_PD | t, the solve stops)
+ *   K = -(Quu + mu I)^-1 Qux               k = -(Quu + mu I)^-1 Qu
+ *   dV1 += k'Qu                            dV2 += 1/2 k'Quu k                     (Quu unregularised here and below)
+ *   Vx  = Qx  + K'Quu k + K'Qu  + Qux'k
+ *   Vxx = Qxx + K'Quu K + K'Qux + Qux'K;   Vxx = 1/2 (Vxx + Vxx')
+ * in jaco_rollout_fb's sign convention: u = u_ref + alpha k + K (x - x_ref).  With mu = 0, lux = lx = lu = NULL, lxx = Q, luu = R and
+ * Vxx = Qf, K is the finite-horizon LQR gain.  The fp32 order of operations is NOT part of the interface; that two runs of the same
+ * call agree bit for bit is.  A NULL lux / lx / lu / Vx gives what an array of zeros gives, bit for bit.
+ * Arrays: every cost array is [nprob][T][..] unless its bit is set in shared_knots (no knot axis: one block per problem) and / or in
+ * shared_probs (no problem axis); the terminal Vxx / Vx have no knot axis to begin with.  mu and prob_idx are per solve: one launch can
+ * try a ladder of regularisations on every problem.  n is not tied to num_envs; the handle supplies the device, the stream rules and
+ * jaco_last_error, the model is not read.
+ * Outputs (each may be NULL; at least one of gain / kff / dV / Vxx0 / Vx0): gain [n][T][rows][nx] and kff [n][T][rows], rows = rows_out ?
+ * rows_out : nu, control a in row row[a] (rows_out = 0: row a); rows that no control maps to are never written -- with rows_out = the
+ * model's nu and row = the motor words the two arrays are JacoRolloutPlan.gain / .kff as they are.  dV [n][2] = (dV1, dV2): the model's
+ * predicted cost change of a step alpha is alpha dV1 + alpha^2 dV2.  Vxx0 [n][nx][nx], Vx0 [n][nx]: the cost-to-go at knot 0.
+ * status [n]: 0; JACO_LQR_BAD_INDEX (prob_idx out of range: only the status word is written); JACO_LQR_NOT_PD | t (the rows of the
+ * knots > t are written, those of the knots <= t are not, neither are dV, Vxx0, Vx0).
+ * Asynchronous: one launch, no allocation, no synchronisation, no host copy; n == 0 returns JACO_OK without a launch.  JACO_EINVAL with
+ * nothing written: NULL options, problem or out; a dimension out of range; n < 0; nprob < 1; n > nprob without an index; a NULL
+ * required array; all five value outputs NULL; rows_out outside [nu, 64] when non-zero; a row out of range or listed twice; a mask bit
+ * outside the seven named. */
+#define JACO_LQR_MAX_NX 36            /* = 2 * JACO_ROLLOUT_FB_MAX_DOFS */
+#define JACO_LQR_MAX_NU 18
+#define JACO_LQR_BAD_INDEX 0x80000u   /* = JACO_ROLLOUT_BAD_INDEX */
+#define JACO_LQR_NOT_PD 0x100000u     /* Quu + mu I not positive definite, or non-finite, at knot (status & 0xffff) */
+/* which cost arrays have no knot axis / no problem axis */
+#define JACO_LQR_LXX 1u
+#define JACO_LQR_LUU 2u
+#define JACO_LQR_LUX 4u
+#define JACO_LQR_LX 8u
+#define JACO_LQR_LU 16u
+#define JACO_LQR_VXX 32u
+#define JACO_LQR_VX 64u
+typedef struct JacoLqrOptions {
+  int32_t nknots, nx, nu;            /* 1..JACO_ROLLOUT_MAX_SUBSTEPS, 1..JACO_LQR_MAX_NX, 1..JACO_LQR_MAX_NU */
+  int32_t rows_out;                  /* row count of the gain / kff outputs; 0 = nu */
+  int32_t row[JACO_LQR_MAX_NU];      /* used when rows_out != 0: control a goes to output row row[a]; distinct, in [0, rows_out) */
+  uint32_t shared_knots, shared_probs;
+} JacoLqrOptions;
+typedef struct JacoLqrProblem {      /* device pointers */
+  const float *A, *B;                /* [nprob][T][nx][nx], [nprob][T][nx][nu]   required */
+  const float *lxx, *luu;            /* [nprob][T][nx][nx], [nprob][T][nu][nu]   required (axes dropped per the shared masks) */
+  const float *lux, *lx, *lu;        /* [..][nu][nx], [..][nx], [..][nu]          or NULL = zero */
+  const float *Vxx, *Vx;             /* terminal: [nprob][nx][nx] required; [nprob][nx] or NULL = zero */
+  const float* mu;                   /* [n] or NULL = 0 */
+  const int32_t* prob_idx;           /* [n] or NULL: solve i takes problem i, so n <= nprob */
+  int32_t nprob;
+} JacoLqrProblem;
+typedef struct JacoLqrOut { float* gain; float* kff; float* dV; float* Vxx0; float* Vx0; uint32_t* status; } JacoLqrOut;
+int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

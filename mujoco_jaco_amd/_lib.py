@@ -155,6 +155,34 @@ class JacoRolloutFbOut(ctypes.Structure):
                 ("ctrl", ctypes.c_void_p)]
 
 
+JACO_LQR_MAX_NX, JACO_LQR_MAX_NU = 36, 18
+JACO_LQR_BAD_INDEX = 0x80000   # jaco_lqr: the solve's problem index was outside [0, nprob); only its status word was written
+JACO_LQR_NOT_PD = 0x100000     # jaco_lqr: Quu + mu I not positive definite, or a non-finite number, at knot (status & 0xffff)
+JACO_LQR_SHARED = dict(lxx=1, luu=2, lux=4, lx=8, lu=16, Vxx=32, Vx=64)   # the bits of shared_knots / shared_probs
+
+
+class JacoLqrOptions(ctypes.Structure):
+    """JacoLqrOptions of include/jaco_env.h.  rows: the output row of every control (nu distinct rows in [0, rows_out)); with
+    rows_out = 0 control a goes to row a."""
+    _fields_ = [("nknots", ctypes.c_int32), ("nx", ctypes.c_int32), ("nu", ctypes.c_int32), ("rows_out", ctypes.c_int32),
+                ("row", ctypes.c_int32 * JACO_LQR_MAX_NU), ("shared_knots", ctypes.c_uint32), ("shared_probs", ctypes.c_uint32)]
+
+    def __init__(self, nknots=0, nx=0, nu=0, rows_out=0, rows=(), shared_knots=0, shared_probs=0):
+        rows = [int(r) for r in rows]
+        if len(rows) > JACO_LQR_MAX_NU:
+            raise ValueError("%d rows: the backward pass takes at most %d controls" % (len(rows), JACO_LQR_MAX_NU))
+        super().__init__(nknots=nknots, nx=nx, nu=nu, rows_out=rows_out, shared_knots=shared_knots, shared_probs=shared_probs)
+        self.row[:len(rows)] = rows
+
+
+class JacoLqrProblem(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")] + [("nprob", ctypes.c_int32)]
+
+
+class JacoLqrOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("gain", "kff", "dV", "Vxx0", "Vx0", "status")]
+
+
 def osc_axes(axes, nframes):
     """The axes words of JacoOscTask for `nframes` frames from what the Python surface accepts: None (all six everywhere), one 6-bit mask
     or one list of six booleans (x, y, z, then the three rotational rows) for every frame, or a list of one of those per frame."""
@@ -247,6 +275,7 @@ SYMBOLS = {
     "jaco_fd": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout_fb": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_lqr": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

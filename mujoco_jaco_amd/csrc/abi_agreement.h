@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h and rollout_fb.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h and lqr.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -52,3 +52,26 @@ static_assert(sizeof(JacoRolloutPlan) == sizeof(JacoRolloutFbPlan) && offsetof(J
                   offsetof(JacoRolloutPlan, xref) == offsetof(JacoRolloutFbPlan, xref) && offsetof(JacoRolloutPlan, alpha) == offsetof(JacoRolloutFbPlan, alpha) &&
                   offsetof(JacoRolloutPlan, plan_idx) == offsetof(JacoRolloutFbPlan, plan_idx) && offsetof(JacoRolloutPlan, nplans) == offsetof(JacoRolloutFbPlan, nplans),
               "JacoRolloutPlan of the public header and the kernel's plan record must agree");
+static_assert(sizeof(JacoLqrOptions) == sizeof(JacoLqrOpts) && offsetof(JacoLqrOptions, nknots) == offsetof(JacoLqrOpts, nknots) &&
+                  offsetof(JacoLqrOptions, nx) == offsetof(JacoLqrOpts, nx) && offsetof(JacoLqrOptions, nu) == offsetof(JacoLqrOpts, nu) &&
+                  offsetof(JacoLqrOptions, rows_out) == offsetof(JacoLqrOpts, rows_out) && offsetof(JacoLqrOptions, row) == offsetof(JacoLqrOpts, row) &&
+                  offsetof(JacoLqrOptions, shared_knots) == offsetof(JacoLqrOpts, shared_knots) &&
+                  offsetof(JacoLqrOptions, shared_probs) == offsetof(JacoLqrOpts, shared_probs) && JACO_LQR_MAX_NX == JLQR_MAX_NX &&
+                  JACO_LQR_MAX_NU == JLQR_MAX_NU && JACO_LQR_MAX_NX == 2 * JACO_ROLLOUT_FB_MAX_DOFS && JACO_ROLLOUT_MAX_SUBSTEPS == JLQR_MAX_KNOTS &&
+                  JACO_LQR_BAD_INDEX == JLQR_BAD_INDEX && JACO_LQR_BAD_INDEX == JACO_ROLLOUT_BAD_INDEX && JACO_LQR_NOT_PD == JLQR_NOT_PD &&
+                  JACO_LQR_LXX == JLQR_LXX && JACO_LQR_LUU == JLQR_LUU && JACO_LQR_LUX == JLQR_LUX && JACO_LQR_LX == JLQR_LX &&
+                  JACO_LQR_LU == JLQR_LU && JACO_LQR_VXX == JLQR_VXX && JACO_LQR_VX == JLQR_VX,
+              "JacoLqrOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoLqrProblem) == sizeof(JacoLqrProb) && offsetof(JacoLqrProblem, A) == offsetof(JacoLqrProb, A) &&
+                  offsetof(JacoLqrProblem, B) == offsetof(JacoLqrProb, B) && offsetof(JacoLqrProblem, lxx) == offsetof(JacoLqrProb, lxx) &&
+                  offsetof(JacoLqrProblem, luu) == offsetof(JacoLqrProb, luu) && offsetof(JacoLqrProblem, lux) == offsetof(JacoLqrProb, lux) &&
+                  offsetof(JacoLqrProblem, lx) == offsetof(JacoLqrProb, lx) && offsetof(JacoLqrProblem, lu) == offsetof(JacoLqrProb, lu) &&
+                  offsetof(JacoLqrProblem, Vxx) == offsetof(JacoLqrProb, Vxx) && offsetof(JacoLqrProblem, Vx) == offsetof(JacoLqrProb, Vx) &&
+                  offsetof(JacoLqrProblem, mu) == offsetof(JacoLqrProb, mu) && offsetof(JacoLqrProblem, prob_idx) == offsetof(JacoLqrProb, prob_idx) &&
+                  offsetof(JacoLqrProblem, nprob) == offsetof(JacoLqrProb, nprob),
+              "JacoLqrProblem of the public header and the kernel's problem record must agree");
+static_assert(sizeof(JacoLqrOut) == sizeof(JacoLqrOutp) && offsetof(JacoLqrOut, gain) == offsetof(JacoLqrOutp, gain) &&
+                  offsetof(JacoLqrOut, kff) == offsetof(JacoLqrOutp, kff) && offsetof(JacoLqrOut, dV) == offsetof(JacoLqrOutp, dV) &&
+                  offsetof(JacoLqrOut, Vxx0) == offsetof(JacoLqrOutp, Vxx0) && offsetof(JacoLqrOut, Vx0) == offsetof(JacoLqrOutp, Vx0) &&
+                  offsetof(JacoLqrOut, status) == offsetof(JacoLqrOutp, status),
+              "JacoLqrOut of the public header and the kernel's output record must agree");

@@ -1,5 +1,5 @@
-// From the C ABI's arguments to the kernel's argument block, for the eight query-style entries (jaco_query, jaco_ik, jaco_osc,
-// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb).  Host only: included by the library's host unit (jaco_env.hip)
+// From the C ABI's arguments to the kernel's argument block, for the nine query-style entries (jaco_query, jaco_ik, jaco_osc,
+// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr).  Host only: included by the library's host unit (jaco_env.hip)
 // and by the CPU tests' host build (tests/emu/emu_driver.cpp), after include/jaco_env.h, physics_kernel.h and abi_agreement.h -- the
 // public records are copied into the kernel-side records that restate them, which the feature headers (query.h ... rollout_fb.h)
 // cannot do: they do not see the public header.  kernels.hip does not include this file.
@@ -12,6 +12,17 @@
 #pragma once
 #include <cstring>
 #include <string>
+
+// (jaco_lqr reads no model and no state: its host build for the CPU tests, tests/emu_lqr, sees lqr.h and the public header only and
+// defines JACO_ENTRY_ARGS_LQR_ONLY to take this one function)
+static inline std::string jaco_lqr_bind(const JacoLqrOptions* opt, int n, const JacoLqrProblem* prob, const JacoLqrOut* out, JacoLqrArgs* Q) {
+  *Q = JacoLqrArgs{};
+  const std::string why = jaco_lqr_resolve(reinterpret_cast<const JacoLqrOpts*>(opt), n, reinterpret_cast<const JacoLqrProb*>(prob),
+                                           reinterpret_cast<const JacoLqrOutp*>(out), Q);
+  return why.empty() ? why : "jaco_lqr: " + why;
+}
+
+#ifndef JACO_ENTRY_ARGS_LQR_ONLY
 
 static inline std::string jaco_query_bind(const JacoModelDev& m, const JacoFrame* frames, int nframes, const float* qpos, const float* qvel, const JacoQueryOut* out,
                                           int num_envs, const float* state_qpos, const float* state_qvel, JacoQueryArgs* Q) {
@@ -138,3 +149,4 @@ static inline std::string jaco_rollout_fb_bind(const JacoModelDev& m, const Jaco
   if (!Q->R.qpos0) { Q->R.qpos0 = state_qpos; Q->R.qvel0 = state_qvel; }
   return why;
 }
+#endif   // JACO_ENTRY_ARGS_LQR_ONLY

@@ -1042,3 +1042,11 @@ extern "C" int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_ho
   return launch_entry(h, jaco_launch_rollout_fb, n, stream, Q);
 }
 
+// the iLQR / TVLQR backward pass (lqr.h): the whole recursion of every problem in one launch; the model is not read
+extern "C" int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoLqrArgs Q;
+  if (refused(h, jaco_lqr_bind(opt_host, n, prob_host, out, &Q))) return JACO_EINVAL;
+  if (n == 0) return JACO_OK;
+  return launch_entry(h, jaco_launch_lqr, n, stream, Q);
+}

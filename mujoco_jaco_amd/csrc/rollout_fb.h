@@ -192,3 +192,6 @@ void jaco_launch_rollout_fb(unsigned grid, hipStream_t st, const JacoRolloutFbAr
 void jaco_launch_rollout_fb(unsigned grid, hipStream_t st, const JacoRolloutFbArgs& Q) { hipLaunchKernelGGL(jaco_rollout_fb_kernel, dim3(grid), dim3(64), 0, st, Q); }
 #endif
 #endif
+
+// the iLQR / TVLQR backward pass kernel (jaco_lqr): translation unit 17
+#include "lqr.h"

@@ -430,6 +430,97 @@ class BatchedMujoco:
         return self._rollout_fb(plan, alpha, pidx, q, v, sidx, nstates, frame, want, n, nknots=T, hold=int(hold), final_only=int(bool(final_only)),
                                 per_substep=int(bool(per_substep)), dofs=dofs if gain is not None else ())
 
+    # ---- the iLQR / TVLQR backward pass (jaco_lqr: the whole recursion of every problem in one launch)
+    def _lqr(self, opt, prob, out, n):
+        """One jaco_lqr launch.  opt: the keywords of _lib.JacoLqrOptions; prob: {field of JacoLqrProblem: contiguous device tensor or
+        None} plus "nprob"; out: {field of JacoLqrOut: tensor or None}, written in place."""
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        o = _lib.JacoLqrOptions(**opt)
+        p = _lib.JacoLqrProblem(*[ptr(prob.get(k)) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")], int(prob["nprob"]))
+        r = _lib.JacoLqrOut(*[ptr(out.get(k)) for k in ("gain", "kff", "dV", "Vxx0", "Vx0", "status")])
+        cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
+        self._chk(self.L.jaco_lqr(self.h, cast(o), int(n), cast(p), cast(r), self._stream()))
+
+    def lqr_backward(self, A, B, lxx, luu, lux=None, lx=None, lu=None, Vxx=None, Vx=None, mu=None, problem_index=None, rows=None, rows_out=None,
+                     out=None):
+        """The backward pass of iLQR / TVLQR for P problems of T knots in one launch: the feed-forward k_t and the gains K_t of
+            u = u_ref + alpha k_t + K_t (x - x_ref)                       (rollout_feedback's convention)
+        that minimise the quadratic model  sum_t (1/2 dx'lxx dx + 1/2 du'luu du + du'lux dx + lx'dx + lu'du) + 1/2 dx_T'Vxx dx_T + Vx'dx_T
+        under  dx_{t+1} = A_t dx_t + B_t du_t  (include/jaco_env.h states the recursion).  A [P, T, nx, nx], B [P, T, nx, nu].  A cost
+        array has the axes [P, T, ...]: lxx [P, T, nx, nx], luu [P, T, nu, nu], lux [P, T, nu, nx], lx [P, T, nx], lu [P, T, nu]; its
+        knot axis may be left out (lxx [P, nx, nx]: the same at every knot), then its problem axis too (lxx [nx, nx]), and an
+        axis of length 1 stands for all P problems or all T knots (lxx [1, T, nx, nx], lx [P, 1, nx]) -- nothing is expanded, the kernel
+        reads the one copy.  lux, lx,
+        lu None: zeros.  Terminal cost: Vxx [P, nx, nx] or [nx, nx] (None: lxx at the last knot), Vx [P, nx] or [nx] (None: zeros).
+        Solve i works on problem problem_index[i] (None: problem i) with the regularisation mu[i] added to Quu's diagonal before it is
+        factored (None: 0; one number: every solve's): n is the length of whichever of the two is given (both the same), else P -- one launch tries a ladder of
+        regularisations on every problem.  rows / rows_out: control a is written to row rows[a] of rows_out rows (the motor words of the
+        model's nu: the arrays are then rollout_feedback's gain / feedforward as they are); the other rows are zero.
+        Returns {"gain": [n, T, rows, nx], "kff": [n, T, rows], "dV": [n, 2] -- the model's cost change of a step alpha is alpha dV[0] +
+        alpha^2 dV[1] --, "Vxx0": [n, nx, nx], "Vx0": [n, nx]: the cost-to-go at knot 0, "status": [n] int32: 0, _lib.JACO_LQR_BAD_INDEX
+        (problem_index out of range: nothing written), or _lib.JACO_LQR_NOT_PD | t: Quu + mu I was not positive definite (or a number
+        not finite) at knot t; the rows of the knots > t are written, nothing else}.  out: a dict of tensors to write into instead of
+        fresh ones (any subset of the names; a name mapped to None is not computed).  One launch on the current stream, no
+        synchronisation; neither the model nor the sim's state is read."""
+        dev = self.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()
+        A, B = f32(A), f32(B)
+        if A.dim() != 4 or A.shape[2] != A.shape[3] or B.dim() != 4 or B.shape[:3] != A.shape[:3]:
+            raise ValueError("lqr_backward: A has shape %s and B %s, not [P, T, nx, nx] and [P, T, nx, nu]" % (tuple(A.shape), tuple(B.shape)))
+        P, T, nx, nu = int(A.shape[0]), int(A.shape[1]), int(A.shape[2]), int(B.shape[3])
+        shared = {"knots": 0, "probs": 0}
+
+        def cost(name, t, tail, knots=True):
+            """The array as the kernel reads it, its dropped axes recorded in the two masks."""
+            t = f32(t)
+            if t is None:
+                return None
+            lead = tuple(t.shape[:t.dim() - len(tail)])
+            full = (P, T) if knots else (P,)
+            if tuple(t.shape[len(lead):]) != tail or len(lead) > len(full) or any(a not in (1, b) for a, b in zip(lead, full)):
+                raise ValueError("lqr_backward: %s has shape %s, not %s with the leading axes %s (or fewer)" % (name, tuple(t.shape), list(tail), list(full)))
+            if knots and (len(lead) < 2 or (lead[1] == 1 and T > 1)):   # (a knot axis of length 1 is one block per problem: [P, 1, ..] = [P, ..])
+                shared["knots"] |= _lib.JACO_LQR_SHARED[name]
+            if not lead or (lead[0] == 1 and P > 1):
+                shared["probs"] |= _lib.JACO_LQR_SHARED[name]
+            return t
+        prob = {"A": A, "B": B, "lxx": cost("lxx", lxx, (nx, nx)), "luu": cost("luu", luu, (nu, nu)), "lux": cost("lux", lux, (nu, nx)),
+                "lx": cost("lx", lx, (nx,)), "lu": cost("lu", lu, (nu,)), "nprob": P}
+        if Vxx is None:   # lxx at the last knot
+            l, m = prob["lxx"], _lib.JACO_LQR_SHARED["lxx"]
+            Vxx = l[:, -1] if l.dim() == 4 else l
+        prob["Vxx"], prob["Vx"] = cost("Vxx", Vxx, (nx, nx), knots=False), cost("Vx", Vx, (nx,), knots=False)
+        idx = self._index(problem_index)
+        mu = None if mu is None else f32(mu).reshape(-1)
+        counts = {k: t.numel() for k, t in (("problem_index", idx), ("mu", mu)) if t is not None and not (k == "mu" and t.numel() == 1)}
+        if len(set(counts.values())) > 1:
+            raise ValueError("lqr_backward: %s" % " but ".join("%d entries of %s" % (c, k) for k, c in counts.items()))
+        n = next(iter(counts.values())) if counts else P
+        if mu is not None and mu.numel() == 1 and n != 1:   # (one mu for every solve)
+            mu = mu.expand(n).contiguous()
+        prob["mu"], prob["prob_idx"] = mu, idx
+        if (rows is None) != (rows_out is None):
+            raise ValueError("lqr_backward: rows and rows_out go together")
+        R = nu if rows_out is None else int(rows_out)
+        if rows is not None and len(rows) != nu:
+            raise ValueError("lqr_backward: %d rows for %d controls" % (len(rows), nu))
+        shapes = {"gain": (n, T, R, nx), "kff": (n, T, R), "dV": (n, 2), "Vxx0": (n, nx, nx), "Vx0": (n, nx), "status": (n,)}
+        res = {}
+        for k, sh in shapes.items():
+            if out is not None and k in out:
+                t = out[k]
+                if t is not None and (tuple(t.shape) != sh or not t.is_contiguous() or t.dtype != (torch.int32 if k == "status" else torch.float32)):
+                    raise ValueError("lqr_backward: out[%r] has shape %s, not a contiguous %s" % (k, tuple(t.shape), list(sh)))
+                res[k] = t
+            elif k == "status":
+                res[k] = torch.zeros(sh, dtype=torch.int32, device=dev)
+            else:   # (rows that no control maps to are never written: zeroed here once)
+                res[k] = (torch.zeros if rows is not None and k in ("gain", "kff") else torch.empty)(sh, dtype=torch.float32, device=dev)
+        if n > 0:
+            self._lqr(dict(nknots=T, nx=nx, nu=nu, rows_out=0 if rows is None else R, rows=() if rows is None else rows,
+                           shared_knots=shared["knots"], shared_probs=shared["probs"]), prob, res, n)
+        return res
+
     def get_xyz(self, name):
         """[num_envs, 3] world position of an MJCF body (sim.data.get_body_xpos, mujoco.py:148-170)."""
         return self.query([self.frames.jaco_frame(name)], xmat=False, jac=False, qM=False, qfrc_bias=False)["xpos"][:, 0]

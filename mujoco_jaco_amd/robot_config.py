@@ -395,6 +395,41 @@ class BatchedMujocoConfig:
         out["status"] = r["status"].reshape(B, A)
         return {key: t[:, 0] for key, t in out.items()} if alphas is None else out
 
+    def ilqr_backward(self, A, B, lxx, luu, lux=None, lx=None, lu=None, Vxx=None, Vx=None, mu=None, joints=None, full=False):
+        """The backward pass of iLQR on the joints and actuators that linearize(joints=...) and rollout_feedback(joints=...) use: x =
+        [q_J, dq_J] (2 n), u the motor words of those joints in the same order (m).  A [B, T, 2 n, 2 n], B [B, T, 2 n, m]: linearize's,
+        stacked over the knots; the cost expansion lxx, luu, lux, lx, lu, the terminal Vxx, Vx and the regularisation mu as
+        BatchedMujoco.lqr_backward takes them.  (K [B, T, m, 2 n], k [B, T, m], dV [B, 2], status [B]) for rollout_feedback(K=, k=,
+        alphas=): the model's cost change of a step alpha is alpha dV[:, 0] + alpha^2 dV[:, 1]; status 0, or _lib.JACO_LQR_NOT_PD | t.
+        full=True: (gain [B, T, nu, 2 n], kff [B, T, nu], dV, status), the rows scattered to the model's ctrl words by the kernel,
+        ready for sim.rollout_feedback(gain=, feedforward=).  One jaco_lqr launch."""
+        dofs, qadr, acts = self._joint_subset(joints, "ilqr_backward")
+        n, m = len(dofs), len(acts)
+        if A.dim() != 4 or tuple(A.shape[2:]) != (2 * n, 2 * n) or B.dim() != 4 or tuple(B.shape[2:]) != (2 * n, m):
+            raise ValueError("ilqr_backward: A has shape %s and B %s, not [B, T, %d, %d] and [B, T, %d, %d]" % (tuple(A.shape), tuple(B.shape), 2 * n, 2 * n, 2 * n, m))
+        scatter = dict(rows=acts, rows_out=self.sim.nu) if full else {}
+        r = self.sim.lqr_backward(A, B, lxx, luu, lux=lux, lx=lx, lu=lu, Vxx=Vxx, Vx=Vx, mu=mu, **scatter)
+        return r["gain"], r["kff"], r["dV"], r["status"]
+
+    def lqr(self, A, B, Q, R, Qf=None, status=False):
+        """lqr_gains(A, B, Q, R, Qf) in one jaco_lqr launch, in fp32 on the sim's device: K [..., T, m, nx] for A [..., T, nx, nx], B [...,
+        T, nx, m], Q, Qf [nx, nx], R [m, m] or batched like A without the knot axis.  Where lqr_gains' linalg.solve returns garbage
+        silently, a problem whose R + B'P B is not positive definite (or holds a number that is not finite) at knot t gets zero gains
+        at the knots <= t and the status word _lib.JACO_LQR_NOT_PD | t.  status=True returns (K, status [...] int32, 0 = solved), a
+        device tensor: reading it is the caller's synchronisation, which is why no error is raised here."""
+        import torch
+        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.sim.device)
+        A, B = f32(A), f32(B)
+        lead, nx, m = tuple(A.shape[:-3]), A.shape[-1], B.shape[-1]
+        flat = lambda t, tail: None if t is None else (f32(t) if f32(t).dim() == len(tail) else f32(t).expand(lead + tail).reshape((-1,) + tail))
+        A, B = A.reshape((-1,) + tuple(A.shape[-3:])), B.reshape((-1,) + tuple(B.shape[-3:]))
+        # (zeros: a problem whose R + B'P B is not positive definite at some knot keeps zero gains from that knot down, not garbage)
+        K = torch.zeros(A.shape[0], A.shape[1], m, nx, dtype=torch.float32, device=self.sim.device)
+        st = self.sim.lqr_backward(A, B, flat(Q, (nx, nx)), flat(R, (m, m)), Vxx=flat(Qf, (nx, nx)),
+                                   out=dict(gain=K, kff=None, dV=None, Vxx0=None, Vx0=None))["status"]
+        K = K.reshape(lead + tuple(K.shape[1:]))
+        return (K, st.reshape(lead)) if status else K
+
     def Tx(self, name, q=None, x=None):
         """[num_envs, 3] world position of the body origin, or of the point x (3-vector in the body frame) on it."""
         i = self._register(name)
