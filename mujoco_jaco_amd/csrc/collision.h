@@ -1070,6 +1070,9 @@ JDEV void stage_collision(const JacoStepArgs& A, const JacoModelDev* m, L& s, in
 // columns, solved by a small Newton solve of its own (newton_side, physics_kernel.h), and the main buffer keeps the other <= 64.
 // The side buffer costs no LDS: it overlays cdof[6..] + cvel, which are dead between this stage and the next substep's tree walk
 // (the controller reads cdof[0..5] only).  Virtual row index of side row j: JSIDE_BASE + j.
+#ifndef JACO_ROWS_FREE
+#define JACO_ROWS_FREE 1   // 0: the Jacobian pass always over all JNV columns (A/B build: tools/build_variant.sh rowsall -DJACO_ROWS_FREE=0)
+#endif
 #define JSIDE_ROWS 16
 #define JSIDE_BASE 64
 #define JSIDE_J 0        // [JSIDE_ROWS][6] Jacobian columns JB1 .. JNV-1
@@ -1104,10 +1107,33 @@ JDEV float contact_row_vel(const L& s, int c, int e, float mu) {
   }
   return vel;
 }
+// column k of the rows of contact ci (the Jacobian pass's lane): the relative point / angular velocity per unit qvel_k in the contact frame
+// (S: dof k's motion axis; a1 / a2: the dof chain masks of the two bodies), combined into the pyramid's edges; ld: the row stride at Jw
 template <class L>
-JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& flags) {
+JDEV void contact_jac_column(const L& s, const sv S, int k, int ci, unsigned a1, unsigned a2, int cdim, float f0, float f1, float f2, float* Jw, int ld) {
+  float coef = (float)((int)((a2 >> k) & 1u) - (int)((a1 >> k) & 1u));
+  v3 pos = ld3(s.c_pos[ci]);
+  v3 jp = (S.b + cross(S.a, pos)) * coef, jr = S.a * coef;
+  const float* fr = s.c_frame[ci];
+  float Jc[6];
+#pragma unroll
+  for (int a = 0; a < 3; a++) { Jc[a] = dot(ld3(fr + 3 * a), jp); Jc[3 + a] = dot(ld3(fr + 3 * a), jr); }
+  if (cdim == 1) Jw[0] = Jc[0];
+  else {
+    Jw[0] = Jc[0] + f0 * Jc[1]; Jw[ld] = Jc[0] - f0 * Jc[1];
+    Jw[2 * ld] = Jc[0] + f0 * Jc[2]; Jw[3 * ld] = Jc[0] - f0 * Jc[2];
+    if (cdim > 3) {
+      Jw[4 * ld] = Jc[0] + f1 * Jc[3]; Jw[5 * ld] = Jc[0] - f1 * Jc[3];
+      Jw[6 * ld] = Jc[0] + f2 * Jc[4]; Jw[7 * ld] = Jc[0] - f2 * Jc[4];
+      Jw[8 * ld] = Jc[0] + f2 * Jc[5]; Jw[9 * ld] = Jc[0] - f2 * Jc[5];
+    }
+  }
+}
+template <class L>
+JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& flags, JProfCtx& pc) {
   constexpr int MAXEFC = L::Caps::MAXEFC;
   constexpr bool SIDE = SideRows<L>::on;
+  (void)pc;
   const int nv = m->nv, ncon = wave_uniform_i(s.ncon), nlim = wave_uniform_i(s.nlimit);
   // per-contact parameters handed to the row lanes through LDS: the contact's own lane writes a0 and 1 / R into e_aref / e_D of each of
   // its rows (the row lanes then only fold the velocity part into e_aref) and the velocity coefficient into c_fn, which is not yet in use
@@ -1118,6 +1144,12 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
   const int cl = lane / JNV, k = lane - cl * JNV;
   const bool dofok = cl < CPP && k < nv;
   const sv S = ldsv(s.cdof[dofok ? k : 0]);
+  // ... or, when every contact of the chunk moves exactly one free body and nothing else (object on its static holder, pedestal on the
+  // floor: nine substeps in ten of the picking workload), lane = (contact slot 0..9, dof of that body): the pass computes the body's six
+  // columns only and the row lanes write +0 to the others.  (The full-width pass computes those as coef = 0 products, +-0: no sum can
+  // tell the difference, see rows_dot in physics_kernel.h.)  Wave-uniform choice per chunk; the surviving entries' expressions are the same.
+  constexpr bool FREE6 = JACO_ROWS_FREE != 0 && !L::Caps::WRENCH && JB1 - JB0 == 6 && (JNV - JB1 == 6 || JNV == JB1);
+  constexpr int CPF = 64 / 6;   // contacts per pass of that mapping
   for (int cb = 0; cb < ncon; cb += 64) {   // lane = contact, 64 at a time (one pass unless the tier holds more than 64 contacts)
     const int ci = cb + lane, nhere = ncon - cb < 64 ? ncon - cb : 64;
     // rows per contact and row offsets
@@ -1128,6 +1160,7 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
     // (pyramidal: 2 mu^2 R of the first row, impratio = 1) and the position part of aref; only the velocity part differs per
     // row.  aref_row = a0 - bcoef * vel_row,  D_row = dinv.
     float a0 = 0.f, bcoef = 0.f, dinv = 0.f;
+    JSTAMP_ROWS(5);
     if (lane < nhere) {
       const JacoPairParam& P = m->pair[s.c_pair[ci]];
       dim = s.c_dim[ci]; nrow = dim == 1 ? 1 : 2 * (dim - 1);
@@ -1140,6 +1173,7 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
       if (dim > 1) R = fmaxf(JMINVAL, 2.f * mu0 * mu0 * R);
       dinv = 1.f / R;
     }
+    JSTAMP_ROWS(11);
     // which contacts could live in the side buffer: dof support = the pedestal block alone, at most 4 rows; usable when they number at most
     // JSIDE_ROWS rows and no other contact reaches into that block (every tier counts them: "would the light tier cope?" needs the number)
     const unsigned mm = cm1 | cm2;
@@ -1184,9 +1218,12 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
     int total = wave_bcast_i(end, kept > 0 ? kept - 1 : 0);
     total = kept > 0 ? total : rowbase;
     const int r0 = sidec ? r0s : end - nrow;
+    // (block bits of my contact: 1 arm + fingers, 2 object, 4 pedestal)
+    const int blk = ((mm & ((1u << JB0) - 1u)) ? 1 : 0) | (((mm >> JB0) & ((1u << (JB1 - JB0)) - 1u)) ? 2 : 0) | ((mm >> JB1) ? 4 : 0);
+    const bool freec = FREE6 && !split && kept > 0 && wave_ballot(lane < kept && blk != 2 && blk != 4) == 0ull;
+    JSTAMP_ROWS(12);
     if (lane < kept) {
       s.c_efc[ci] = r0;
-      int blk = ((mm & ((1u << JB0) - 1u)) ? 1 : 0) | (((mm >> JB0) & ((1u << (JB1 - JB0)) - 1u)) ? 2 : 0) | ((mm >> JB1) ? 4 : 0);
       // body-space rows carry their body pair: (fused body + 1) of geom 1 / geom 2, 0 = static (c_ob keeps them at bits 8 / 24)
       const int bodies = L::Caps::WRENCH ? ((((s.c_ob[ci] >> 8) & 31) << 19) | (((s.c_ob[ci] >> 24) & 31) << 24)) : 0;
       if (!sidec) for (int e = 0; e < nrow; e++) {
@@ -1197,11 +1234,22 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
       s.c_fn[ci] = bcoef;
     }
     wave_sync();   // e_con, the per-contact parameters and the row maps are visible
+    JSTAMP_ROWS(13);
     // per-row parameters of this chunk's main rows, lane = row (before the Jacobian rows: in split mode those overwrite cvel)
     for (int rr = rowbase + lane; rr < total; rr += 64) {
       const int ce = s.e_con[rr], c = ce & 255, e = (ce >> 8) & 255;
       const float vel = contact_row_vel(s, c, e, s.e_f[rr]);
       s.e_aref[rr] = s.e_aref[rr] - s.c_fn[c] * vel;
+      if (freec) {   // (no split: the chunk's rows are [rowbase, total) of the main buffer)  every column outside the contact's own block
+        float* Jz = s.J + rr * JLD;
+#pragma unroll
+        for (int a = 0; a < JB0; a++) Jz[a] = 0.f;
+        if (JNV - JB1 == 6) {
+          Jz += ((ce >> 16) & 2) ? JB1 : JB0;
+#pragma unroll
+          for (int a = 0; a < 6; a++) Jz[a] = 0.f;
+        }
+      }
     }
     // ... and of the side rows, by their contact's own lane, into registers (the side buffer overlays cvel, which is still being read)
     float aside[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1216,6 +1264,7 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
         for (int e = 0; e < 4; e++) if (e < nrow) { sd[JSIDE_AREF + r0 - JSIDE_BASE + e] = aside[e]; sd[JSIDE_D + r0 - JSIDE_BASE + e] = dinv; }
       }
     }
+    JSTAMP_ROWS(14);
     if (L::Caps::WRENCH) {
       // the rows themselves, lane = row: wrench of pyramid edge e of contact c about the world origin -- linear part dir = n +- mu t_k
       // (k < 3) or n (torsional / rolling edges), angular part pos x dir (+- mu axis_k for k >= 3) -- so that J[r][d] = sgn_d(r) w . S_d
@@ -1233,35 +1282,34 @@ JDEV void stage_contact_rows(const JacoModelDev* m, L& s, int lane, unsigned& fl
         R[0] = ang.x; R[1] = ang.y; R[2] = ang.z; R[3] = lin.x; R[4] = lin.y; R[5] = lin.z; R[6] = 0.f; R[7] = 0.f;
       }
     } else
+    if (freec) {
+      const int cf = lane / 6, kf = lane - cf * 6;
+      for (int c0 = 0; c0 < kept; c0 += CPF) {
+#ifdef JACO_EMULATED
+        if (lane == 0) emu_counter[14]++;   // (CPU tests: Jacobian passes over one free body's columns; 15: over all columns)
+#endif
+        const int c = c0 + (cf < CPF ? cf : 0), src = c < 64 ? c : 0;
+        const int cdim = wave_shfl_i(dim, src), cr0 = wave_shfl_i(r0, src);
+        const float f0 = wave_shfl(mu0, src), f1 = wave_shfl(mu1, src), f2 = wave_shfl(mu2, src);
+        const unsigned a1 = (unsigned)wave_shfl_i((int)cm1, src), a2 = (unsigned)wave_shfl_i((int)cm2, src);
+        const int kk = (((a1 | a2) >> JB1) ? JB1 : JB0) + kf;
+        if (cf < CPF && c < kept && kk < nv) contact_jac_column(s, ldsv(s.cdof[kk]), kk, cb + c, a1, a2, cdim, f0, f1, f2, s.J + cr0 * JLD + kk, JLD);
+      }
+    } else
     for (int c0 = 0; c0 < kept; c0 += CPP) {
+#ifdef JACO_EMULATED
+      if (lane == 0) emu_counter[15]++;
+#endif
       int c = c0 + (cl < CPP ? cl : 0);
       int src = c < 64 ? c : 0;
       int cdim = wave_shfl_i(dim, src), cr0 = wave_shfl_i(r0, src);
       float f0 = wave_shfl(mu0, src), f1 = wave_shfl(mu1, src), f2 = wave_shfl(mu2, src);
       unsigned a1 = (unsigned)wave_shfl_i((int)cm1, src), a2 = (unsigned)wave_shfl_i((int)cm2, src);
       const bool cside = SIDE && cr0 >= JSIDE_BASE;   // (side rows hold the pedestal block's six columns only: their other entries are zero by construction)
-      if (dofok && c < kept && (!cside || k >= JB1)) {
-        float coef = (float)((int)((a2 >> k) & 1u) - (int)((a1 >> k) & 1u));
-        v3 pos = ld3(s.c_pos[cb + c]);
-        v3 jp = (S.b + cross(S.a, pos)) * coef, jr = S.a * coef;
-        const float* fr = s.c_frame[cb + c];
-        float Jc[6];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { Jc[a] = dot(ld3(fr + 3 * a), jp); Jc[3 + a] = dot(ld3(fr + 3 * a), jr); }
-        const int ld = cside ? 6 : JLD;
-        float* Jw = cside ? sd + JSIDE_J + (cr0 - JSIDE_BASE) * 6 + (k - JB1) : s.J + cr0 * JLD + k;
-        if (cdim == 1) Jw[0] = Jc[0];
-        else {
-          Jw[0] = Jc[0] + f0 * Jc[1]; Jw[ld] = Jc[0] - f0 * Jc[1];
-          Jw[2 * ld] = Jc[0] + f0 * Jc[2]; Jw[3 * ld] = Jc[0] - f0 * Jc[2];
-          if (cdim > 3) {
-            Jw[4 * ld] = Jc[0] + f1 * Jc[3]; Jw[5 * ld] = Jc[0] - f1 * Jc[3];
-            Jw[6 * ld] = Jc[0] + f2 * Jc[4]; Jw[7 * ld] = Jc[0] - f2 * Jc[4];
-            Jw[8 * ld] = Jc[0] + f2 * Jc[5]; Jw[9 * ld] = Jc[0] - f2 * Jc[5];
-          }
-        }
-      }
+      if (dofok && c < kept && (!cside || k >= JB1))
+        contact_jac_column(s, S, k, cb + c, a1, a2, cdim, f0, f1, f2, cside ? sd + JSIDE_J + (cr0 - JSIDE_BASE) * 6 + (k - JB1) : s.J + cr0 * JLD + k, cside ? 6 : JLD);
     }
+    JSTAMP_ROWS(1);
     rowbase = total; kept_total += kept;
     if (kept < nhere) { flags |= JFLAG_EFC_OVERFLOW; break; }   // the row buffer is full: this contact and all later ones are dropped
   }

@@ -109,12 +109,24 @@ JDEV void jprof_stamp(JProfCtx& pc, int i, int lane) {
 // -DJACO_NARROW_PROFILE (with JACO_PROFILE_STAGES; tools/gpu_stage_profile.py --narrow): the narrowphase split by what it ran -- slot 11 candidate
 // records (L2 round trip), 12 box-box, 13 plane-*, 14 MPR hits, 1 MPR misses incl. the cached-direction test; the Newton solver's four intervals,
 // the usual owners of 11 .. 14, all go to slot 6 in such a build
-#ifdef JACO_NARROW_PROFILE
+// -DJACO_ROWS_PROFILE (with JACO_PROFILE_STAGES; tools/gpu_stage_profile.py --rows): stage_contact_rows (collision.h) split the same way -- slot 11
+// per-contact parameters incl. the pair-constant fetch, 12 row offsets and side-row bookkeeping, 13 per-contact row writes, 14 row velocities,
+// 1 Jacobian passes; slot 5 keeps the stage's tail; the Newton solver again goes to slot 6.  Each of these stamps first waits for every
+// outstanding load and lets the compiler move nothing across it, so that an interval holds the latency of what it issued.
+#if defined(JACO_NARROW_PROFILE) || defined(JACO_ROWS_PROFILE)
 #define JSTAMP_NEWTON(i) JSTAMP(6)
-#define JSTAMP_NARROW(i) JSTAMP(i)
 #else
 #define JSTAMP_NEWTON(i) JSTAMP(i)
+#endif
+#ifdef JACO_NARROW_PROFILE
+#define JSTAMP_NARROW(i) JSTAMP(i)
+#else
 #define JSTAMP_NARROW(i)
+#endif
+#if defined(JACO_ROWS_PROFILE) && defined(JACO_PROFILE_STAGES) && !defined(JACO_EMULATED)
+#define JSTAMP_ROWS(i) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); JSTAMP(i); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define JSTAMP_ROWS(i)
 #endif
 // -DJACO_REGIME_CENSUS (diagnostic builds only; tools/gpu_regime_census.py, profiles/newton_regime.txt): no stamps; the profile row counts the
 // constrained solves of stage_newton instead -- slot 0 solves with rows, 1 those without a row on the arm/finger block ((rowblocks & 1) == 0),
@@ -1150,6 +1162,48 @@ JDEV float mat_vec(const float (&mrow)[JNV], float vk, bool free_only = false) {
   for (int k = JB0; k < JNV; k++) acc += mrow[k] * vb[k - JB0];
   return acc;
 }
+// M v (returned) and J v (out) of one vector in one go: mat_vec and rows_dot behind ONE set of column broadcasts and one column-range
+// branch, the two sums side by side.  stage_newton's start point and search directions: as two calls, each product sat behind its own
+// branch with its own broadcasts, one 12-deep dependent fma chain after the other (profiles/newton_regime.txt 3).  Each sum keeps its
+// ascending-k order and its form: every bit of both stays.  -DJACO_NEWTON_FUSE=0 (A/B build): the two calls.
+#ifndef JACO_NEWTON_FUSE
+#define JACO_NEWTON_FUSE 1
+#endif
+template <int NR>
+JDEV float mat_vec_rows_dot(const float (&mrow)[JNV], const float* J, const float (&jrow)[JNV], float vk, int lane, int ne, int nv, float (&out)[NR], bool free_only) {
+#if JACO_NEWTON_FUSE
+  const float* Jr[NR];
+#pragma unroll
+  for (int q = 0; q < NR; q++) { int r = lane + 64 * q; Jr[q] = J + (r < ne ? r : 0) * JLD; out[q] = 0.f; }
+  float acc = 0.f;
+  if (!(JACO_NEWTON_REGIME && free_only)) {
+    float vb[JB0];
+#pragma unroll
+    for (int k = 0; k < JB0; k++) vb[k] = wave_bcast(vk, k);
+#pragma unroll
+    for (int k = 0; k < JB0; k++) {
+      acc += mrow[k] * vb[k];
+#pragma unroll
+      for (int q = 0; q < NR; q++) out[q] += (NR == 1 ? jrow[k] : Jr[q][k]) * vb[k];
+    }
+  }
+  float vb[JNV - JB0];
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) vb[k - JB0] = wave_bcast(vk, k);
+#pragma unroll
+  for (int k = JB0; k < JNV; k++) {
+    acc += mrow[k] * vb[k - JB0];
+#pragma unroll
+    for (int q = 0; q < NR; q++) out[q] += (NR == 1 ? jrow[k] : Jr[q][k]) * vb[k - JB0];
+  }
+  (void)nv;
+  return acc;
+#else
+  const float acc = mat_vec(mrow, vk, free_only);
+  rows_dot<NR>(J, jrow, vk, lane, ne, nv, out, free_only);
+  return acc;
+#endif
+}
 // sum_r J[r][lane] * f_r, f distributed over the row slots; 4 rows in flight per step to cover LDS latency
 template <int NR>
 JDEV float jt_vec(const float* J, const float (&f)[NR], int ne, int lane, int nv) {
@@ -1253,9 +1307,8 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
   // Start: warm start on the row-carrying blocks (MuJoCo additionally compares it with the unconstrained point; with
   // an exact line search either start reaches the same optimum), exact solution elsewhere.
   float a = mine ? s.qacc_ws[lane] : afree;
-  float Ma = mat_vec(mrow, a, free_only) - smooth;   // from here on "Ma" = gradient of the smooth part, M a - qfrc_smooth
+  float Ma = mat_vec_rows_dot<NR>(mrow, s.J, jrow, a, lane, ne, nv, x, free_only) - smooth;   // (x = J a)  from here on "Ma" = gradient of the smooth part, M a - qfrc_smooth
   Ma = mine ? Ma : 0.f;
-  rows_dot<NR>(s.J, jrow, a, lane, ne, nv, x, free_only);
 #pragma unroll
   for (int q = 0; q < NR; q++) x[q] = valid[q] ? x[q] - ar[q] : 0.f;
   JSTAMP_NEWTON(11);
@@ -1358,10 +1411,9 @@ JDEV NewtonOut stage_newton(const JacoModelDev* m, L& s, const float (&mrow)[JNV
     p = lane < nv ? p : 0.f;
     JSTAMP_NEWTON(13);
     // exact line search on phi(al) = cost(a + al p)
-    float Mp = mat_vec(mrow, p, free_only);
+    float Mp = mat_vec_rows_dot<NR>(mrow, s.J, jrow, p, lane, ne, nv, jp, free_only);
     float pMp, pMa;
     wave_sum2(p * Mp, p * Ma, &pMp, &pMa);
-    rows_dot<NR>(s.J, jrow, p, lane, ne, nv, jp, free_only);
 #pragma unroll
     for (int q = 0; q < NR; q++) jp[q] = valid[q] ? jp[q] : 0.f;
     float al = 0.f, lo = 0.f, hi = 3.0e38f, d10 = 0.f, dlo = 0.f, dhi = 0.f;
@@ -2248,7 +2300,7 @@ again:
       stage_limit_rows(m, s, lane, pf);
       wave_sync();
       JSTAMP(3);
-      stage_contact_rows(m, s, lane, cflags);
+      stage_contact_rows(m, s, lane, cflags, pc);
       wave_sync();
       JSTAMP(5);
     } else {

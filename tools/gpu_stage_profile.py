@@ -69,6 +69,9 @@ names = ["walk", "geoms+inertia", "accum+mass+act", "limit rows", "collision: na
 if "--narrow" in sys.argv:   # a -DJACO_NARROW_PROFILE build of the diagnostic twin (JACO_ENV_LIB names it): the narrowphase by what it ran
     names[11], names[12], names[13], names[14], names[1] = "narrow: candidate records", "narrow: box-box", "narrow: plane-*", "narrow: MPR hits", "narrow: MPR misses + cached-direction tests"
     names[6] = "newton: everything"; names[4] = "narrow: rest (bookkeeping, tail)"
+if "--rows" in sys.argv:   # a -DJACO_ROWS_PROFILE build of the diagnostic twin (JACO_ENV_LIB names it): the contact-row stage by its parts
+    names[11], names[12], names[13], names[14], names[1] = "rows: per-contact parameters (pair constants)", "rows: row offsets, side-row bookkeeping", "rows: per-contact row writes", "rows: row velocities", "rows: Jacobian passes"
+    names[6] = "newton: everything"; names[5] = "rows: rest (entry, tail)"
 per = prof[:, :16].astype(np.float64) / nsub
 print("B", B, "nsub", nsub, "substeps/s %.3g" % (B * nsub / dt), "flags", int(env.flags().max()))
 st = env.stats().cpu().numpy()
