@@ -1,6 +1,7 @@
 """CPU tier: the contact record (jaco_set_contact_record) of the *unmodified* kernel source under the wavefront emulator
 (emu_binding.EmuEnv.step_rec), against the fp64 oracle's forward() at the same fp32-rounded state: data.contact and mj_contactForce
-restated from its efc_force.  One-substep ctrl-level steps on jaco2_curtain_torque; the record is that substep's forward pass."""
+restated from its efc_force.  One-substep ctrl-level steps on jaco2_curtain_torque; the record is that substep's forward pass.  Further down: the placed-object sweep through
+every narrowphase regime and the golden poses of the two-arm and the sensor model, contact by contact (contacts_binding.check_contacts)."""
 import os
 
 import numpy as np
@@ -159,3 +160,61 @@ def test_dual_arm_layout_counts_match_the_oracle():
         assert n[i] == oc["ncon"] == P["ncon"][i], (i, n[i], oc["ncon"])
         m = min(int(n[i]), 64)
         assert np.isfinite(R["force"][i, :m]).all() and (R["force"][i, :m, 0] >= 0).all()
+
+
+# ---------------------------------------------------------------- contact by contact beyond the reset draws (contacts_binding.placed_states)
+SWEEP_SEED = 7
+
+
+def test_placed_object_sweep_matches_oracle_contact_by_contact(names):
+    """210 placed-object states, 30 per regime (contacts_binding.REGIMES), one substep in one launch: the edge-edge branch of
+    collide_box_box4, reference corners and edge crossings (up to six contacts per pair), both reference sides, two and three pairs in one
+    pass, plane-box with one to four corners down, box-hull MPR from grazing to centimetres deep.  No state may be left out but by the
+    oracle-only knife-edge criterion (at most 1 %); every other state: exact count, each contact paired with the oracle's, equal dim,
+    analytic contacts inside BOUNDS_SWEEP, MPR contacts consistent and optimal in fp64 (contacts_binding.check_contacts), forces.
+    Measured: census box-box pairs 1: 94, 2: 48, 3: 30, 4: 58, 5: 8, 6: 2 (the largest count reached), plane-box 1: 10, 2: 7, 3: 3, 75 box-hull
+    contacts, 55 states with three pairs; 0 states left out; analytic dist 6.2e-8, pos 1.6e-7, normal 1.5e-7; MPR dist 1.8e-7, pos 1.9e-7,
+    normal 2.9e-5, none beyond BOUNDS_SWEEP, consistency 1.2e-7, optimality 1.5e-7; force 3.3e-6 / 6.2e-6 of the largest normal force."""
+    M = _model()
+    qs, regime = cb.placed_states(M, 210, SWEEP_SEED)
+    assert np.bincount(regime).tolist() == [30] * 7
+    ocs = cb.oracle_states("jaco2_curtain_torque", M, qs, np.zeros(9), knife=True)
+    cb.check_census(*cb.census(ocs, M, bodies=(names["body"].index("object_body"), names["body"].index("object_dest"))))
+    skip = {i for i, oc in enumerate(ocs) if oc["knife"]}
+    print("knife-edge states left out: %d of %d" % (len(skip), len(qs)))
+    assert len(skip) <= cb.KNIFE_CAP * len(qs)
+    assert max(a for oc in ocs for a in cb.oracle_consistency(M, oc)) < 1e-12   # the criterion on the reference's own contacts
+    e, R = _record(qs, np.zeros(9))
+    assert (e.flags & 31).max() == 0
+    s = cb.summarise(cb.tabulate(R, ocs, M, skip=skip))
+    cb.print_summary("placed sweep (emulator)", s)
+    cb.check_contacts(s, cb.PLACED)
+
+
+@pytest.mark.parametrize("model,poses,layout,bounds,want", [
+    ("jaco2_dual_torque", "dual_cross_poses.npz", "_d30", cb.DUAL_POSES, {(7, 7): 79, (6, 7): 178, (6, 6): 72}),
+    ("jaco2_curtain_torque_sensor", "sensor_post_poses.npz", "_d12", cb.SENSOR_POSES, {(5, 7): 29, (5, 6): 8})])
+def test_golden_poses_match_oracle_contact_by_contact(model, poses, layout, bounds, want):
+    """The arm-on-arm poses of the two-arm model (hull-hull, box-hull and box-box contacts) and the arm-on-cylinder poses of the sensor
+    model (cylinder-hull, cylinder-box), fp32-rounded, zero ctrl, one substep: every contact against the oracle's and, for MPR contacts,
+    the fp64 consistency / optimality check with box, cylinder and hull support functions.
+    Measured, two-arm: analytic dist 1.4e-7, pos 9.8e-8, normal 1.6e-7; MPR inside BOUNDS_SWEEP dist 6.3e-7, pos 2.8e-7, normal 7.0e-5, one of
+    257 beyond (normal 6.7e-4, 5.5 mm deep); consistency 1.8e-7, optimality 5.9e-7 (the one beyond: 7.7e-8, 8.1e-7); force 1.14e-4.
+    Sensor model: 7 of 37 beyond (pos 3.2e-5, normal 2.5e-4: other rim points of a cylinder), consistency 8.5e-8 (beyond 6.3e-8), optimality
+    6.6e-8 (beyond 3.3e-7); force 8.4e-4."""
+    from collections import Counter
+    M = _model(model)
+    P = np.load(os.path.join(ROOT, "tests", "golden", poses))
+    qs = cb._f32(P["qpos"])
+    nu = int(M["nu"][0])
+    ocs = cb.oracle_states(model, M, qs, np.zeros(nu))
+    assert max(a for oc in ocs for a in cb.oracle_consistency(M, oc)) < 1e-12
+    e = EmuEnv(model, nenv=len(qs), layout=layout)
+    e.qpos[:] = qs; e.qvel[:] = 0; e.qacc_ws[:] = 0
+    rec, n = e.step_rec(np.zeros(nu), nsub=1, cap=64)
+    assert (e.flags & 31).max() == 0 and np.array_equal(n, P["ncon"])
+    rows = cb.tabulate(cb.unpack(rec, n), ocs, M)
+    assert Counter(tuple(sorted(int(M["geom_type"][g]) for g in r["geoms"])) for r in rows) == want
+    s = cb.summarise(rows)
+    cb.print_summary(model + " golden poses (emulator)", s)
+    cb.check_contacts(s, bounds)

@@ -1,6 +1,7 @@
 """GPU tier: the contact record (jaco_set_contact_record; BatchedMujoco.record_contacts / contacts / net_contact_force) on the MI355X --
 oracle parity through every capacity tier, static equilibrium of the resting object, the auto_reset rule, and that recording changes no
-result (default build at the env tier, _d30 build at the sim tier)."""
+result (default build at the env tier, _d30 build at the sim tier); and, beyond the reset draws, the placed-object sweep, the device's
+record against the emulated kernel's, and the golden poses of the two-arm and the sensor model contact by contact."""
 import os
 
 import numpy as np
@@ -203,3 +204,102 @@ def test_two_arm_model_at_the_sim_tier():
         assert torch.equal(a, b)
     ncon, stat = recs
     assert np.array_equal(ncon[:n], P["ncon"]) and np.array_equal(ncon, stat)
+
+
+# ---------------------------------------------------------------- contact by contact beyond the reset draws (contacts_binding.placed_states)
+@pytest.fixture(scope="module")
+def placed_sweep():
+    """1 024 placed-object states (the emulator tier's 210 are the first of them), one substep in one launch, and the oracle's forward() of each
+    with its knife-edge verdict: computed once, read by the tests below."""
+    M = _model()
+    B = 1024
+    qs, regime = cb.placed_states(M, B, 7)
+    sim = BatchedMujoco(B)
+    sim.set_state(_dev(qs), torch.zeros(B, 21, device="cuda:0"), torch.zeros(B, 21, device="cuda:0"))
+    sim.record_contacts(128)
+    sim.clear_flags()
+    sim.send_forces(torch.zeros(B, 9, device="cuda:0"), nsub=1)
+    R = _np_record(sim.contacts())
+    fl = sim.flags().cpu().numpy()
+    sim.close()
+    ocs = cb.oracle_states("jaco2_curtain_torque", M, qs, np.zeros(9), knife=True)
+    return M, qs, regime, ocs, R, fl
+
+
+def _ident(M):
+    return np.arange(len(M["geom_type"]), dtype=np.int32)
+
+
+def test_placed_object_sweep_matches_oracle_contact_by_contact(placed_sweep, names):
+    """The emulator tier's sweep (tests/test_contacts_emu.py) at 1 024 envs on the device: same criteria, caps and bounds, census minima x 4.
+    Measured on the emulator at these states: box-box pairs 1: 427, 2: 235, 3: 95, 4: 329, 5: 36, 6: 7, plane-box 1: 33, 2: 44, 3: 20, 342
+    box-hull contacts, 260 states with three pairs, 0 left out; analytic dist 8.8e-8, pos 3.2e-7, normal 3.5e-7; MPR dist 3.7e-7, pos 2.3e-7, normal
+    1.5e-4, none beyond BOUNDS_SWEEP, consistency 1.2e-7, optimality 4.9e-7; force 3.3e-6 / 1.8e-5."""
+    M, qs, regime, ocs, R, fl = placed_sweep
+    cb.check_census(*cb.census(ocs, M, bodies=(names["body"].index("object_body"), names["body"].index("object_dest"))), scale=4)
+    skip = {i for i, oc in enumerate(ocs) if oc["knife"]}
+    print("knife-edge states left out: %d of %d" % (len(skip), len(qs)))
+    assert len(skip) <= cb.KNIFE_CAP * len(qs)
+    assert (fl & 31).max() == 0
+    s = cb.summarise(cb.tabulate(R, ocs, M, gmap=_ident(M), skip=skip))
+    cb.print_summary("placed sweep (MI355X)", s)
+    cb.check_contacts(s, cb.PLACED)
+
+
+def test_device_record_against_the_emulated_kernel(placed_sweep):
+    """The first 210 placed states under the wavefront emulator: the device's record has the same counts and the same geom pairs in the same
+    order; dist, pos, normal and force (relative to the env's largest normal force) within cb.DEVICE_VS_EMU -- a wave primitive or a
+    compiler choice the emulator does not model would show here.  Not expected to be bit for bit."""
+    from emu_binding import EmuEnv
+    M, qs, regime, ocs, R, fl = placed_sweep
+    n = 210
+    e = EmuEnv(nenv=n)
+    e.qpos[:] = qs[:n]; e.qvel[:] = 0; e.qacc_ws[:] = 0
+    rec, ncon = e.step_rec(np.zeros(9), nsub=1, cap=128)
+    E = cb.unpack(rec, ncon)
+    assert np.array_equal(ncon, R["ncon"][:n])
+    worst = np.zeros(4)
+    for i in range(n):
+        k = int(ncon[i])
+        assert np.array_equal(M["f_geom_orig"][E["geom"][i, :k]], R["geom"][i, :k]), i
+        assert np.array_equal(E["dim"][i, :k], R["dim"][i, :k]), i
+        if k:
+            fmax = max(np.abs(E["force"][i, :k, 0]).max(), 1e-9)
+            worst = np.maximum(worst, [np.abs(E["dist"][i, :k] - R["dist"][i, :k]).max(), np.abs(E["pos"][i, :k] - R["pos"][i, :k]).max(),
+                                       np.abs(E["frame"][i, :k, 0] - R["frame"][i, :k, 0]).max(), np.abs(E["force"][i, :k] - R["force"][i, :k]).max() / fmax])
+    print("device against emulator, %d states, %d contacts: worst [dist, pos, normal, force rel]" % (n, int(ncon.sum())), worst)
+    assert (worst <= cb.DEVICE_VS_EMU).all(), worst
+
+
+@pytest.mark.parametrize("model,poses,bounds,want", [
+    ("jaco2_dual_torque", "dual_cross_poses.npz", cb.DUAL_POSES, {(7, 7): 79, (6, 7): 178, (6, 6): 72}),
+    ("jaco2_curtain_torque_sensor", "sensor_post_poses.npz", cb.SENSOR_POSES, {(5, 7): 29, (5, 6): 8})])
+def test_golden_poses_match_oracle_contact_by_contact(model, poses, bounds, want):
+    """The arm-on-arm poses on the _d30 build (through JacoBatchedEnv(n_robots=2)) and the arm-on-cylinder poses of the sensor model on the
+    _d12 build, fp32-rounded, zero ctrl, one substep: hull-hull, box-hull, box-box, cylinder-hull and cylinder-box contacts one by one
+    against the oracle's, with the emulator tier's checks and bounds (tests/test_contacts_emu.py, same test name)."""
+    from collections import Counter
+    M = _model(model)
+    P = np.load(os.path.join(ROOT, "tests", "golden", poses))
+    qs = cb._f32(P["qpos"])
+    B, nv, nu = len(qs), int(M["nv"][0]), int(M["nu"][0])
+    if model == "jaco2_dual_torque":
+        from mujoco_jaco_amd.env import JacoBatchedEnv
+        owner = JacoBatchedEnv(num_envs=B, n_robots=2)
+        sim = owner.sim
+    else:
+        owner = sim = BatchedMujoco(B, robot_file=model)
+    sim.record_contacts(64)
+    sim.set_state(_dev(qs), torch.zeros(B, nv, device="cuda:0"), torch.zeros(B, nv, device="cuda:0"))
+    sim.clear_flags()
+    sim.send_forces(torch.zeros(B, nu, device="cuda:0"), nsub=1)
+    R = _np_record(sim.contacts())
+    fl = sim.flags().cpu().numpy()
+    owner.close()
+    assert (fl & 31).max() == 0 and np.array_equal(R["ncon"], P["ncon"])
+    ocs = cb.oracle_states(model, M, qs, np.zeros(nu))
+    rows = cb.tabulate(R, ocs, M, gmap=_ident(M))
+    assert Counter(tuple(sorted(int(M["geom_type"][g]) for g in r["geoms"])) for r in rows) == want
+    s = cb.summarise(rows)
+    cb.print_summary(model + " golden poses (MI355X)", s)
+    cb.check_contacts(s, bounds)
