@@ -2,7 +2,7 @@
 // how does it change with the state and the ctrl?  MuJoCo's data.qacc_smooth after mj_forward, and a contact-free mjd_transitionFD.
 //
 // One 64-lane wavefront per env on the contact-free LDS type (JacoLDS<JacoArm>).  The state is exactly the floats handed in (low words
-// zero) and stage_model runs once; everything from the tree walk on is one pass (fd_pass) made of the step kernel's own stages, called
+// zero) and stage_model runs once (entry_state); everything from the tree walk on is one pass (fd_pass) made of the step kernel's own stages, called
 // as they are:
 //   stage_walk, stage_accumulate, stage_mass_bias (s.smooth = passive - bias), stage_actuation with act_fetch's constants (ctrl clamped
 //   to ctrlrange, kp (c - q) for the position servos, forcerange: s.smooth += qfrc_actuator), then row `lane` of the block-diagonal
@@ -19,7 +19,7 @@
 //     actual difference of the two rounded coordinates goes straight to global memory: row c of the output is one contiguous [nv] row, so
 //     the lanes store consecutive words.  Rows the mask does not select are written as zeros.  A NULL output skips its loop.
 // No LDS beyond the forward pass's, no scratch memory.  Nothing of a handle is read but the model.
-// Included at the end of joint.h; the kernel is translation unit 14 (kernels.hip -DJACO_TU=14).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 14 (kernels.hip -DJACO_TU=14).
 #pragma once
 #include <cmath>
 #include <string>
@@ -66,27 +66,12 @@ static inline std::string jaco_fd_resolve(const JacoModelDev& m, const JacoFdOpt
   return std::string();
 }
 
-// (as osc_args_view)
-#ifdef JACO_EMULATED
-JDEV const JacoFdArgs* fd_args_view(const JacoFdArgs& Q) { return &Q; }
-#else
-JDEV const JacoFdArgs* fd_args_view(const JacoFdArgs&) {
-  typedef const JacoFdArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoFdArgs*)p;
-}
-#endif
-
-// row `lane` of M (+ hd on the diagonal) from the block-diagonal storage; lanes >= nv hold identity rows (as run_env loads mrow)
+// row `lane` of M (mass_row) + hd on the diagonal; lanes >= nv hold identity rows
 template <class L>
 JDEV void fd_rows(float (&h)[JNV], const L& s, int lane, int nv, float hd) {
-  const int blo = lane < JB0 ? 0 : (lane < JB1 ? JB0 : JB1), bn = lane < JB0 ? JB0 : (lane < JB1 ? JB1 - JB0 : JNV - JB1);
-  const int rbase = lane < nv ? m_index(lane, blo) : 0;
+  mass_row(h, s, lane, nv);
 #pragma unroll
-  for (int j = 0; j < JNV; j++) {
-    const bool in = lane < nv && j >= blo && j < blo + bn;
-    h[j] = (in ? s.M[in ? rbase + j - blo : 0] : 0.f) + (lane == j ? (lane < nv ? hd : 1.f) : 0.f);
-  }
+  for (int j = 0; j < JNV; j++) h[j] += lane == j ? (lane < nv ? hd : 1.f) : 0.f;
 }
 
 // h D of the Euler stage for this lane's dof: on the damped block only
@@ -102,16 +87,10 @@ JDEV float fd_pass(const JacoModelDev* m, L& s, int lane, int implicit, int bloc
   m = opaque_ptr(m);
   lane = wave_opaque_i(lane);
   const int nv = m->nv;
-  stage_walk(m, s, lane, false);
-  for (int i = lane; i < JMBLK; i += 64) s.M[i] = 0.f;
-  wave_sync();
+  entry_walk(m, s, lane);
   // (fetched per pass, as the step kernel fetches them per substep: held over the whole loop they would cost the solve its registers)
   const ActParams actp = act_fetch(m, lane);
-  const StagePrefetch pf = stage_prefetch(m, lane);
-  stage_accumulate(m, s, lane);
-  wave_sync();
-  stage_mass_bias(m, s, lane, pf);
-  wave_sync();
+  const StagePrefetch pf = entry_mass_bias(m, s, lane);
   stage_actuation(m, s, lane, actp);
   wave_sync();
   float h[JNV];
@@ -123,16 +102,10 @@ JDEV float fd_pass(const JacoModelDev* m, L& s, int lane, int implicit, int bloc
 template <class L>
 JDEV void run_fd(const JacoFdArgs& Q_, L& s, int env, int lane) {
   static_assert(JNV <= 32, "the perturbed dof set is a 32-bit mask");
-  const JacoFdArgs* Qp = fd_args_view(Q_);
-  const JacoFdArgs& Q = *Qp;
+  const JacoFdArgs& Q = *kernarg_view(Q_);   // (as run_osc reads its block)
   const JacoModelDev* m = opaque_ptr(Q.model);
-  const int nq = m->nq, nv = m->nv, nu = m->nu;
-  // the prologue of run_query: the state is exactly the floats handed in (low-order words zero)
-  if (lane < nq) { s.qpos[lane] = Q.qpos[(size_t)env * nq + lane]; s.qpos_lo[lane] = 0.f; }
-  if (lane < nv) { s.qvel[lane] = Q.qvel[(size_t)env * nv + lane]; s.qvel_lo[lane] = 0.f; }
-  if (lane < nu) s.ctrl[lane] = Q.ctrl ? Q.ctrl[(size_t)env * nu + lane] : 0.f;
-  stage_model(m, s, lane);
-  wave_sync();
+  const int nv = m->nv, nu = m->nu;
+  entry_state<ENTRY_CTRL>(m, s, Q.qpos, Q.qvel, Q.ctrl, env, lane);
   const int implicit = Q.implicit_damping;
   const int blockmask = 1 | (nv > JB0 ? 2 : 0) | (nv > JB1 ? 4 : 0);
   const float qacc = fd_pass(m, s, lane, implicit, blockmask);
@@ -195,20 +168,7 @@ JDEV void run_fd(const JacoFdArgs& Q_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(14)
-__global__ __launch_bounds__(64, 4) void jaco_fd_kernel(JacoFdArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= Q.nenv) return;
-  run_fd(Q, s, env, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(fd, JacoFdArgs, Q.nenv, run_fd)
+#else
+JACO_DECLARE_ENTRY(fd, JacoFdArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_fd(unsigned grid, hipStream_t st, const JacoFdArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 14
-void jaco_launch_fd(unsigned grid, hipStream_t st, const JacoFdArgs& Q) { hipLaunchKernelGGL(jaco_fd_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
-#endif
-
-// the open-loop rollout kernel (jaco_rollout): translation unit 15
-#include "rollout.h"

@@ -17,7 +17,7 @@
 // wave): a wave leaves as soon as its env has converged.
 // Nothing of a handle is read but the model; outputs: qpos_out (the seed row with the active dofs replaced, every other word copied bit
 // for bit), resid (|e_p|, |e_r| of the last evaluation), status (iterations taken, converged 0 / 1).
-// Included at the end of physics_kernel.h; the kernel is translation unit 10 (kernels.hip -DJACO_TU=10).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 10 (kernels.hip -DJACO_TU=10).
 #pragma once
 
 #define JIK_MAX_ITERS 256   // = JACO_IK_MAX_ITERS
@@ -55,21 +55,10 @@ static inline const char* jaco_ik_resolve(const JacoModelDev& m, const JacoQuery
   return nullptr;
 }
 
-// (as query_args_view: the block is read through the kernarg segment pointer, an s_load per use, nothing carried across the loop)
-#ifdef JACO_EMULATED
-JDEV const JacoIkArgs* ik_args_view(const JacoIkArgs& Q) { return &Q; }
-#else
-JDEV const JacoIkArgs* ik_args_view(const JacoIkArgs&) {
-  typedef const JacoIkArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoIkArgs*)p;
-}
-#endif
-
 template <class L>
 JDEV void run_ik(const JacoIkArgs& Q_, L& s, int env, int lane) {
-  const JacoIkArgs* Qp = ik_args_view(Q_);
-  const JacoIkArgs& Q = *Qp;
+  // (the block is read through the kernarg segment pointer, an s_load per use, nothing carried across the loop)
+  const JacoIkArgs& Q = *kernarg_view(Q_);
   const JacoModelDev* m = opaque_ptr(Q.model);
   const int nq = m->nq, nv = m->nv;
   // the prologue of run_query: the state is exactly the floats handed in (low-order words zero), at rest
@@ -173,17 +162,7 @@ JDEV void run_ik(const JacoIkArgs& Q_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(10)
-__global__ __launch_bounds__(64, 4) void jaco_ik_kernel(JacoIkArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= Q.nenv) return;
-  run_ik(Q, s, env, (int)threadIdx.x);
-}
-#endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_ik(unsigned grid, hipStream_t st, const JacoIkArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 10
-void jaco_launch_ik(unsigned grid, hipStream_t st, const JacoIkArgs& Q) { hipLaunchKernelGGL(jaco_ik_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
+JACO_DEFINE_ENTRY(ik, JacoIkArgs, Q.nenv, run_ik)
+#else
+JACO_DECLARE_ENTRY(ik, JacoIkArgs)
 #endif

@@ -4,7 +4,7 @@
 // (kp = kv = 0 and nothing else: abr_control's Floating).
 //
 // One 64-lane wavefront per env on the contact-free LDS type (JacoLDS<JacoArm>): run_osc's prologue and forward pass as they are
-// (osc_forward of osc_task.h: the state floats as handed in, low words zero, model tables, tree walk, subtree sums, mass matrix + bias --
+// (entry_state_forward: the state floats as handed in, low words zero, model tables, tree walk, subtree sums, mass matrix + bias --
 // the values of a sim.forward() on the given state), then, with the active dof set A that the host half resolved (a wave-uniform mask):
 //   e_d = q*_d - q_d                                   for a limited joint,
 //   e_d = ((q*_d - q_d + pi) mod 2 pi) - pi            for an unlimited one (floor-style modulus: osc_task.h's resting term);  e = 0
@@ -19,9 +19,9 @@
 // Mapping: lane d owns dof d and row d of M; max |e| is a wave reduction (lanes outside A hold 0); the row sum walks A by bit scan of the
 // wave-uniform mask -- a scalar loop -- and takes a_k from lane k by v_readlane.  No LDS beyond the forward pass's but the [JNV] output
 // row at s.J[224, 224 + JNV) (the row area is free: stage_mass_bias is done with it), no scratch memory.
-// Output: run_osc's epilogue exactly (osc_write_ctrl): the ctrl_in row with u_d at the motor actuator of every d in A, every other word
+// Output: run_osc's epilogue, as osc_write_ctrl states it (run_osc holds a twin of it written out): the ctrl_in row with u_d at the motor actuator of every d in A, every other word
 // moved as an integer; ctrl_out may be ctrl_in.  No clamping.  Nothing of a handle is read but the model.
-// Included at the end of osc_task.h; the kernel is translation unit 13 (kernels.hip -DJACO_TU=13).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 13 (kernels.hip -DJACO_TU=13).
 #pragma once
 #include <cmath>
 #include <string>
@@ -73,28 +73,16 @@ static inline std::string jaco_joint_resolve(const JacoModelDev& m, const JacoJo
   return std::string();
 }
 
-// (as osc_args_view)
-#ifdef JACO_EMULATED
-JDEV const JacoJointArgs* joint_args_view(const JacoJointArgs& Q) { return &Q; }
-#else
-JDEV const JacoJointArgs* joint_args_view(const JacoJointArgs&) {
-  typedef const JacoJointArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoJointArgs*)p;
-}
-#endif
-
 template <class L>
 JDEV void run_joint(const JacoJointArgs& Q_, L& s, int env, int lane) {
   static_assert(JNV <= 32, "the active dof set is a 32-bit mask");
-  const JacoJointArgs* Qp = joint_args_view(Q_);
-  const JacoJointArgs& Q = *Qp;
+  const JacoJointArgs& Q = *kernarg_view(Q_);   // (as run_osc reads its block)
   const JacoModelDev* m = opaque_ptr(Q.model);
   const int nq = m->nq, nv = m->nv, nu = m->nu;
   // this lane's ctrl word, read before anything is written (ctrl_out may be ctrl_in): moved as an integer
   unsigned word = 0u;
   if (lane < nu && Q.ctrl_in) word = reinterpret_cast<const unsigned*>(Q.ctrl_in)[(size_t)env * nu + lane];
-  osc_forward(m, Q.qpos, Q.qvel, s, env, lane);
+  entry_state_forward(m, s, Q.qpos, Q.qvel, env, lane);
   const unsigned act = (unsigned)wave_uniform_i((int)Q.active);
   const bool mine = lane < nv && ((act >> (lane & 31)) & 1u) != 0u;   // (every active dof is < nv <= JNV)
   const int d = mine ? lane : 0;
@@ -133,19 +121,7 @@ JDEV void run_joint(const JacoJointArgs& Q_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(13)
-__global__ __launch_bounds__(64, 4) void jaco_joint_kernel(JacoJointArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= Q.nenv) return;
-  run_joint(Q, s, env, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(joint, JacoJointArgs, Q.nenv, run_joint)
+#else
+JACO_DECLARE_ENTRY(joint, JacoJointArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_joint(unsigned grid, hipStream_t st, const JacoJointArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 13
-void jaco_launch_joint(unsigned grid, hipStream_t st, const JacoJointArgs& Q) { hipLaunchKernelGGL(jaco_joint_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
-#endif
-
-#include "fd.h"

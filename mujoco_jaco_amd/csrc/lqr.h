@@ -27,8 +27,8 @@
 // then on; B is dead by then too and holds (K | k).  27 440 B: five workgroups per CU.  No scratch memory.
 // Failure: a solve that stops at knot t has written the rows of the knots > t and nothing else but its status word; a knot's rows go
 // out only after that knot's K, k, Vxx and Vx were all found finite.  An index out of range writes JLQR_BAD_INDEX and nothing else.
-// The header needs jaco/wave_ops.h and nothing of the model: the CPU tests build it on its own.  In the library it hangs at the end of
-// rollout_fb.h; the kernel is translation unit 17 (kernels.hip -DJACO_TU=17).
+// The header needs jaco/wave_ops.h and nothing of the model: the CPU tests build it on its own.  In the library it is the last of the entry
+// headers listed at the tail of physics_kernel.h; the kernel is translation unit 17 (kernels.hip -DJACO_TU=17).
 #pragma once
 #include <cmath>
 #include <string>
@@ -104,8 +104,8 @@ static inline std::string jaco_lqr_resolve(const JacoLqrOpts* o, int n, const Ja
   return std::string();
 }
 
-// (as rollout_args_view: the block is read through the kernel-argument segment, so that a per-lane index into row[] is a load, not a
-// private copy of the block)
+// (kernarg_view of physics_kernel.h, which this header must do without: the block is read through the kernel-argument segment, so
+// that a per-lane index into row[] is a load, not a private copy of the block)
 #ifdef JACO_EMULATED
 JDEV const JacoLqrArgs* lqr_args_view(const JacoLqrArgs& Q) { return &Q; }
 #else

@@ -17,7 +17,7 @@
 // determinant goes through a wave-uniform value: a scalar branch.
 // Nothing of a handle is read but the model; outputs: ctrl_out (the ctrl_in row with u_d at the motor actuator of every active dof d,
 // every other word moved as an integer) and status (1: pseudo-inverse branch).
-// Included at the end of physics_kernel.h; the kernel is translation unit 11 (kernels.hip -DJACO_TU=11).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 11 (kernels.hip -DJACO_TU=11).
 #pragma once
 #include <string>
 
@@ -74,19 +74,37 @@ static inline std::string jaco_osc_resolve(const JacoModelDev& m, const JacoQuer
   return std::string();
 }
 
-// (as query_args_view: the block is read through the kernarg segment pointer, an s_load per use; a by-value parameter indexed by the
-// frame loop's counter would be copied to scratch)
-#ifdef JACO_EMULATED
-JDEV const JacoOscArgs* osc_args_view(const JacoOscArgs& Q) { return &Q; }
-#else
-JDEV const JacoOscArgs* osc_args_view(const JacoOscArgs&) {
-  typedef const JacoOscArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoOscArgs*)p;
-}
-#endif
-
 struct OscGains { float kp, ko, kv, sat_xyz, sat_abg; };
+
+// The pieces of run_osc_task (osc_task.h) and run_joint (joint.h).  run_osc below does NOT call them: it holds each of them written out
+// (the ctrl word, the gains, the unit quaternion, the ctrl row), hand-kept twins, because its kernel on the shared functions measured
+// 1 - 2 % slower on the MI355X and its part of that change was taken back whole.  A change here has to be made in run_osc too.
+// this lane's ctrl_in word, read before anything is written (ctrl_out may be ctrl_in): moved as an integer
+JDEV unsigned osc_read_ctrl(const float* ctrl_in, int env, int lane, int nu) {
+  return (lane < nu && ctrl_in) ? reinterpret_cast<const unsigned*>(ctrl_in)[(size_t)env * nu + lane] : 0u;
+}
+// the gains out of the argument block
+JDEV OscGains osc_gains(const JacoOscArgs& Q) {
+  OscGains g;
+  g.kp = Q.opt.kp; g.ko = Q.opt.ko; g.kv = Q.opt.kv; g.sat_xyz = Q.sat_xyz; g.sat_abg = Q.sat_abg;
+  return g;
+}
+// the target quaternion, normalised again (a zero one: the identity)
+JDEV void osc_unit_quat(const float* tq, float (&qd)[4]) {
+  qd[0] = tq[0]; qd[1] = tq[1]; qd[2] = tq[2]; qd[3] = tq[3];
+  const float qn = sqrtf(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]);
+  if (qn < JMINVAL) { qd[0] = 1.f; qd[1] = qd[2] = qd[3] = 0.f; } else { const float in = 1.f / qn; for (int k = 0; k < 4; k++) qd[k] *= in; }
+}
+// the ctrl_in row (`word`: this lane's, from osc_read_ctrl) with the motor of every active dof replaced: every other word goes out as
+// it came in
+JDEV void osc_write_ctrl(const JacoModelDev* m, float* ctrl_out, int env, int lane, unsigned all, unsigned word, const float* Uo) {
+  const int nv = m->nv, nu = m->nu;
+  if (lane < nu) {
+    const int d = m->a_dof[lane];
+    const bool mine = m->a_position[lane] == 0 && d >= 0 && d < nv && ((all >> (d >= 0 ? d : 0)) & 1u) != 0u;
+    reinterpret_cast<unsigned*>(ctrl_out)[(size_t)env * nu + lane] = mine ? __builtin_bit_cast(unsigned, Uo[mine ? d : 0]) : word;
+  }
+}
 
 // stage_osc_general (env_logic.h) with its four fixed things made arguments: the active dofs (a 32-bit mask, 1 <= popcount <= 6), the
 // frame pose (pe, Re), the target (pt, unit qd) and the gains.  Needs s.cdof, s.M, s.bias, s.qvel; writes u_d to Uo[d] for every
@@ -180,8 +198,9 @@ JDEV int stage_osc_frame(L& s, int lane, unsigned active, const v3 pe, const m3&
 
 template <class L>
 JDEV void run_osc(const JacoOscArgs& Q_, L& s, int env, int lane) {
-  const JacoOscArgs* Qp = osc_args_view(Q_);
-  const JacoOscArgs& Q = *Qp;
+  // (the block is read through the kernarg segment pointer, an s_load per use; a by-value parameter indexed by the frame loop's counter
+  // would be copied to scratch)
+  const JacoOscArgs& Q = *kernarg_view(Q_);
   const JacoModelDev* m = opaque_ptr(Q.model);
   const int nq = m->nq, nv = m->nv, nu = m->nu, nf = Q.nframes;
   // this lane's ctrl word, read before anything is written (ctrl_out may be ctrl_in): moved as an integer
@@ -231,19 +250,7 @@ JDEV void run_osc(const JacoOscArgs& Q_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(11)
-__global__ __launch_bounds__(64, 4) void jaco_osc_kernel(JacoOscArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= Q.nenv) return;
-  run_osc(Q, s, env, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(osc, JacoOscArgs, Q.nenv, run_osc)
+#else
+JACO_DECLARE_ENTRY(osc, JacoOscArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_osc(unsigned grid, hipStream_t st, const JacoOscArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 11
-void jaco_launch_osc(unsigned grid, hipStream_t st, const JacoOscArgs& Q) { hipLaunchKernelGGL(jaco_osc_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
-#endif
-
-#include "osc_task.h"

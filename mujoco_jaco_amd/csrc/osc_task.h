@@ -1,7 +1,7 @@
 // Operational-space controller with task axes and null-space posture terms (jaco_osc_task, include/jaco_env.h): abr_control's
 // OSC(robot_config, kp, ko, kv, vmax, ctrlr_dof, null_controllers=[Damping, RestingConfig]).generate().
 //
-// run_osc of osc.h with another per-frame stage: the same forward pass (osc_forward), the same frame pose, then stage_osc_task_frame.
+// run_osc of osc.h with another per-frame stage: the same forward pass (entry_state, entry_forward), the same frame pose, then stage_osc_task_frame.
 // With rows = the task rows that the frame's 6-bit axis mask selects (k of them) and Js = J[rows]:
 //   X  = Js M^-1 Js^T (k x k);  Mx = X^-1 when n >= k and |det X| >= 1e-3, else the pseudo-inverse that drops singular values < 0.005;
 //   u_task as in osc.h (both halves saturated on their full three components, then the gains), then its selected rows;
@@ -14,7 +14,7 @@
 // entries of the right-hand side are 0.  Then the determinant and the inverse block are those of the k x k matrix, and the padding's
 // singular values are 1 and never dropped.  n < k (exactly rank deficient) is decided from the two counts, both wave-uniform scalars.
 // Scratch: stage_osc_frame's s.J[0, 222), Uo at s.J[224, 224 + JNV), and s.J[256, 268) behind it for z and the right-hand side.
-// Included at the end of osc.h; the kernel is translation unit 12 (kernels.hip -DJACO_TU=12).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 12 (kernels.hip -DJACO_TU=12).
 #pragma once
 #include <cmath>
 
@@ -59,64 +59,6 @@ static inline std::string jaco_osc_task_resolve(const JacoModelDev& m, const Jac
   }
   T->null_kv = t.null_kv; T->rest_kp = t.rest_kp; T->rest_kv = t.rest_kv;
   return std::string();
-}
-
-// (as osc_args_view)
-#ifdef JACO_EMULATED
-JDEV const JacoOscTaskArgs* osc_task_args_view(const JacoOscTaskArgs& T) { return &T; }
-#else
-JDEV const JacoOscTaskArgs* osc_task_args_view(const JacoOscTaskArgs&) {
-  typedef const JacoOscTaskArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoOscTaskArgs*)p;
-}
-#endif
-
-// run_osc's pieces, restated so that osc.h and the code of translation unit 11 stay as they are.
-// osc_forward: the prologue of run_query -- the state is exactly the floats handed in (low-order words zero) -- then the step kernel's
-// tree walk, subtree sums and mass matrix + bias: the values of a sim.forward() on the given state.
-template <class L>
-JDEV void osc_forward(const JacoModelDev* m, const float* qpos, const float* qvel, L& s, int env, int lane) {
-  const int nq = m->nq, nv = m->nv;
-  if (lane < nq) { s.qpos[lane] = qpos[(size_t)env * nq + lane]; s.qpos_lo[lane] = 0.f; }
-  if (lane < nv) { s.qvel[lane] = qvel[(size_t)env * nv + lane]; s.qvel_lo[lane] = 0.f; }
-  stage_model(m, s, lane);
-  wave_sync();
-  stage_walk(m, s, lane, false);
-  for (int i = lane; i < JMBLK; i += 64) s.M[i] = 0.f;
-  wave_sync();
-  {
-    const StagePrefetch pf = stage_prefetch(m, lane);
-    stage_accumulate(m, s, lane);
-    wave_sync();
-    stage_mass_bias(m, s, lane, pf);
-    wave_sync();
-  }
-}
-// frame pose, every lane (same-address LDS reads): as run_query composes it
-template <class L>
-JDEV void osc_frame_pose(const L& s, const JacoQueryFrame& fr, v3* p, m3* R) {
-  const int b = fr.body;
-  const m3 Rb = ldm(s.xmat[b]);
-  const v3 pf = ld3(s.xpos[b]) + mul(Rb, ld3(fr.pos));
-  *R = mul(Rb, ldm(fr.mat));
-  *p = pf + mul(*R, ld3(fr.point));
-}
-// the target quaternion, normalised again (a zero one: the identity)
-JDEV void osc_unit_quat(const float* tq, float (&qd)[4]) {
-  qd[0] = tq[0]; qd[1] = tq[1]; qd[2] = tq[2]; qd[3] = tq[3];
-  const float qn = sqrtf(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]);
-  if (qn < JMINVAL) { qd[0] = 1.f; qd[1] = qd[2] = qd[3] = 0.f; } else { const float in = 1.f / qn; for (int k = 0; k < 4; k++) qd[k] *= in; }
-}
-// the ctrl_in row (`word`: this lane's, read before anything was written) with the motor of every active dof replaced: every other word
-// goes out as it came in
-JDEV void osc_write_ctrl(const JacoModelDev* m, float* ctrl_out, int env, int lane, unsigned all, unsigned word, const float* Uo) {
-  const int nv = m->nv, nu = m->nu;
-  if (lane < nu) {
-    const int d = m->a_dof[lane];
-    const bool mine = m->a_position[lane] == 0 && d >= 0 && d < nv && ((all >> (d >= 0 ? d : 0)) & 1u) != 0u;
-    reinterpret_cast<unsigned*>(ctrl_out)[(size_t)env * nu + lane] = mine ? __builtin_bit_cast(unsigned, Uo[mine ? d : 0]) : word;
-  }
 }
 
 struct OscNull { float null_kv, rest_kp, rest_kv; unsigned held; const float* rest; };   // rest: this env's row, or nullptr
@@ -250,18 +192,15 @@ JDEV int stage_osc_task_frame(const JacoModelDev* m, L& s, int lane, unsigned ac
 
 template <class L>
 JDEV void run_osc_task(const JacoOscTaskArgs& T_, L& s, int env, int lane) {
-  const JacoOscTaskArgs* Tp = osc_task_args_view(T_);
-  const JacoOscTaskArgs& T = *Tp;
+  const JacoOscTaskArgs& T = *kernarg_view(T_);   // (as run_osc reads its block)
   const JacoOscArgs& Q = T.o;
   const JacoModelDev* m = opaque_ptr(Q.model);
-  const int nq = m->nq, nu = m->nu, nf = Q.nframes;
-  // this lane's ctrl word, read before anything is written (ctrl_out may be ctrl_in): moved as an integer
-  unsigned word = 0u;
-  if (lane < nu && Q.ctrl_in) word = reinterpret_cast<const unsigned*>(Q.ctrl_in)[(size_t)env * nu + lane];
-  osc_forward(m, Q.qpos, Q.qvel, s, env, lane);
+  const int nq = m->nq, nf = Q.nframes;
+  const unsigned word = osc_read_ctrl(Q.ctrl_in, env, lane, m->nu);
+  entry_state(m, s, Q.qpos, Q.qvel, nullptr, env, lane);
+  entry_forward(m, s, lane);
   float* Uo = s.J + 224;   // [JNV] u_d by dof
-  OscGains g;
-  g.kp = Q.opt.kp; g.ko = Q.opt.ko; g.kv = Q.opt.kv; g.sat_xyz = Q.sat_xyz; g.sat_abg = Q.sat_abg;
+  const OscGains g = osc_gains(Q);
   OscNull nl;
   nl.null_kv = T.null_kv; nl.rest_kp = T.rest_kp; nl.rest_kv = T.rest_kv;
   nl.rest = T.rest_qpos ? T.rest_qpos + (size_t)env * nq : nullptr;
@@ -269,7 +208,8 @@ JDEV void run_osc_task(const JacoOscTaskArgs& T_, L& s, int env, int lane) {
   for (int f = 0; f < nf; f++) {   // wave-uniform
     v3 p;
     m3 R;
-    osc_frame_pose(s, Q.fr[f], &p, &R);
+    body_frame_pose(s, Q.fr[f], &p, &R);   // (the host half lets no world-fixed frame through)
+    p = frame_point(p, R, Q.fr[f]);
     const v3 pt = ld3(Q.target_pos + ((size_t)env * nf + f) * 3);
     const unsigned axes = T.axes[f];
     float qd[4] = {1.f, 0.f, 0.f, 0.f};   // (no rotational row: the quaternions are not read, they may be missing)
@@ -284,19 +224,7 @@ JDEV void run_osc_task(const JacoOscTaskArgs& T_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(12)
-__global__ __launch_bounds__(64, 4) void jaco_osc_task_kernel(JacoOscTaskArgs T) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= T.o.nenv) return;
-  run_osc_task(T, s, env, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(osc_task, JacoOscTaskArgs, Q.o.nenv, run_osc_task)
+#else
+JACO_DECLARE_ENTRY(osc_task, JacoOscTaskArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_osc_task(unsigned grid, hipStream_t st, const JacoOscTaskArgs& T);
-#if defined(JACO_TU) && JACO_TU == 12
-void jaco_launch_osc_task(unsigned grid, hipStream_t st, const JacoOscTaskArgs& T) { hipLaunchKernelGGL(jaco_osc_task_kernel, dim3(grid), dim3(64), 0, st, T); }
-#endif
-#endif
-
-#include "joint.h"

@@ -260,6 +260,17 @@ JDEV const JacoStepArgs* args_view(const JacoStepArgs&) {
   return (const JacoStepArgs*)p;
 }
 #endif
+// The same for the argument block of any other kernel that takes its block as its only parameter (the entries of entry_common.h): an
+// s_load or a global load per use, where a by-value parameter under a dynamic index would be copied to scratch.
+template <class T>
+JDEV const T* kernarg_view(const T& A) {
+#ifdef JACO_EMULATED
+  return &A;
+#else
+  typedef const T __attribute__((address_space(4))) * KP;
+  return (const T*)(KP)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
+}
 
 // debug dump layout (floats)
 #define JDBG_XPOS 0                       // [JNB][3]
@@ -2931,9 +2942,14 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #endif
 #endif
 
-// the robot-configuration query kernel (jaco_query): translation unit 9
-#include "query.h"
-// the inverse-kinematics kernel (jaco_ik): translation unit 10
-#include "ik.h"
-// the operational-space controller kernel (jaco_osc): translation unit 11
-#include "osc.h"
+// The query-style entries, one kernel and one translation unit each, in the order in which they build on one another.
+#include "entry_common.h"   // what they share
+#include "query.h"          //  9  jaco_query: robot-configuration queries
+#include "ik.h"             // 10  jaco_ik: inverse kinematics
+#include "osc.h"            // 11  jaco_osc: the operational-space controller
+#include "osc_task.h"       // 12  jaco_osc_task: task axes and null-space posture terms
+#include "joint.h"          // 13  jaco_joint: the joint-space controller and inverse dynamics
+#include "fd.h"             // 14  jaco_fd: forward dynamics and its linearisation
+#include "rollout.h"        // 15  jaco_rollout: open-loop rollouts
+#include "rollout_fb.h"     // 16  jaco_rollout_fb: closed-loop rollouts
+#include "lqr.h"            // 17  jaco_lqr: the iLQR / TVLQR backward pass

@@ -5,16 +5,11 @@
 // One 64-lane wavefront per env, the step kernel's own stages on the contact-free LDS type (JacoLDS<JacoArm>: its tree walk skips the
 // geom poses, nothing after the mass matrix runs): state load, model tables, tree walk, subtree sums, mass matrix + bias, then the
 // outputs.  Nothing is written back to the env's state, task row, cache, flags or sensordata.
-// Included at the end of physics_kernel.h; the kernel is translation unit 9 (kernels.hip -DJACO_TU=9).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 9 (kernels.hip -DJACO_TU=9).
 #pragma once
 #include <string>
 
 #define JQ_MAXFRAMES 16   // = JACO_QUERY_MAX_FRAMES
-struct JacoQueryFrame {   // = JacoFrame of include/jaco_env.h (static_assert in abi_agreement.h)
-  int body;               // fused body index, -1: world-fixed
-  float pos[3], mat[9];   // frame pose in that body's frame (row-major rotation)
-  float point[3];         // Jacobian reference point, in the frame's coordinates
-};
 struct JacoQueryArgs {
   const JacoModelDev* model;
   const float* qpos;      // [nenv][nq]  (the handle's hi words, or the caller's override)
@@ -42,22 +37,11 @@ static inline std::string jaco_query_resolve(const JacoModelDev& m, const JacoQu
   return std::string();
 }
 
-// The frame table is indexed per lane: read through the kernarg segment pointer (global loads) rather than the by-value parameter,
-// which a dynamic index would copy to scratch.
-#ifdef JACO_EMULATED
-JDEV const JacoQueryArgs* query_args_view(const JacoQueryArgs& Q) { return &Q; }
-#else
-JDEV const JacoQueryArgs* query_args_view(const JacoQueryArgs&) {
-  typedef const JacoQueryArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoQueryArgs*)p;
-}
-#endif
-
 template <class L>
 JDEV void run_query(const JacoQueryArgs& Q_, L& s, int env, int lane) {
-  const JacoQueryArgs* Qp = query_args_view(Q_);
-  const JacoQueryArgs& Q = *Qp;
+  // The frame table is indexed per lane: read through the kernarg segment pointer (global loads) rather than the by-value parameter,
+  // which a dynamic index would copy to scratch.
+  const JacoQueryArgs& Q = *kernarg_view(Q_);
   const JacoModelDev* m = opaque_ptr(Q.model);
   const int nq = m->nq, nv = m->nv, nf = Q.nframes;
   // the prologue of run_env, state and model tables only: the state is exactly the floats handed in (low-order words zero)
@@ -115,17 +99,7 @@ JDEV void run_query(const JacoQueryArgs& Q_, L& s, int env, int lane) {
 }
 
 #if JACO_TU_HAS(9)
-__global__ __launch_bounds__(64, 4) void jaco_query_kernel(JacoQueryArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int env = (int)blockIdx.x;
-  if (env >= Q.nenv) return;
-  run_query(Q, s, env, (int)threadIdx.x);
-}
-#endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_query(unsigned grid, hipStream_t st, const JacoQueryArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 9
-void jaco_launch_query(unsigned grid, hipStream_t st, const JacoQueryArgs& Q) { hipLaunchKernelGGL(jaco_query_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
+JACO_DEFINE_ENTRY(query, JacoQueryArgs, Q.nenv, run_query)
+#else
+JACO_DECLARE_ENTRY(query, JacoQueryArgs)
 #endif

@@ -17,9 +17,10 @@
 // Fan-out: rollout i starts from state row state_idx[i] (NULL: row i); an index outside [0, nstates) writes the status word
 // JROLLOUT_BAD_INDEX and nothing else.
 // No LDS beyond the step's, no scratch memory.  Nothing of a handle is read but the model (and its fp32 state when no override is given).
-// Included at the end of fd.h; the kernel is translation unit 15 (kernels.hip -DJACO_TU=15).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 15 (kernels.hip -DJACO_TU=15).
 #pragma once
 #include <string>
+#include <type_traits>
 
 #define JROLLOUT_MAX_SUBSTEPS 16384   // = JACO_ROLLOUT_MAX_SUBSTEPS
 #define JROLLOUT_BAD_INDEX 0x80000u   // = JACO_ROLLOUT_BAD_INDEX
@@ -75,45 +76,18 @@ static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const Jaco
                                       "at least one of the outputs qpos, qvel, xpos and xmat is required", Q);
 }
 
-// (as fd_args_view)
-#ifdef JACO_EMULATED
-JDEV const JacoRolloutArgs* rollout_args_view(const JacoRolloutArgs& Q) { return &Q; }
-#else
-JDEV const JacoRolloutArgs* rollout_args_view(const JacoRolloutArgs&) {
-  typedef const JacoRolloutArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoRolloutArgs*)p;
-}
-#endif
-
-// The first half of a substep: the tree walk and the zeroing of s.M.  Leaves the body poses of the current state in s.xpos / s.xmat.
-template <class L>
-JDEV void rollout_walk(const JacoModelDev* m, L& s, int lane) {
-  stage_walk(m, s, lane, false);
-  for (int i = lane; i < JMBLK; i += 64) s.M[i] = 0.f;
-  wave_sync();
-}
-
-// The rest of the substep, from the subtree sums to the position update: run_env's contact-free substep body, stage by stage.
+// A substep after its first half (entry_walk: the tree walk and the zeroing of s.M), from the subtree sums to the position update:
+// run_env's contact-free substep body, stage by stage.
 template <class L>
 JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags) {
   const int nv = m->nv;
   const ActParams actp = act_fetch(m, lane);
-  const StagePrefetch pf = stage_prefetch(m, lane);
-  stage_accumulate(m, s, lane);
-  wave_sync();
-  stage_mass_bias(m, s, lane, pf);
-  wave_sync();
+  const StagePrefetch pf = entry_mass_bias(m, s, lane);
   stage_actuation(m, s, lane, actp);
   stage_limit_rows(m, s, lane, pf);
   wave_sync();
-  float mrow[JNV], h[JNV];   // row `lane` of the block-diagonal mass matrix (as run_env loads it: zero rows for lanes >= nv)
-  {
-    const int blo = lane < JB0 ? 0 : (lane < JB1 ? JB0 : JB1), bn = lane < JB0 ? JB0 : (lane < JB1 ? JB1 - JB0 : JNV - JB1);
-    const int rbase = lane < nv ? m_index(lane, blo) : 0;
-#pragma unroll
-    for (int j = 0; j < JNV; j++) { const bool in = lane < nv && j >= blo && j < blo + bn; mrow[j] = in ? s.M[in ? rbase + j - blo : 0] : 0.f; }
-  }
+  float mrow[JNV], h[JNV];
+  mass_row(mrow, s, lane, nv);
   const float smooth = lane < nv ? s.smooth[lane] : 0.f;
   wave_sync();
   const float hdamp = (m->has_damping && lane < nv) ? m->timestep * pf.damping : 0.f;
@@ -149,19 +123,13 @@ JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags
   wave_sync();
 }
 
-// The frame's pose at the body poses in s.xpos / s.xmat (run_query's composition: xpos_b + R_b p, R_b R_f) into row `row` of the pose
-// outputs: every lane composes it, lane k stores word k.
+// The frame's pose at the body poses in s.xpos / s.xmat (run_query's: frame_pose) into row `row` of the pose outputs: every lane
+// composes it (the world-fixed case is wave-uniform), lane k stores word k.
 template <class L>
 JDEV void rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lane) {
-  const JacoQueryFrame& F = Q.fr;
-  const int b = F.body;
-  v3 p = ld3(F.pos);
-  m3 R = ldm(F.mat);
-  if (b >= 0) {   // (wave-uniform)
-    const m3 Rb = ldm(s.xmat[b]);
-    p = ld3(s.xpos[b]) + mul(Rb, ld3(F.pos));
-    R = mul(Rb, ldm(F.mat));
-  }
+  v3 p;
+  m3 R;
+  frame_pose(s, Q.fr, &p, &R);
   float w = lane == 0 ? p.x : (lane == 1 ? p.y : p.z), r = 0.f;
 #pragma unroll
   for (int k = 0; k < 9; k++) if (lane == k) r = R.m[k];
@@ -169,87 +137,87 @@ JDEV void rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lan
   if (Q.xmat && lane < 9) Q.xmat[row * 9 + lane] = r;
 }
 
-// The prologue of a rollout (run_query's): state row `src` into LDS exactly as the floats handed in (low-order words zero), a zero warm
-// start, the model staged once.
+// The closed-loop kernel's block and law (rollout_fb.h), which the one loop below serves too.
+struct JacoRolloutFbArgs;
 template <class L>
-JDEV void rollout_prologue(const JacoRolloutArgs* Qp, const JacoModelDev* m, L& s, int src, int lane) {
-  const int nq = m->nq, nv = m->nv;
-  if (lane < nq) { s.qpos[lane] = Qp->qpos0[(size_t)src * nq + lane]; s.qpos_lo[lane] = 0.f; }
-  if (lane < nv) { s.qvel[lane] = Qp->qvel0[(size_t)src * nv + lane]; s.qvel_lo[lane] = 0.f; s.qacc_ws[lane] = 0.f; }
-  stage_model(m, s, lane);
-  if (lane == 0) { s.ncon = 0; s.nefc = 0; s.ncand = 0; s.nlimit = 0; s.nsphere = 0; s.nside = 0; s.nside_cand = 0; }   // (LDS is not zeroed between workgroups)
-  wave_sync();
+JDEV void rollout_fb_law(const JacoRolloutFbArgs* Q, const JacoModelDev* m, L& s, int i, int p, int k, size_t erow, int lane);
+template <class A> inline constexpr bool rollout_closed = std::is_same<A, JacoRolloutFbArgs>::value;
+// the JacoRolloutArgs of either block: the block itself, or the closed-loop block's R
+template <class A>
+JDEV const JacoRolloutArgs* rollout_block(const A* Q) {
+  if constexpr (rollout_closed<A>) return &Q->R; else return Q;
 }
 
-// The lanes' sticky flags, or-reduced over the wavefront into rollout i's status word.
-JDEV void rollout_status(const JacoRolloutArgs* Qp, unsigned flags, int i, int lane) {
-  if (Qp->status) {
-    unsigned f = flags;
-    for (int o = 1; o < 64; o <<= 1) f |= (unsigned)wave_shfl_i((int)f, lane ^ o);
-    if (lane == 0) Qp->status[i] = f;
-  }
-}
-
-template <class L>
-JDEV void run_rollout(const JacoRolloutArgs& Q_, L& s, int i, int lane) {
-  const JacoRolloutArgs* Qp = rollout_args_view(Q_);
-  const JacoModelDev* m = opaque_ptr(Qp->model);
+// The knot x hold loop of rollout i, for jaco_rollout (A = JacoRolloutArgs) and jaco_rollout_fb (A = JacoRolloutFbArgs).  The two differ
+// in where a knot's ctrl comes from -- its row of the ctrl sequences, loaded once per knot, or rollout_fb_law evaluated on the state in
+// LDS, per knot or per substep -- and in the closed-loop kernel's plan index.
+template <class A, class L>
+JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
+  constexpr bool closed = rollout_closed<A>;
+  const A* Qp = kernarg_view(Q_);
+  const JacoRolloutArgs* R = rollout_block(Qp);
+  const JacoModelDev* m = opaque_ptr(R->model);
   const int nq = m->nq, nv = m->nv, nu = m->nu;
-  const int src = wave_uniform_i(Qp->state_idx ? Qp->state_idx[i] : i);
-  if (src < 0 || src >= Qp->nstates) {   // (as jaco_load_envs: neither a fault nor silence)
-    if (lane == 0 && Qp->status) Qp->status[i] = JROLLOUT_BAD_INDEX;
+  const int src = wave_uniform_i(R->state_idx ? R->state_idx[i] : i);
+  int p = 0;
+  bool bad = src < 0 || src >= R->nstates;
+  if constexpr (closed) {
+    p = wave_uniform_i(Qp->plan.plan_idx ? Qp->plan.plan_idx[i] : i);
+    bad = bad || p < 0 || p >= Qp->plan.nplans;
+  }
+  if (bad) {   // (as jaco_load_envs: neither a fault nor silence)
+    if (lane == 0 && R->status) R->status[i] = JROLLOUT_BAD_INDEX;
     return;
   }
-  rollout_prologue(Qp, m, s, src, lane);
+  // the state row exactly as the floats handed in, a zero warm start, the model staged once
+  entry_state<ENTRY_SUBSTEPS>(m, s, R->qpos0, R->qvel0, nullptr, src, lane);
   unsigned flags = 0u;
-  const int nknots = Qp->nknots, hold = Qp->hold;
-  const bool every = Qp->final_only == 0, pose = Qp->xpos != nullptr || Qp->xmat != nullptr;
+  const int nknots = R->nknots, hold = R->hold;
+  const bool every = R->final_only == 0, pose = R->xpos != nullptr || R->xmat != nullptr;
+  bool each = false;
+  if constexpr (closed) each = Qp->per_substep != 0;
 #pragma nounroll
   for (int k = 0; k < nknots; k++) {
-    if (lane < nu) s.ctrl[lane] = Qp->ctrl[((size_t)i * nknots + k) * nu + lane];
-    wave_sync();
+    if constexpr (!closed) {
+      if (lane < nu) s.ctrl[lane] = R->ctrl[((size_t)i * nknots + k) * nu + lane];
+      wave_sync();
+    }
 #pragma nounroll
     for (int sub = 0; sub < hold; sub++) {
       // (as run_env's substep loop and fd_pass: the argument block is read afresh, and with the pointer's provenance and the lane id
       // hidden the optimiser cannot hoist the substep's model loads and lane-derived addresses out of the loop and keep them alive,
       // spilled, across all of it)
-      Qp = rollout_args_view(Q_);
-      m = opaque_ptr(Qp->model);
+      Qp = kernarg_view(Q_);
+      R = rollout_block(Qp);
+      m = opaque_ptr(R->model);
       lane = wave_opaque_i(lane);
-      rollout_walk(m, s, lane);
-      if (pose && every && sub == 0 && k > 0) rollout_pose(*Qp, s, (size_t)i * nknots + (k - 1), lane);   // the previous knot's pose: this walk's
+      if constexpr (closed) {
+        if (each || sub == 0) rollout_fb_law(Qp, m, s, i, p, k, each ? ((size_t)i * nknots + k) * hold + sub : (size_t)i * nknots + k, lane);
+      }
+      entry_walk(m, s, lane);
+      if (pose && every && sub == 0 && k > 0) rollout_pose(*R, s, (size_t)i * nknots + (k - 1), lane);   // the previous knot's pose: this walk's
       rollout_substep(m, s, lane, flags);
     }
     if (every || k == nknots - 1) {
       const size_t row = every ? (size_t)i * nknots + k : (size_t)i;
-      if (Qp->qpos && lane < nq) Qp->qpos[row * nq + lane] = s.qpos[lane];
-      if (Qp->qvel && lane < nv) Qp->qvel[row * nv + lane] = s.qvel[lane];
+      if (R->qpos && lane < nq) R->qpos[row * nq + lane] = s.qpos[lane];
+      if (R->qvel && lane < nv) R->qvel[row * nv + lane] = s.qvel[lane];
     }
   }
-  Qp = rollout_args_view(Q_);
+  R = rollout_block(kernarg_view(Q_));
   if (pose) {   // the last knot's pose needs a walk of its own
-    stage_walk(opaque_ptr(Qp->model), s, lane, false);
+    stage_walk(opaque_ptr(R->model), s, lane, false);
     wave_sync();
-    rollout_pose(*Qp, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
+    rollout_pose(*R, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
   }
-  rollout_status(Qp, flags, i, lane);
+  if (R->status) {   // the lanes' sticky flags, or-reduced over the wavefront
+    const unsigned f = wave_or(flags);
+    if (lane == 0) R->status[i] = f;
+  }
 }
 
 #if JACO_TU_HAS(15)
-__global__ __launch_bounds__(64, 4) void jaco_rollout_kernel(JacoRolloutArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int i = (int)blockIdx.x;
-  if (i >= Q.n) return;
-  run_rollout(Q, s, i, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(rollout, JacoRolloutArgs, Q.n, run_rollout)
+#else
+JACO_DECLARE_ENTRY(rollout, JacoRolloutArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 15
-void jaco_launch_rollout(unsigned grid, hipStream_t st, const JacoRolloutArgs& Q) { hipLaunchKernelGGL(jaco_rollout_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
-#endif
-
-// the closed-loop rollout kernel (jaco_rollout_fb): translation unit 16
-#include "rollout_fb.h"

@@ -1,9 +1,9 @@
 // Batched closed-loop rollouts (jaco_rollout_fb, include/jaco_env.h): jaco_rollout with the ctrl of knot k computed inside the kernel from
 // the state at knot k -- the forward pass of iLQR and its line search, a plan tracked with TVLQR gains, PD tracking of a joint trajectory.
 //
-// One 64-lane wavefront per rollout on JacoLDS<JacoArm>, the whole knot x hold loop in the one launch: run_rollout of rollout.h with its
-// prologue, rollout_walk, rollout_substep, rollout_pose and status reduction called as they are.  The one thing that differs is where
-// run_rollout loads the knot's ctrl row into s.ctrl: here the feedback law is evaluated from the state in LDS.
+// One 64-lane wavefront per rollout on JacoLDS<JacoArm>, the whole knot x hold loop in the one launch: run_rollout of rollout.h itself,
+// instantiated on this kernel's argument block -- the same prologue, substep, pose and status reduction.  The one thing that differs is
+// where run_rollout loads the knot's ctrl row into s.ctrl: here the feedback law is evaluated from the state in LDS.
 //
 // THE LAW (the order of operations is part of the interface: tests recompute it).  Rollout i follows plan p = plan_idx[i] (NULL: i); at
 // an evaluation in knot k, with nd = ndofs and nx = 2 nd:
@@ -19,9 +19,9 @@
 // Mapping: lane j < nx forms d_j in a register; lane a < nu accumulates u_a, fetching d_j with wave_bcast (j is wave-uniform) and reading
 // its gain row gain[p][k][a][0 .. nx) -- contiguous -- at the point of use, all of it in flight before the first fma.  Nothing of the law lives across a substep; no LDS beyond the
 // step's, no scratch memory.  The options (the dof list included) and the frame travel by value in the kernel arguments, re-read through
-// rollout_fb_args_view per substep as run_rollout does and for the reason written there.
+// kernarg_view per substep by run_rollout, for the reason written there.
 // A state_idx or plan_idx entry out of range writes the status word JROLLOUT_BAD_INDEX and nothing else.
-// Included at the end of rollout.h; the kernel is translation unit 16 (kernels.hip -DJACO_TU=16).
+// Listed at the tail of physics_kernel.h; the kernel is translation unit 16 (kernels.hip -DJACO_TU=16).
 #pragma once
 
 #define JROLLOUT_FB_MAX_DOFS 18   // = JACO_ROLLOUT_FB_MAX_DOFS
@@ -85,17 +85,6 @@ static inline std::string jaco_rollout_fb_resolve(const JacoModelDev& m, const J
   return std::string();
 }
 
-// (as rollout_args_view)
-#ifdef JACO_EMULATED
-JDEV const JacoRolloutFbArgs* rollout_fb_args_view(const JacoRolloutFbArgs& Q) { return &Q; }
-#else
-JDEV const JacoRolloutFbArgs* rollout_fb_args_view(const JacoRolloutFbArgs&) {
-  typedef const JacoRolloutFbArgs __attribute__((address_space(4))) * KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  return (const JacoRolloutFbArgs*)p;
-}
-#endif
-
 // One evaluation of the law (the header's order of operations) for rollout i on plan p at knot k, into s.ctrl and row `erow` of the ctrl
 // output.  Every lane runs the j loop: wave_bcast is a wavefront operation.
 template <class L>
@@ -134,64 +123,9 @@ JDEV void rollout_fb_law(const JacoRolloutFbArgs* Q, const JacoModelDev* m, L& s
   wave_sync();
 }
 
-template <class L>
-JDEV void run_rollout_fb(const JacoRolloutFbArgs& Q_, L& s, int i, int lane) {
-  const JacoRolloutFbArgs* Qp = rollout_fb_args_view(Q_);
-  const JacoModelDev* m = opaque_ptr(Qp->R.model);
-  const int nq = m->nq, nv = m->nv;
-  const int src = wave_uniform_i(Qp->R.state_idx ? Qp->R.state_idx[i] : i);
-  const int p = wave_uniform_i(Qp->plan.plan_idx ? Qp->plan.plan_idx[i] : i);
-  if (src < 0 || src >= Qp->R.nstates || p < 0 || p >= Qp->plan.nplans) {   // (as run_rollout: neither a fault nor silence)
-    if (lane == 0 && Qp->R.status) Qp->R.status[i] = JROLLOUT_BAD_INDEX;
-    return;
-  }
-  rollout_prologue(&Qp->R, m, s, src, lane);
-  unsigned flags = 0u;
-  const int nknots = Qp->R.nknots, hold = Qp->R.hold;
-  const bool every = Qp->R.final_only == 0, pose = Qp->R.xpos != nullptr || Qp->R.xmat != nullptr, each = Qp->per_substep != 0;
-#pragma nounroll
-  for (int k = 0; k < nknots; k++) {
-#pragma nounroll
-    for (int sub = 0; sub < hold; sub++) {
-      // (as run_rollout's substep loop: the argument block is read afresh, the pointer's provenance and the lane id hidden)
-      Qp = rollout_fb_args_view(Q_);
-      m = opaque_ptr(Qp->R.model);
-      lane = wave_opaque_i(lane);
-      if (each || sub == 0) rollout_fb_law(Qp, m, s, i, p, k, each ? ((size_t)i * nknots + k) * hold + sub : (size_t)i * nknots + k, lane);
-      rollout_walk(m, s, lane);
-      if (pose && every && sub == 0 && k > 0) rollout_pose(Qp->R, s, (size_t)i * nknots + (k - 1), lane);   // the previous knot's pose: this walk's
-      rollout_substep(m, s, lane, flags);
-    }
-    if (every || k == nknots - 1) {
-      const size_t row = every ? (size_t)i * nknots + k : (size_t)i;
-      if (Qp->R.qpos && lane < nq) Qp->R.qpos[row * nq + lane] = s.qpos[lane];
-      if (Qp->R.qvel && lane < nv) Qp->R.qvel[row * nv + lane] = s.qvel[lane];
-    }
-  }
-  Qp = rollout_fb_args_view(Q_);
-  if (pose) {   // the last knot's pose needs a walk of its own
-    stage_walk(opaque_ptr(Qp->R.model), s, lane, false);
-    wave_sync();
-    rollout_pose(Qp->R, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
-  }
-  rollout_status(&Qp->R, flags, i, lane);
-}
-
+// (the kernel: run_rollout of rollout.h on this block)
 #if JACO_TU_HAS(16)
-__global__ __launch_bounds__(64, 4) void jaco_rollout_fb_kernel(JacoRolloutFbArgs Q) {
-  __shared__ JacoLDS<JacoArm> s;
-  const int i = (int)blockIdx.x;
-  if (i >= Q.R.n) return;
-  run_rollout_fb(Q, s, i, (int)threadIdx.x);
-}
+JACO_DEFINE_ENTRY(rollout_fb, JacoRolloutFbArgs, Q.R.n, run_rollout)
+#else
+JACO_DECLARE_ENTRY(rollout_fb, JacoRolloutFbArgs)
 #endif
-
-#ifndef JACO_EMULATED
-void jaco_launch_rollout_fb(unsigned grid, hipStream_t st, const JacoRolloutFbArgs& Q);
-#if defined(JACO_TU) && JACO_TU == 16
-void jaco_launch_rollout_fb(unsigned grid, hipStream_t st, const JacoRolloutFbArgs& Q) { hipLaunchKernelGGL(jaco_rollout_fb_kernel, dim3(grid), dim3(64), 0, st, Q); }
-#endif
-#endif
-
-// the iLQR / TVLQR backward pass kernel (jaco_lqr): translation unit 17
-#include "lqr.h"

@@ -17,6 +17,21 @@ class JacoError(RuntimeError):
     pass
 
 
+def _rows(t, dev, n, rows=-1):
+    """t as a contiguous fp32 [rows, n] tensor on dev (rows -1: as many as it holds), or None."""
+    return None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(rows, n).contiguous()
+
+
+def _ptr(t):
+    """A tensor's device pointer, or None."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _ref(rec):
+    """The address of a ctypes record (or of an array of them), as the C ABI's untyped pointer."""
+    return ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p)
+
+
 class Contacts:
     """One contact record (BatchedMujoco.contacts): the fields of include/jaco_env.h JacoContact as [B, K, ...] device tensors."""
 
@@ -187,11 +202,9 @@ class BatchedMujoco:
         want = {"xpos": (xpos, (B, nf, 3)), "xmat": (xmat, (B, nf, 9)), "jac": (jac, (B, nf, 6, self.nv)), "qM": (qM, (B, self.nv, self.nv)),
                 "qfrc_bias": (qfrc_bias, (B, self.nv))}
         res = {k: torch.empty(shape, device=dev) for k, (on, shape) in want.items() if on}
-        ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
-        out = _lib.JacoQueryOut(ptr("xpos"), ptr("xmat"), ptr("jac"), ptr("qM"), ptr("qfrc_bias"))
+        out = _lib.JacoQueryOut(*[_ptr(res.get(k)) for k in want])
         arr = (_lib.JacoFrame * max(nf, 1))(*frames)
-        self._chk(self.L.jaco_query(self.h, ctypes.cast(arr, ctypes.c_void_p), nf, self._dev(qpos, self.nq), self._dev(qvel, self.nv),
-                                    ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        self._chk(self.L.jaco_query(self.h, _ref(arr), nf, self._dev(qpos, self.nq), self._dev(qvel, self.nv), _ref(out), self._stream()))
         return res
 
     # ---- inverse kinematics (jaco_ik: a damped least-squares solve per env, one launch)
@@ -202,17 +215,15 @@ class BatchedMujoco:
         current stream; {"qpos": [B, nq] the seed with the active dofs replaced, "converged": [B] bool, "iters": [B] int32, "err_pos" /
         "err_rot": [B] the last |e_p| / |e_r|}.  The sim's state is not touched: apply the result with set_state."""
         B, dev = self.num_envs, self.device
-        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
-        tp, tq, seed = prep(target_pos, 3), prep(target_quat, 4), prep(qpos, self.nq)
+        tp, tq, seed = _rows(target_pos, dev, 3, B), _rows(target_quat, dev, 4, B), _rows(qpos, dev, self.nq, B)
         if tp is None:
             raise ValueError("ik: target_pos is required")
         out = torch.empty(B, self.nq, device=dev)
         resid = torch.empty(B, 2, device=dev)
         status = torch.empty(B, 2, dtype=torch.int32, device=dev)
         opt = _lib.JacoIkOptions(**options)
-        self._chk(self.L.jaco_ik(self.h, ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                                 self._dev(seed, self.nq), self._dev(tp, 3), self._dev(tq, 4), ctypes.c_void_p(out.data_ptr()),
-                                 ctypes.c_void_p(resid.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream()))
+        self._chk(self.L.jaco_ik(self.h, _ref(frame), _ref(opt), self._dev(seed, self.nq), self._dev(tp, 3), self._dev(tq, 4), _ptr(out),
+                                 _ptr(resid), _ptr(status), self._stream()))
         return {"qpos": out, "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
 
     # ---- operational-space controller (jaco_osc: abr_control's OSC.generate per env and frame, one launch)
@@ -232,21 +243,20 @@ class BatchedMujoco:
         if isinstance(frames, _lib.JacoFrame):
             frames = [frames]
         nf, B, dev = len(frames), self.num_envs, self.device
-        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
-        tp, tq = prep(target_pos, 3 * nf), prep(target_quat, 4 * nf)
-        q, v, cin = prep(qpos, self.nq), prep(qvel, self.nv), prep(ctrl, self.nu)
+        tp, tq = _rows(target_pos, dev, 3 * nf, B), _rows(target_quat, dev, 4 * nf, B)
+        q, v, cin = _rows(qpos, dev, self.nq, B), _rows(qvel, dev, self.nv, B), _rows(ctrl, dev, self.nu, B)
         out = torch.empty(B, self.nu, device=dev)
         status = torch.empty(B, max(nf, 1), dtype=torch.int32, device=dev)
         opt = _lib.JacoOscOptions(**options)
         arr = (_lib.JacoFrame * max(nf, 1))(*frames)
-        head = (self.h, ctypes.cast(arr, ctypes.c_void_p), nf, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p))
-        tail = (self._dev(cin, self.nu), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream())
+        head = (self.h, _ref(arr), nf, _ref(opt))
+        tail = (self._dev(cin, self.nu), _ptr(out), _ptr(status), self._stream())
         if axes is None and null_kv == 0.0 and rest_qpos is None and rest_kp == 0.0 and rest_kv == 0.0 and rest_mask == 0:
             self._chk(self.L.jaco_osc(*head, self._dev(q, self.nq), self._dev(v, self.nv), self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), *tail))
         else:
-            rest = prep(rest_qpos, self.nq)
+            rest = _rows(rest_qpos, dev, self.nq, B)
             task = _lib.JacoOscTask(axes=_lib.osc_axes(axes, nf), null_kv=null_kv, rest_kp=rest_kp, rest_kv=rest_kv, rest_mask=rest_mask)
-            self._chk(self.L.jaco_osc_task(*head, ctypes.cast(ctypes.pointer(task), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
+            self._chk(self.L.jaco_osc_task(*head, _ref(task), self._dev(q, self.nq), self._dev(v, self.nv),
                                            self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(rest, self.nq), *tail))
         return {"ctrl": out, "singular": status != 0}
 
@@ -262,29 +272,25 @@ class BatchedMujoco:
         is inverse dynamics; kp = kv = 0 with nothing else is bias compensation.  One launch on the current stream, no synchronisation;
         returns the ctrl tensor [B, nu].  The sim's state is not touched: apply the result with send_forces."""
         B, dev = self.num_envs, self.device
-        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
-        tq, tv, ff = prep(target_qpos, self.nq), prep(target_qvel, self.nv), prep(qacc, self.nv)
-        q, v, cin = prep(qpos, self.nq), prep(qvel, self.nv), prep(ctrl, self.nu)
+        tq, tv, ff = _rows(target_qpos, dev, self.nq, B), _rows(target_qvel, dev, self.nv, B), _rows(qacc, dev, self.nv, B)
+        q, v, cin = _rows(qpos, dev, self.nq, B), _rows(qvel, dev, self.nv, B), _rows(ctrl, dev, self.nu, B)
         out = torch.empty(B, self.nu, device=dev)
         opt = _lib.JacoJointOptions(**options)
-        self._chk(self.L.jaco_joint(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
-                                    self._dev(tq, self.nq), self._dev(tv, self.nv), self._dev(ff, self.nv), self._dev(cin, self.nu),
-                                    ctypes.c_void_p(out.data_ptr()), self._stream()))
+        self._chk(self.L.jaco_joint(self.h, _ref(opt), self._dev(q, self.nq), self._dev(v, self.nv),
+                                    self._dev(tq, self.nq), self._dev(tv, self.nv), self._dev(ff, self.nv), self._dev(cin, self.nu), _ptr(out), self._stream()))
         return out
 
     # ---- forward dynamics and its linearisation (jaco_fd: qacc_smooth of a forward pass and its derivatives per env, one launch)
     def _fd(self, ctrl, qpos, qvel, want, **options):
         """One jaco_fd launch: {name: tensor} of the outputs in `want` (names of JacoFdOut), in the C ABI's layout."""
         B, dev = self.num_envs, self.device
-        prep = lambda t, n: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(B, n).contiguous()
-        c, q, v = prep(ctrl, self.nu), prep(qpos, self.nq), prep(qvel, self.nv)
+        c, q, v = _rows(ctrl, dev, self.nu, B), _rows(qpos, dev, self.nq, B), _rows(qvel, dev, self.nv, B)
         shapes = {"qacc": (B, self.nv), "qfrc_smooth": (B, self.nv), "dqacc_dqpos": (B, self.nv, self.nv), "dqacc_dqvel": (B, self.nv, self.nv),
                   "dqacc_dctrl": (B, self.nu, self.nv)}
         res = {k: torch.empty(shapes[k], device=dev) for k in want}
-        out = _lib.JacoFdOut(*[ctypes.c_void_p(res[k].data_ptr()) if k in res else None for k in shapes])
+        out = _lib.JacoFdOut(*[_ptr(res.get(k)) for k in shapes])
         opt = _lib.JacoFdOptions(**options)
-        self._chk(self.L.jaco_fd(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), self._dev(q, self.nq), self._dev(v, self.nv),
-                                 self._dev(c, self.nu), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        self._chk(self.L.jaco_fd(self.h, _ref(opt), self._dev(q, self.nq), self._dev(v, self.nv), self._dev(c, self.nu), _ref(out), self._stream()))
         return res
 
     def forward_dynamics(self, ctrl=None, qpos=None, qvel=None, implicit_damping=False, want_qfrc=False):
@@ -321,12 +327,10 @@ class BatchedMujoco:
         res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
         if n == 0:   # (no launch: jaco_rollout returns JACO_OK for n == 0)
             return res
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        out = _lib.JacoRolloutOut(*[ptr(res.get(k)) for k in shapes])
+        out = _lib.JacoRolloutOut(*[_ptr(res.get(k)) for k in shapes])
         opt = _lib.JacoRolloutOptions(**options)
-        self._chk(self.L.jaco_rollout(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                                      None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, ptr(state_index), int(nstates),
-                                      ptr(qpos), ptr(qvel), ptr(ctrl), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        self._chk(self.L.jaco_rollout(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
+                                      _ptr(qpos), _ptr(qvel), _ptr(ctrl), _ref(out), self._stream()))
         return res
 
     def rollout(self, ctrl, qpos=None, qvel=None, state_index=None, hold=1, frame=None, final_only=False):
@@ -345,8 +349,7 @@ class BatchedMujoco:
         if ctrl.dim() != 3 or ctrl.shape[2] != self.nu:
             raise ValueError("rollout: ctrl has shape %s, not [n, T, %d]" % (tuple(ctrl.shape), self.nu))
         n = ctrl.shape[0]
-        prep = lambda t, w: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, w).contiguous()
-        q, v = prep(qpos, self.nq), prep(qvel, self.nv)
+        q, v = _rows(qpos, dev, self.nq), _rows(qvel, dev, self.nv)
         if q is not None and v is not None and q.shape[0] != v.shape[0]:
             raise ValueError("rollout: %d qpos rows but %d qvel rows" % (q.shape[0], v.shape[0]))
         nstates = self.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
@@ -369,15 +372,12 @@ class BatchedMujoco:
         res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
         if n == 0:   # (no launch: jaco_rollout_fb returns JACO_OK for n == 0)
             return res
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        out = _lib.JacoRolloutFbOut(*[ptr(res.get(k)) for k in shapes])
-        rec = _lib.JacoRolloutPlan(ptr(plan["ctrl"]), ptr(plan.get("kff")), ptr(plan.get("gain")), ptr(plan.get("xref")), ptr(alpha), ptr(plan_index),
+        out = _lib.JacoRolloutFbOut(*[_ptr(res.get(k)) for k in shapes])
+        rec = _lib.JacoRolloutPlan(_ptr(plan["ctrl"]), _ptr(plan.get("kff")), _ptr(plan.get("gain")), _ptr(plan.get("xref")), _ptr(alpha), _ptr(plan_index),
                                    int(plan["ctrl"].shape[0]))
         opt = _lib.JacoRolloutFbOptions(**options)
-        self._chk(self.L.jaco_rollout_fb(self.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                                         None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, ptr(state_index), int(nstates),
-                                         ptr(qpos), ptr(qvel), ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p),
-                                         ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), self._stream()))
+        self._chk(self.L.jaco_rollout_fb(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
+                                         _ptr(qpos), _ptr(qvel), _ref(rec), _ref(out), self._stream()))
         return res
 
     def rollout_feedback(self, ctrl, qpos=None, qvel=None, gain=None, x_ref=None, dofs=None, feedforward=None, alpha=None, plan_index=None,
@@ -413,8 +413,7 @@ class BatchedMujoco:
                 raise ValueError("rollout_feedback: x_ref has shape %s, not [%d, %d, %d]" % (None if x_ref is None else tuple(x_ref.shape), P, T, nx))
         if alpha is not None and kff is None:
             raise ValueError("rollout_feedback: alpha needs feedforward")
-        prep = lambda t, w: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, w).contiguous()
-        q, v = prep(qpos, self.nq), prep(qvel, self.nv)
+        q, v = _rows(qpos, dev, self.nq), _rows(qvel, dev, self.nv)
         if q is not None and v is not None and q.shape[0] != v.shape[0]:
             raise ValueError("rollout_feedback: %d qpos rows but %d qvel rows" % (q.shape[0], v.shape[0]))
         nstates = self.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
@@ -434,12 +433,10 @@ class BatchedMujoco:
     def _lqr(self, opt, prob, out, n):
         """One jaco_lqr launch.  opt: the keywords of _lib.JacoLqrOptions; prob: {field of JacoLqrProblem: contiguous device tensor or
         None} plus "nprob"; out: {field of JacoLqrOut: tensor or None}, written in place."""
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         o = _lib.JacoLqrOptions(**opt)
-        p = _lib.JacoLqrProblem(*[ptr(prob.get(k)) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")], int(prob["nprob"]))
-        r = _lib.JacoLqrOut(*[ptr(out.get(k)) for k in ("gain", "kff", "dV", "Vxx0", "Vx0", "status")])
-        cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-        self._chk(self.L.jaco_lqr(self.h, cast(o), int(n), cast(p), cast(r), self._stream()))
+        p = _lib.JacoLqrProblem(*[_ptr(prob.get(k)) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")], int(prob["nprob"]))
+        r = _lib.JacoLqrOut(*[_ptr(out.get(k)) for k in ("gain", "kff", "dV", "Vxx0", "Vx0", "status")])
+        self._chk(self.L.jaco_lqr(self.h, _ref(o), int(n), _ref(p), _ref(r), self._stream()))
 
     def lqr_backward(self, A, B, lxx, luu, lux=None, lx=None, lu=None, Vxx=None, Vx=None, mu=None, problem_index=None, rows=None, rows_out=None,
                      out=None):
