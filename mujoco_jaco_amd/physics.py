@@ -194,20 +194,36 @@ class BatchedMujoco:
         return out
 
     # ---- robot-configuration queries (jaco_query; MujocoConfig: robot_config.BatchedMujocoConfig)
-    def query(self, frames, qpos=None, qvel=None, xpos=True, xmat=True, jac=True, qM=True, qfrc_bias=True):
-        """One query launch on the current stream: {"xpos": [B, nf, 3], "xmat": [B, nf, 9], "jac": [B, nf, 6, nv], "qM": [B, nv, nv],
-        "qfrc_bias": [B, nv]} (the outputs asked for) of the frames (_lib.JacoFrame list, FrameTable.jaco_frame) at the current state or at
-        the given qpos [B, nq] / qvel [B, nv].  The values of a sim.forward() on that state; the handle's state is not touched."""
+    def _query(self, frames, qpos, qvel, want):
+        """One jaco_query launch: {name: tensor} of the outputs in `want` (names of JacoQueryOut), in the C ABI's layout.  qpos [B, nq] /
+        qvel [B, nv] fp32 or None: contiguous device tensors."""
         nf, B, dev = len(frames), self.num_envs, self.device
-        want = {"xpos": (xpos, (B, nf, 3)), "xmat": (xmat, (B, nf, 9)), "jac": (jac, (B, nf, 6, self.nv)), "qM": (qM, (B, self.nv, self.nv)),
-                "qfrc_bias": (qfrc_bias, (B, self.nv))}
-        res = {k: torch.empty(shape, device=dev) for k, (on, shape) in want.items() if on}
-        out = _lib.JacoQueryOut(*[_ptr(res.get(k)) for k in want])
+        shapes = {"xpos": (B, nf, 3), "xmat": (B, nf, 9), "jac": (B, nf, 6, self.nv), "qM": (B, self.nv, self.nv), "qfrc_bias": (B, self.nv)}
+        res = {k: torch.empty(shapes[k], device=dev) for k in want}
+        out = _lib.JacoQueryOut(*[_ptr(res.get(k)) for k in shapes])
         arr = (_lib.JacoFrame * max(nf, 1))(*frames)
         self._chk(self.L.jaco_query(self.h, _ref(arr), nf, self._dev(qpos, self.nq), self._dev(qvel, self.nv), _ref(out), self._stream()))
         return res
 
+    def query(self, frames, qpos=None, qvel=None, xpos=True, xmat=True, jac=True, qM=True, qfrc_bias=True):
+        """One query launch on the current stream: {"xpos": [B, nf, 3], "xmat": [B, nf, 9], "jac": [B, nf, 6, nv], "qM": [B, nv, nv],
+        "qfrc_bias": [B, nv]} (the outputs asked for) of the frames (_lib.JacoFrame list, FrameTable.jaco_frame) at the current state or at
+        the given qpos [B, nq] / qvel [B, nv].  The values of a sim.forward() on that state; the handle's state is not touched."""
+        on = {"xpos": xpos, "xmat": xmat, "jac": jac, "qM": qM, "qfrc_bias": qfrc_bias}
+        return self._query(frames, qpos, qvel, tuple(k for k in on if on[k]))
+
     # ---- inverse kinematics (jaco_ik: a damped least-squares solve per env, one launch)
+    def _ik(self, frame, seed, target_pos, target_quat, **options):
+        """One jaco_ik launch: {"qpos": [B, nq], "resid": [B, 2] the last |e_p| / |e_r|, "status": [B, 2] int32 (iterations, converged)}.
+        seed [B, nq], target_pos [B, 3], target_quat [B, 4] fp32, seed and target_quat or None: contiguous device tensors."""
+        B, dev = self.num_envs, self.device
+        res = {"qpos": torch.empty(B, self.nq, device=dev), "resid": torch.empty(B, 2, device=dev),
+               "status": torch.empty(B, 2, dtype=torch.int32, device=dev)}
+        opt = _lib.JacoIkOptions(**options)
+        self._chk(self.L.jaco_ik(self.h, _ref(frame), _ref(opt), self._dev(seed, self.nq), self._dev(target_pos, 3), self._dev(target_quat, 4),
+                                 _ptr(res["qpos"]), _ptr(res["resid"]), _ptr(res["status"]), self._stream()))
+        return res
+
     def ik(self, frame, target_pos, target_quat=None, qpos=None, **options):
         """Which arm configuration puts `frame` (_lib.JacoFrame; FrameTable.jaco_frame(name, point=...): `point` is the controlled point)
         at target_pos [B, 3] and, if given, at the orientation target_quat [B, 4] (unit quaternions, w first)?  Seed: qpos [B, nq], default
@@ -218,15 +234,30 @@ class BatchedMujoco:
         tp, tq, seed = _rows(target_pos, dev, 3, B), _rows(target_quat, dev, 4, B), _rows(qpos, dev, self.nq, B)
         if tp is None:
             raise ValueError("ik: target_pos is required")
-        out = torch.empty(B, self.nq, device=dev)
-        resid = torch.empty(B, 2, device=dev)
-        status = torch.empty(B, 2, dtype=torch.int32, device=dev)
-        opt = _lib.JacoIkOptions(**options)
-        self._chk(self.L.jaco_ik(self.h, _ref(frame), _ref(opt), self._dev(seed, self.nq), self._dev(tp, 3), self._dev(tq, 4), _ptr(out),
-                                 _ptr(resid), _ptr(status), self._stream()))
-        return {"qpos": out, "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
+        r = self._ik(frame, seed, tp, tq, **options)
+        status, resid = r["status"], r["resid"]
+        return {"qpos": r["qpos"], "converged": status[:, 1] != 0, "iters": status[:, 0], "err_pos": resid[:, 0], "err_rot": resid[:, 1]}
 
-    # ---- operational-space controller (jaco_osc: abr_control's OSC.generate per env and frame, one launch)
+    # ---- operational-space controller (jaco_osc: abr_control's OSC.generate per env and frame, one launch; jaco_osc_task: the same
+    # with task axes and null-space terms)
+    def _osc(self, frames, qpos, qvel, target_pos, target_quat, ctrl_in, task, rest_qpos, **options):
+        """One jaco_osc launch (task None) or one jaco_osc_task launch (task: the keyword values of _lib.JacoOscTask): {"ctrl": [B, nu],
+        "status": [B, nf] int32, non-zero where the pseudo-inverse branch ran}.  qpos [B, nq], qvel [B, nv], target_pos [B, 3 nf],
+        target_quat [B, 4 nf], ctrl_in [B, nu], rest_qpos [B, nq] fp32, each but target_pos or None: contiguous device tensors."""
+        nf, B, dev = len(frames), self.num_envs, self.device
+        res = {"ctrl": torch.empty(B, self.nu, device=dev), "status": torch.empty(B, max(nf, 1), dtype=torch.int32, device=dev)}
+        opt = _lib.JacoOscOptions(**options)
+        arr = (_lib.JacoFrame * max(nf, 1))(*frames)
+        head = (self.h, _ref(arr), nf, _ref(opt))
+        state = (self._dev(qpos, self.nq), self._dev(qvel, self.nv), self._dev(target_pos, 3 * nf), self._dev(target_quat, 4 * nf))
+        tail = (self._dev(ctrl_in, self.nu), _ptr(res["ctrl"]), _ptr(res["status"]), self._stream())
+        if task is None:
+            self._chk(self.L.jaco_osc(*head, *state, *tail))
+        else:
+            rec = _lib.JacoOscTask(**task)
+            self._chk(self.L.jaco_osc_task(*head, _ref(rec), *state, self._dev(rest_qpos, self.nq), *tail))
+        return res
+
     def osc(self, frames, target_pos, target_quat=None, qpos=None, qvel=None, ctrl=None, axes=None, null_kv=0.0, rest_qpos=None, rest_kp=0.0,
             rest_kv=0.0, rest_mask=0, **options):
         """The torques that drive `frames` (one or two _lib.JacoFrame; FrameTable.jaco_frame(name, point=...): `point` is the controlled
@@ -245,22 +276,23 @@ class BatchedMujoco:
         nf, B, dev = len(frames), self.num_envs, self.device
         tp, tq = _rows(target_pos, dev, 3 * nf, B), _rows(target_quat, dev, 4 * nf, B)
         q, v, cin = _rows(qpos, dev, self.nq, B), _rows(qvel, dev, self.nv, B), _rows(ctrl, dev, self.nu, B)
-        out = torch.empty(B, self.nu, device=dev)
-        status = torch.empty(B, max(nf, 1), dtype=torch.int32, device=dev)
-        opt = _lib.JacoOscOptions(**options)
-        arr = (_lib.JacoFrame * max(nf, 1))(*frames)
-        head = (self.h, _ref(arr), nf, _ref(opt))
-        tail = (self._dev(cin, self.nu), _ptr(out), _ptr(status), self._stream())
         if axes is None and null_kv == 0.0 and rest_qpos is None and rest_kp == 0.0 and rest_kv == 0.0 and rest_mask == 0:
-            self._chk(self.L.jaco_osc(*head, self._dev(q, self.nq), self._dev(v, self.nv), self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), *tail))
+            task = None
         else:
-            rest = _rows(rest_qpos, dev, self.nq, B)
-            task = _lib.JacoOscTask(axes=_lib.osc_axes(axes, nf), null_kv=null_kv, rest_kp=rest_kp, rest_kv=rest_kv, rest_mask=rest_mask)
-            self._chk(self.L.jaco_osc_task(*head, _ref(task), self._dev(q, self.nq), self._dev(v, self.nv),
-                                           self._dev(tp, 3 * nf), self._dev(tq, 4 * nf), self._dev(rest, self.nq), *tail))
-        return {"ctrl": out, "singular": status != 0}
+            task = dict(axes=_lib.osc_axes(axes, nf), null_kv=null_kv, rest_kp=rest_kp, rest_kv=rest_kv, rest_mask=rest_mask)
+        r = self._osc(frames, q, v, tp, tq, cin, task, _rows(rest_qpos, dev, self.nq, B), **options)
+        return {"ctrl": r["ctrl"], "singular": r["status"] != 0}
 
     # ---- joint-space controller and inverse dynamics (jaco_joint: abr_control's Joint.generate per env, one launch)
+    def _joint(self, qpos, qvel, target_qpos, target_qvel, qacc_ff, ctrl_in, **options):
+        """One jaco_joint launch: ctrl [B, nu].  qpos / target_qpos [B, nq], qvel / target_qvel / qacc_ff [B, nv], ctrl_in [B, nu] fp32,
+        each or None: contiguous device tensors."""
+        out = torch.empty(self.num_envs, self.nu, device=self.device)
+        opt = _lib.JacoJointOptions(**options)
+        self._chk(self.L.jaco_joint(self.h, _ref(opt), self._dev(qpos, self.nq), self._dev(qvel, self.nv), self._dev(target_qpos, self.nq),
+                                    self._dev(target_qvel, self.nv), self._dev(qacc_ff, self.nv), self._dev(ctrl_in, self.nu), _ptr(out), self._stream()))
+        return out
+
     def joint(self, target_qpos=None, target_qvel=None, qacc=None, qpos=None, qvel=None, ctrl=None, **options):
         """The torques that drive the arm to the configuration target_qpos [B, nq] (read only at the qpos addresses of the active dofs: a
         row of ik()["qpos"] goes in as it is) with the joint velocities target_qvel [B, nv] and the feed-forward accelerations qacc
@@ -274,11 +306,7 @@ class BatchedMujoco:
         B, dev = self.num_envs, self.device
         tq, tv, ff = _rows(target_qpos, dev, self.nq, B), _rows(target_qvel, dev, self.nv, B), _rows(qacc, dev, self.nv, B)
         q, v, cin = _rows(qpos, dev, self.nq, B), _rows(qvel, dev, self.nv, B), _rows(ctrl, dev, self.nu, B)
-        out = torch.empty(B, self.nu, device=dev)
-        opt = _lib.JacoJointOptions(**options)
-        self._chk(self.L.jaco_joint(self.h, _ref(opt), self._dev(q, self.nq), self._dev(v, self.nv),
-                                    self._dev(tq, self.nq), self._dev(tv, self.nv), self._dev(ff, self.nv), self._dev(cin, self.nu), _ptr(out), self._stream()))
-        return out
+        return self._joint(q, v, tq, tv, ff, cin, **options)
 
     # ---- forward dynamics and its linearisation (jaco_fd: qacc_smooth of a forward pass and its derivatives per env, one launch)
     def _fd(self, ctrl, qpos, qvel, want, **options):

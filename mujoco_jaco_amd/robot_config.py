@@ -45,6 +45,7 @@ class FrameTable:
         self.fid = {0: -1}
         for i, r in enumerate([b for b in range(1, nbody) if self.weld[b] == b]):
             self.fid[r] = i
+        self._motor = None
 
     @classmethod
     def for_model(cls, robot_file):
@@ -95,6 +96,29 @@ class FrameTable:
             if self.M["jnt_type"][j] != kin.JNT_HINGE:
                 raise ValueError("body %r hangs from a free joint: it has no arm chain of hinge joints" % name)
         return [int(self.M["jnt_qposadr"][j]) for j in joints], [int(self.M["jnt_dofadr"][j]) for j in joints]
+
+    def hinge_joints(self, joints):
+        """Joint ids of the MJCF joint names `joints` (one name or a list of them), in the order given: each a hinge joint of the
+        model, none listed twice."""
+        M, names = self.M, self.names["joint"]
+        ids = []
+        for n in ([joints] if isinstance(joints, str) else joints):
+            if n is None or n not in names:
+                raise ValueError("unknown joint %r: the model's joints are %s" % (n, [x for x in names if x]))
+            j = names.index(n)
+            if M["jnt_type"][j] != kin.JNT_HINGE:
+                raise ValueError("joint %r is not a hinge joint" % n)
+            if j in ids:
+                raise ValueError("joint %r is listed twice" % n)
+            ids.append(j)
+        return ids
+
+    def motor_of_dof(self):
+        """{dof: index of its motor actuator} (the blob's fused actuator table; position servos are left out), built once."""
+        if self._motor is None:
+            M = self.M
+            self._motor = {int(M["jnt_dofadr"][int(j)]): a for a, (j, pos) in enumerate(zip(M["actuator_jntid"], M["actuator_position"])) if not pos}
+        return self._motor
 
 
 class ContactNames:
@@ -151,6 +175,21 @@ def mat2quat(R):
     return torch.where(q[..., :1] < 0, -q, q)
 
 
+def splice(sim, qadr, dadr, q, dq):
+    """(qpos, qvel) rows for the sim: copies of its current state with q [num_envs, len(qadr)] written at the qpos addresses qadr and dq
+    [num_envs, len(dadr)] at the dof addresses dadr (each may be None: left as it is); (None, None), the current state itself, when both
+    are None."""
+    if q is None and dq is None:
+        return None, None
+    import torch
+    qpos, qvel, _ = sim.get_state()
+    if q is not None:
+        qpos[:, qadr] = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], len(qadr))
+    if dq is not None:
+        qvel[:, dadr] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], len(dadr))
+    return qpos.contiguous(), qvel.contiguous()
+
+
 class BatchedMujocoConfig:
     """MujocoConfig (mujoco_config.py:201-447) over a BatchedMujoco: J, M, g, R, quaternion, Tx for every env at once.
 
@@ -189,11 +228,7 @@ class BatchedMujocoConfig:
                 self._cache = self.sim.query(self._frames)
                 self._cache_key = key
             return self._cache
-        import torch
-        qpos = self.sim.get_state()[0]
-        q = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], self.n_arm)
-        qpos[:, self.arm_qadr] = q
-        return self.sim.query(self._frames, qpos=qpos.contiguous())
+        return self.sim.query(self._frames, qpos=self._spliced(q, None)[0])
 
     def _cols(self, t, full):
         return t if full else t[..., self.arm]
@@ -228,12 +263,7 @@ class BatchedMujocoConfig:
         (w first), the body at that orientation.  Seed: q ([num_envs, n_arm] arm angles spliced into the current qpos, as every
         accessor's q), default the current state.  options: tol_pos, tol_rot, damping, max_step, max_iters, dof_mask (BatchedMujoco.ik).
         One jaco_ik launch; the sim's state is not touched."""
-        seed = None
-        if q is not None:
-            import torch
-            seed = self.sim.get_state()[0]
-            seed[:, self.arm_qadr] = torch.as_tensor(q, dtype=seed.dtype, device=seed.device).reshape(seed.shape[0], self.n_arm)
-            seed = seed.contiguous()
+        seed = self._spliced(q, None)[0]
         frame = self.table.jaco_frame(name, point=np.zeros(3) if x is None else np.asarray(x, np.float64).reshape(3))
         r = self.sim.ik(frame, pos, quat, seed, **options)
         return r["qpos"][:, self.arm_qadr], r["converged"]
@@ -248,15 +278,7 @@ class BatchedMujocoConfig:
 
     def _spliced(self, q, dq):
         """(qpos, qvel) rows for the sim: None where the current state is meant, else q / dq [num_envs, n_arm] spliced into it."""
-        if q is None and dq is None:
-            return None, None
-        import torch
-        qpos, qvel, _ = self.sim.get_state()
-        if q is not None:
-            qpos[:, self.arm_qadr] = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], self.n_arm)
-        if dq is not None:
-            qvel[:, self.arm] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], self.n_arm)
-        return qpos.contiguous(), qvel.contiguous()
+        return splice(self.sim, self.arm_qadr, self.arm, q, dq)
 
     def forward_dynamics(self, ctrl=None, q=None, dq=None, implicit_damping=False, full=False):
         """[num_envs, n_arm] joint accelerations that ctrl [num_envs, nu] (None: zeros) produces (full=True: all nv dofs): mj_forward's
@@ -267,23 +289,15 @@ class BatchedMujocoConfig:
     def _joint_subset(self, joints, what):
         """(dofs, qpos addresses, motor actuators) of the hinge joints `joints` (MJCF names; default: this config's arm), the actuators in
         the joints' order -- the x = [q_J, dq_J] and u of linearize and rollout_feedback."""
-        M, names = self.table.M, self.table.names["joint"]
+        M = self.table.M
         if joints is None:
             dofs, qadr = list(self.arm), list(self.arm_qadr)
         else:
-            dofs, qadr = [], []
-            for n in ([joints] if isinstance(joints, str) else joints):
-                if n is None or n not in names:
-                    raise ValueError("unknown joint %r: the model's joints are %s" % (n, [x for x in names if x]))
-                j = names.index(n)
-                if M["jnt_type"][j] != kin.JNT_HINGE:
-                    raise ValueError("joint %r is not a hinge joint" % n)
-                if int(M["jnt_dofadr"][j]) in dofs:
-                    raise ValueError("joint %r is listed twice" % n)
-                dofs.append(int(M["jnt_dofadr"][j])); qadr.append(int(M["jnt_qposadr"][j]))
+            ids = self.table.hinge_joints(joints)
+            dofs, qadr = [int(M["jnt_dofadr"][j]) for j in ids], [int(M["jnt_qposadr"][j]) for j in ids]
         if not dofs:
             raise ValueError("%s: no joint chosen" % what)
-        motor = {int(M["jnt_dofadr"][int(j)]): a for a, (j, pos) in enumerate(zip(M["actuator_jntid"], M["actuator_position"])) if not pos}
+        motor = self.table.motor_of_dof()
         return dofs, qadr, [motor[d] for d in dofs if d in motor]
 
     def linearize(self, joints=None, ctrl=None, q=None, dq=None, **steps):
@@ -549,17 +563,7 @@ class BatchedOSC:
 
     def _state(self, q, dq):
         """Full qpos / qvel rows with the controlled chains' q / dq ([B, sum of chain lengths]) spliced into the current state."""
-        if q is None and dq is None:
-            return None, None
-        import torch
-        qpos, qvel, _ = self.sim.get_state()
-        qadr = [a for c in self.chains for a in c[0]]
-        dadr = [d for c in self.chains for d in c[1]]
-        if q is not None:
-            qpos[:, qadr] = torch.as_tensor(q, dtype=qpos.dtype, device=qpos.device).reshape(qpos.shape[0], len(qadr))
-        if dq is not None:
-            qvel[:, dadr] = torch.as_tensor(dq, dtype=qvel.dtype, device=qvel.device).reshape(qvel.shape[0], len(dadr))
-        return qpos.contiguous(), qvel.contiguous()
+        return splice(self.sim, [a for c in self.chains for a in c[0]], [d for c in self.chains for d in c[1]], q, dq)
 
     def generate_pose(self, pos, quat=None, q=None, dq=None, ctrl=None):
         """ctrl [B, nu] for target positions pos [B, 3] (or [B, n_names, 3]) and unit quaternions quat [B, 4] ([B, n_names, 4]), w first;
@@ -588,23 +592,15 @@ class BatchedJoint:
     def __init__(self, robot_config, kp=50.0, kv=20.0, vmax=None, joints=None):
         self.robot_config, self.sim = robot_config, robot_config.sim
         M, names = robot_config.table.M, robot_config.table.names["joint"]
-        motor = {int(M["jnt_dofadr"][int(j)]) for j, pos in zip(M["actuator_jntid"], M["actuator_position"]) if not pos}
+        motor = robot_config.table.motor_of_dof()
         if joints is None:
             ids = sorted((j for j in range(len(names)) if M["jnt_type"][j] == kin.JNT_HINGE and int(M["jnt_dofadr"][j]) in motor),
                          key=lambda j: int(M["jnt_dofadr"][j]))
         else:
-            ids = []
-            for n in ([joints] if isinstance(joints, str) else joints):
-                if n is None or n not in names:
-                    raise ValueError("unknown joint %r: the model's joints are %s" % (n, [x for x in names if x]))
-                j = names.index(n)
-                if M["jnt_type"][j] != kin.JNT_HINGE:
-                    raise ValueError("joint %r is not a hinge joint" % n)
+            ids = robot_config.table.hinge_joints(joints)
+            for j in ids:
                 if int(M["jnt_dofadr"][j]) not in motor:
-                    raise ValueError("joint %r has no motor actuator (a position servo cannot be torque controlled)" % n)
-                if j in ids:
-                    raise ValueError("joint %r is listed twice" % n)
-                ids.append(j)
+                    raise ValueError("joint %r has no motor actuator (a position servo cannot be torque controlled)" % names[j])
         if not ids:
             raise ValueError("BatchedJoint controls no joint")
         self.joints = [names[j] for j in ids]

@@ -5,7 +5,8 @@ against a lockstep 64-lane wavefront emulator, so kernel logic can be checked ag
 without a GPU.  Not a product path: the product library refuses to run without a HIP device.
 One library per layout / build option holds every entry: ctrl-level steps (with the contact record),
 env-level calls, the eight query-style entries (tests/query_binding.py, ik_binding.py, osc_binding.py, osc_task_binding.py,
-joint_binding.py, fd_binding.py, rollout_binding.py, rollout_fb_binding.py), and one set of option switches.  lib() is the only
+joint_binding.py, fd_binding.py, rollout_binding.py, rollout_fb_binding.py; emu_sim.py puts them under BatchedMujoco's own public
+methods as one stand-in sim), and one set of option switches.  lib() is the only
 place that builds and loads such a library and declares the argument types of its emu_* entries.  The switches are process-wide
 state of a library that every entry shares: whoever flips one puts it back (try / finally), so that no test depends on what ran
 before it.

@@ -1,0 +1,107 @@
+"""BatchedMujoco on the wavefront emulator -- TEST INFRASTRUCTURE ONLY.
+
+EmuSim(model, qpos, qvel) is what robot_config (BatchedMujocoConfig, BatchedOSC, BatchedJoint) and the cases of the *_binding.py files need
+of a BatchedMujoco, on CPU tensors: every public entry method is BatchedMujoco's own, and only the eight launch methods under them are
+replaced, each by the emulated entry of its *_binding.py file.  So the CPU tier runs the product's argument handling, defaults, choice of
+entry and result shaping, and no line of them is restated here.
+
+`launches` counts the launches per C entry reached ("jaco_osc" and "jaco_osc_task" apart); `calls` holds the options of every _joint
+launch.  EmuSim() without a model serves the one entry that reads none, jaco_lqr.
+"""
+import numpy as np
+import torch
+
+import fd_binding as fb
+import ik_binding as ib
+import joint_binding as jb
+import lqr_binding as lb
+import osc_binding as ob
+import osc_task_binding as tb
+import query_binding as qb
+import rollout_binding as rb
+import rollout_fb_binding as fbb
+from mujoco_jaco_amd.physics import BatchedMujoco
+from mujoco_jaco_amd.robot_config import FrameTable
+
+ENTRIES = ("jaco_query", "jaco_ik", "jaco_osc", "jaco_osc_task", "jaco_joint", "jaco_fd", "jaco_rollout", "jaco_rollout_fb", "jaco_lqr")
+
+
+def _np(t):
+    return None if t is None else torch.as_tensor(t).numpy()
+
+
+def _tensors(r):
+    """{name: array} as CPU tensors; a status array (the bindings keep it as uint32 words) as int32."""
+    return {k: torch.from_numpy(x.view(np.int32) if x.dtype == np.uint32 else x) for k, x in r.items()}
+
+
+class EmuSim:
+    device = torch.device("cpu")
+
+    def __init__(self, model=None, qpos=None, qvel=None):
+        self.model = model
+        self.state_version = 0
+        self.launches = dict.fromkeys(ENTRIES, 0)
+        self.calls = []
+        if model is not None:
+            self.frames = FrameTable.for_model(model)
+            self.qpos, self.qvel = torch.tensor(qpos, dtype=torch.float32), torch.tensor(qvel, dtype=torch.float32)
+            self.num_envs, self.nq, self.nv, self.nu = self.qpos.shape[0], self.qpos.shape[1], self.qvel.shape[1], ob._model_info(model)[2]
+
+    def get_state(self):
+        return self.qpos.clone(), self.qvel.clone(), None
+
+    def _state(self, qpos, qvel):
+        """The rows an entry computes at, as numpy views: the ones given, else the sim's."""
+        return _np(self.qpos if qpos is None else qpos), _np(self.qvel if qvel is None else qvel)
+
+    # ---- the launches
+    def _query(self, frames, qpos, qvel, want):
+        self.launches["jaco_query"] += 1
+        return _tensors(qb.query(self.model, *self._state(qpos, qvel), frames, tuple(want)))
+
+    def _ik(self, frame, seed, target_pos, target_quat, **options):
+        self.launches["jaco_ik"] += 1
+        r = ib.ik(self.model, frame, self._state(seed, None)[0], _np(target_pos), _np(target_quat), **options)
+        return _tensors({"qpos": r["qpos"], "resid": r["resid"], "status": np.stack([r["iters"], r["converged"]], 1)})
+
+    def _osc(self, frames, qpos, qvel, target_pos, target_quat, ctrl_in, task, rest_qpos, **options):
+        args = (self.model, list(frames), *self._state(qpos, qvel), _np(target_pos), _np(target_quat), _np(ctrl_in))
+        if task is None:
+            self.launches["jaco_osc"] += 1
+            return _tensors(ob.osc(*args, **options))
+        self.launches["jaco_osc_task"] += 1
+        task = dict(task)
+        return _tensors(tb.osc_task(*args, _np(rest_qpos), raw_axes=task.pop("axes"), **task, **options))
+
+    def _joint(self, qpos, qvel, target_qpos, target_qvel, qacc_ff, ctrl_in, **options):
+        self.launches["jaco_joint"] += 1
+        self.calls.append(dict(options))
+        return torch.from_numpy(jb.joint(self.model, *self._state(qpos, qvel), _np(target_qpos), _np(target_qvel), _np(qacc_ff), _np(ctrl_in), **options))
+
+    def _fd(self, ctrl, qpos, qvel, want, **options):
+        self.launches["jaco_fd"] += 1
+        return _tensors(fb.fd(self.model, *self._state(qpos, qvel), _np(ctrl), want=tuple(want), **options))
+
+    def _rollout(self, ctrl, qpos, qvel, state_index, nstates, frame, want, **options):
+        self.launches["jaco_rollout"] += 1
+        return _tensors(rb.rollout(self.model, _np(ctrl), _np(qpos), _np(qvel), _np(state_index), nstates, frame, tuple(want), options["hold"],
+                                   options["final_only"], handle=self._state(None, None)))
+
+    def _rollout_fb(self, plan, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        self.launches["jaco_rollout_fb"] += 1
+        return _tensors(fbb.rollout_fb(self.model, _np(plan["ctrl"]), _np(qpos), _np(qvel), _np(plan.get("kff")), _np(plan.get("gain")),
+                                       _np(plan.get("xref")), options["dofs"], _np(alpha), _np(plan_index), _np(state_index), nstates, frame,
+                                       tuple(want), options["hold"], options["final_only"], options["per_substep"], handle=self._state(None, None), n=n))
+
+    def _lqr(self, opt, prob, out, n):
+        self.launches["jaco_lqr"] += 1
+        lb.lqr(opt, prob, out, n)
+
+    raw = staticmethod(lb.raw)   # (jaco_lqr as it is, for the refusals: lqr_binding.case_refusal)
+
+    # ---- everything above the launches is the product's
+    query, ik, osc, joint = BatchedMujoco.query, BatchedMujoco.ik, BatchedMujoco.osc, BatchedMujoco.joint
+    forward_dynamics, linearize = BatchedMujoco.forward_dynamics, BatchedMujoco.linearize
+    rollout, rollout_feedback, lqr_backward = BatchedMujoco.rollout, BatchedMujoco.rollout_feedback, BatchedMujoco.lqr_backward
+    _index = BatchedMujoco._index

@@ -4,8 +4,8 @@ tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRU
 Also: the fp64 references -- the oracle's qacc_smooth / qfrc_smooth after forward() at the fp32-rounded inputs, (qM + h diag(damping))^-1
 qfrc_smooth from the oracle's quantities for implicit_damping = 1, central differences of the oracle's acceleration with eps 1e-6 for
 the state derivatives, the columns of the fp64 inverse times the actuator's gate for dqacc_dctrl --, the input sets (kept off the
-actuator model's knife edges, asserted on the fp64 side), the cases shared by the CPU and the GPU tier, the refusals and a stand-in
-for BatchedMujoco.forward_dynamics / linearize backed by the emulator (CPU tests of robot_config).
+actuator model's knife edges, asserted on the fp64 side), the cases shared by the CPU and the GPU tier and the refusals.  emu_sim.EmuSim
+runs BatchedMujoco.forward_dynamics / linearize on the emulated call (CPU tests of robot_config).
 """
 import ctypes
 
@@ -344,7 +344,7 @@ def case_stepper(run):
     return verr(pred[ok], v1[ok]), (q, v, c), ok
 
 
-# ---- case 8: robot_config.linearize / forward_dynamics.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or EmuFdSim.
+# ---- case 8: robot_config.linearize / forward_dynamics.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 LIN_STEP = 1e-3
 
 
@@ -420,26 +420,3 @@ def refusal_args(case):
             "eps_qvel_inf": dict(eps_qvel=float("inf")), "beyond_nv": dict(dof_mask=(1 << 21) | 1), "free_dof": dict(dof_mask=(1 << 9) | 1),
             "implicit_2": dict(implicit_damping=2)}.get(case, {})
     return (() if case == "no_outputs" else ("qacc",)), case == "null_out", opts
-
-
-class EmuFdSim(ib.EmuIkSim):
-    """EmuIkSim plus BatchedMujoco.forward_dynamics / linearize on the emulator (CPU tensors), through the product's own methods: only
-    the one launch (_fd) is replaced."""
-    device = "cpu"
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.nu = ob._model_info(self.model)[2]
-        self.launches_fd = 0
-
-    def _fd(self, ctrl, qpos, qvel, want, **options):
-        import torch
-        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
-        self.launches_fd += 1
-        r = fd(self.model, (self.qpos if qpos is None else torch.as_tensor(qpos)).numpy(), (self.qvel if qvel is None else torch.as_tensor(qvel)).numpy(),
-               n(ctrl), want=tuple(want), **options)
-        return {k: torch.from_numpy(x) for k, x in r.items()}
-
-    from mujoco_jaco_amd.physics import BatchedMujoco as _B
-    forward_dynamics, linearize = _B.forward_dynamics, _B.linearize
-    del _B

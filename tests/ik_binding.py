@@ -2,8 +2,8 @@
 tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 numpy restatement of the algorithm on modelc.kin.fk / jac_point, the fp64 oracle's forward kinematics as the judge of a
-returned configuration, the target sets of the tests, and a stand-in for BatchedMujoco's query + ik surface backed by the emulator (CPU
-tests of robot_config.BatchedMujocoConfig.ik).
+returned configuration and the target sets of the tests.  emu_sim.EmuSim runs BatchedMujoco.ik on the emulated call (CPU tests of
+robot_config.BatchedMujocoConfig.ik).
 """
 import ctypes
 import os
@@ -172,14 +172,3 @@ def targets(model, name, point, seeds, s, seed=11, clamp=True):
         p, R, f = pose_fp64(M, body, np.asarray(point, np.float64), G[e])
         P[e], Qt[e] = p, f[1][body]
     return P.astype(np.float32), Qt.astype(np.float32), G
-
-
-class EmuIkSim(qb.EmuQuerySim):
-    """EmuQuerySim plus BatchedMujoco.ik on the emulator (CPU tensors)."""
-
-    def ik(self, frame, target_pos, target_quat=None, qpos=None, **options):
-        import torch
-        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
-        r = ik(self.model, frame, (self.qpos if qpos is None else qpos).numpy(), n(target_pos), n(target_quat), **options)
-        return {"qpos": torch.from_numpy(r["qpos"]), "converged": torch.from_numpy(r["converged"] != 0), "iters": torch.from_numpy(r["iters"]),
-                "err_pos": torch.from_numpy(r["resid"][:, 0].copy()), "err_rot": torch.from_numpy(r["resid"][:, 1].copy())}

@@ -3,8 +3,8 @@ tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRU
 
 Also: the fp64 reference -- the formula of include/jaco_env.h ("joint-space controller") written in numpy on the fp64 oracle's qM,
 qfrc_bias and qvel, read as osc_binding.reference reads them --, the input sets of the tests (targets kept off the wrap's and the
-saturation's knife edges by construction), the refusal cases, the closed loops and a stand-in for BatchedMujoco.joint backed by the
-emulator (CPU tests of robot_config.BatchedJoint).
+saturation's knife edges by construction), the refusal cases and the closed loops.  emu_sim.EmuSim runs BatchedMujoco.joint on the
+emulated call (CPU tests of robot_config.BatchedJoint).
 """
 import ctypes
 
@@ -252,23 +252,6 @@ def closed_loop_emu(q0, target_row, steps=LOOP_STEPS):
     for _ in range(steps):
         e.step(joint(LOOP_MODEL, e.qpos, e.qvel, target_row, ctrl_in=cin, **LOOP_GAINS), nsub=1, disable_contact=True)
     return e.qpos.copy()
-
-
-class EmuJointSim(ib.EmuIkSim):
-    """EmuIkSim plus BatchedMujoco.joint on the emulator (CPU tensors); `calls` records the options of every call."""
-    device = "cpu"
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.nu = ob._model_info(self.model)[2]
-        self.calls = []
-
-    def joint(self, target_qpos=None, target_qvel=None, qacc=None, qpos=None, qvel=None, ctrl=None, **options):
-        import torch
-        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
-        self.calls.append(dict(options))
-        return torch.from_numpy(joint(self.model, (self.qpos if qpos is None else qpos).numpy(), (self.qvel if qvel is None else qvel).numpy(),
-                                      n(target_qpos), n(target_qvel), n(qacc), n(ctrl), **options))
 
 
 # ---- the cases, shared by the CPU tier (run = the emulated call) and the GPU tier (run = BatchedMujoco.joint through numpy):

@@ -3,7 +3,7 @@ on demand as emu_binding.lib builds its libraries) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the input sets, the fp64 recursion (numpy, from the formulas of include/jaco_env.h) with the condition the inputs must meet
 asserted on it, the measures, and the cases shared by the CPU and the GPU tier.  A tier hands the cases a `sim`: a BatchedMujoco (GPU)
-or EmuLqrSim (the product's own lqr_backward with only the one launch replaced), and for the refusals the raw entry.
+or emu_sim.EmuSim (the product's own lqr_backward with only the one launch replaced), and for the refusals the raw entry.
 Every output is handed in filled with FILL (status: STATUS_FILL), so what a call leaves untouched shows.
 """
 import ctypes
@@ -33,47 +33,24 @@ def lib():
     return _lib[0]
 
 
-class EmuLqrLaunch:
-    """BatchedMujoco.lqr_backward on the emulator (CPU tensors): the product's own method, only the one launch (_lqr) replaced.  Mixed
-    into a stand-in sim: EmuLqrSim below, or rollout_fb_binding.EmuFbSim for the robot_config tier (config_sim)."""
-    launches_lqr = 0
-
-    def raw(self, opt, n, prob, out):
-        """The entry as it is: (return code, the message it left)."""
-        cast = lambda s: None if s is None else ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-        L = lib()
-        rc = L.emu_lqr(cast(opt), int(n), cast(prob), cast(out))
-        return rc, L.emu_last_error().decode()
-
-    def _lqr(self, opt, prob, out, n):
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        o = product_lib.JacoLqrOptions(**opt)
-        p = product_lib.JacoLqrProblem(*[ptr(prob.get(k)) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")], int(prob["nprob"]))
-        r = product_lib.JacoLqrOut(*[ptr(out.get(k)) for k in OUTS])
-        self.launches_lqr += 1
-        rc, why = self.raw(o, n, p, r)
-        if rc != 0:
-            raise ValueError("emu_lqr returned %d: %s" % (rc, why))
-
-    from mujoco_jaco_amd.physics import BatchedMujoco as _B
-    lqr_backward = _B.lqr_backward
-    del _B
+def raw(opt, n, prob, out):
+    """The entry as it is, on ctypes records (None: a NULL pointer): (return code, the message it left)."""
+    cast = lambda s: None if s is None else ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
+    L = lib()
+    rc = L.emu_lqr(cast(opt), int(n), cast(prob), cast(out))
+    return rc, L.emu_last_error().decode()
 
 
-class EmuLqrSim(EmuLqrLaunch):
-    def __init__(self):
-        import torch
-        self.device = torch.device("cpu")
-
-    def _index(self, idx):
-        import torch
-        return None if idx is None else torch.as_tensor(idx).to(dtype=torch.int32).reshape(-1).contiguous()
-
-
-def config_sim(model, q, v):
-    """make_sim of the CPU tier for case_config: rollout_fb_binding's stand-in sim plus lqr_backward."""
-    import rollout_fb_binding as fbb
-    return type("EmuIlqrSim", (EmuLqrLaunch, fbb.EmuFbSim), {})(model, q, v)
+def lqr(opt, prob, out, n):
+    """Emulated jaco_lqr on what BatchedMujoco._lqr is handed (CPU tensors), written in place.  Raises ValueError with the library's
+    message when the call is refused."""
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    o = product_lib.JacoLqrOptions(**opt)
+    p = product_lib.JacoLqrProblem(*[ptr(prob.get(k)) for k in ("A", "B", "lxx", "luu", "lux", "lx", "lu", "Vxx", "Vx", "mu", "prob_idx")], int(prob["nprob"]))
+    r = product_lib.JacoLqrOut(*[ptr(out.get(k)) for k in OUTS])
+    rc, why = raw(o, n, p, r)
+    if rc != 0:
+        raise ValueError("emu_lqr returned %d: %s" % (rc, why))
 
 
 def bits(a):
@@ -156,14 +133,15 @@ REAL_MODEL, REAL_T = "jaco2_curtain_torque", 50
 
 
 def real_inputs():
-    """The realistic set: A, B of the emulated linearize (fd_binding's sim) of the default model's nine hinge joints -- the arm's six
+    """The realistic set: A, B of the emulated linearize (emu_sim.EmuSim) of the default model's nine hinge joints -- the arm's six
     and the three fingers, whose position servos are part of A; u is the six motor words, linearize's convention -- at
     rollout_fb_binding's posture-hold states around gravity compensation, repeated over REAL_T knots, with that case's weights on the
     angles, the velocities and the torques; the gradients drawn as in the other sets.  (nx, nu) = (18, 6)."""
     import rollout_fb_binding as fbb
+    from emu_sim import EmuSim
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
     q, v = fbb.hold_postures(REAL_MODEL)
-    cfg = BatchedMujocoConfig(fbb.EmuFbSim(REAL_MODEL, q, v), ee="EE")
+    cfg = BatchedMujocoConfig(EmuSim(REAL_MODEL, q, v), ee="EE")
     M, names = cfg.table.M, cfg.table.names["joint"]
     hinge = [names[j] for j in range(len(names)) if M["jnt_type"][j] == 3]
     A, Bm, _ = cfg.linearize(joints=hinge, ctrl=cfg.joint(joints=None).gravity_compensation())
@@ -456,7 +434,7 @@ def case_refusal(sim, case):
     return why
 
 
-# ---- the robot_config tier.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or config_sim's stand-in.
+# ---- the robot_config tier.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 CONFIG_T = 12
 
 

@@ -2,8 +2,8 @@
 tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference (oracle/glue.py osc_generate on the fp64 oracle's J, M[active, active], qfrc_bias[active], point and
-quaternion), the input sets of the tests (seeds, targets, near-singular configurations), the closed loops and a stand-in for
-BatchedMujoco's osc surface backed by the emulator (CPU tests of robot_config.BatchedOSC).
+quaternion), the input sets of the tests (seeds, targets, near-singular configurations) and the closed loops.  emu_sim.EmuSim runs
+BatchedMujoco.osc on the emulated call (CPU tests of robot_config.BatchedOSC).
 """
 import ctypes
 import os
@@ -67,10 +67,8 @@ def active_dofs(model, name, dof_mask=0):
 
 
 def motor_of(model):
-    """{dof: index of its motor actuator} of the model (the blob's fused actuator table)."""
-    M = ib.load_model(model)
-    jd = np.asarray(M["jnt_dofadr"])
-    return {int(jd[int(j)]): a for a, (j, pos) in enumerate(zip(M["actuator_jntid"], M["actuator_position"])) if not pos}
+    """{dof: index of its motor actuator} of the model (FrameTable.motor_of_dof)."""
+    return ib.table_of(model).motor_of_dof()
 
 
 def reference(model, names, qpos, qvel, target6, dof_mask=0, kp=50.0, ko=180.0, kv=20.0, vmax_xyz=0.4, vmax_abg=1.0472):
@@ -284,15 +282,3 @@ def closed_loop_emu(q0, target6, steps=LOOP_STEPS):
         c = osc(LOOP_MODEL, fr, e.qpos, e.qvel, tp, tq, cin)["ctrl"]
         e.step(c, nsub=1, disable_contact=True)
     return e.qpos.copy()
-
-
-class EmuOscSim(ib.EmuIkSim):
-    """EmuIkSim plus BatchedMujoco.osc on the emulator (CPU tensors)."""
-    device = "cpu"
-
-    def osc(self, frames, target_pos, target_quat, qpos=None, qvel=None, ctrl=None, **options):
-        import torch
-        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
-        r = osc(self.model, list(frames), (self.qpos if qpos is None else qpos).numpy(), (self.qvel if qvel is None else qvel).numpy(),
-                n(target_pos), n(target_quat), n(ctrl), **options)
-        return {"ctrl": torch.from_numpy(r["ctrl"]), "singular": torch.from_numpy(r["status"] != 0)}

@@ -3,7 +3,7 @@
 
 Also: the fp64 restatement of abr_control's OSC.generate() with ctrlr_dof and null_controllers = [Damping, RestingConfig] on true
 k x k matrices (generate / reference: the oracle's J, qM, qfrc_bias, point and quaternion, taken as osc_binding.reference takes them),
-the inputs of the tests, the refusal cases, the closed loops and a stand-in for BatchedMujoco's osc surface backed by the emulator.
+the inputs of the tests, the refusal cases and the closed loops.  emu_sim.EmuSim runs BatchedMujoco.osc on the emulated call.
 """
 import ctypes
 
@@ -235,25 +235,3 @@ def closed_loop_emu(q0, target6, rest, steps=ob.LOOP_STEPS):
         c = osc_task(ob.LOOP_MODEL, fr, e.qpos, e.qvel, tp, None, cin, rest, axes=POS, **NULL)["ctrl"]
         e.step(c, nsub=1, disable_contact=True)
     return e.qpos.copy()
-
-
-class EmuOscTaskSim(ob.EmuOscSim):
-    """EmuOscSim with the task keywords of BatchedMujoco.osc: with all of them at their defaults the call goes to emu_osc (jaco_osc), as
-    BatchedMujoco's does; `entries` records which entry each call reached."""
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.entries = []
-
-    def osc(self, frames, target_pos, target_quat=None, qpos=None, qvel=None, ctrl=None, axes=None, null_kv=0.0, rest_qpos=None, rest_kp=0.0,
-            rest_kv=0.0, rest_mask=0, **options):
-        import torch
-        if axes is None and null_kv == 0.0 and rest_qpos is None and rest_kp == 0.0 and rest_kv == 0.0 and rest_mask == 0:
-            self.entries.append("jaco_osc")
-            return super().osc(frames, target_pos, target_quat, qpos, qvel, ctrl, **options)
-        self.entries.append("jaco_osc_task")
-        n = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).numpy()
-        r = osc_task(self.model, list(frames), (self.qpos if qpos is None else qpos).numpy(), (self.qvel if qvel is None else qvel).numpy(),
-                     n(target_pos), n(target_quat), n(ctrl), n(rest_qpos), axes=axes, null_kv=null_kv, rest_kp=rest_kp, rest_kv=rest_kv,
-                     rest_mask=rest_mask, **options)
-        return {"ctrl": torch.from_numpy(r["ctrl"]), "singular": torch.from_numpy(r["status"] != 0)}

@@ -1,7 +1,7 @@
 """The robot-configuration query kernel (mujoco_jaco_amd/csrc/query.h) under the wavefront emulator (emu_query of
 tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
-Also the fp64 oracle's answers to the same questions, and a stand-in for BatchedMujoco's query surface backed by the emulator (CPU tests of
+Also the fp64 oracle's answers to the same questions.  emu_sim.EmuSim runs BatchedMujoco.query on the emulated call (CPU tests of
 robot_config.BatchedMujocoConfig).
 """
 import ctypes
@@ -74,29 +74,6 @@ def random_states(M, B, seed, qvel_scale=1.0):
             q[:, a + 3:a + 7] = u / np.linalg.norm(u, axis=1, keepdims=True)
     v = rng.normal(size=(B, nv)) * qvel_scale
     return q.astype(np.float32), v.astype(np.float32)
-
-
-class EmuQuerySim:
-    """What robot_config.BatchedMujocoConfig needs of a BatchedMujoco (frames, state, state_version, query), on the emulator, CPU tensors."""
-
-    def __init__(self, model, qpos, qvel):
-        import torch
-        from mujoco_jaco_amd.robot_config import FrameTable
-        self.model = model
-        self.frames = FrameTable.for_model(model)
-        self.qpos, self.qvel = torch.tensor(qpos, dtype=torch.float32), torch.tensor(qvel, dtype=torch.float32)
-        self.num_envs, self.nq, self.nv = self.qpos.shape[0], self.qpos.shape[1], self.qvel.shape[1]
-        self.state_version = 0
-        self.launches = 0
-
-    def get_state(self):
-        return self.qpos.clone(), self.qvel.clone(), None
-
-    def query(self, frames, qpos=None, qvel=None):
-        import torch
-        self.launches += 1
-        r = query(self.model, (self.qpos if qpos is None else qpos).numpy(), (self.qvel if qvel is None else qvel).numpy(), frames)
-        return {k: torch.from_numpy(v) for k, v in r.items()}
 
 
 # ---- closed loop through the query surface: ctrl[arm] = -g + PD (gravity compensation), fingers held by their position servos

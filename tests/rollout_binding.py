@@ -3,7 +3,7 @@ tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRU
 
 Also: the fp64 reference (the oracle with contacts disabled: per rollout qpos / qvel and a zero warm start, then step(ctrl_k, hold) per
 knot), the input sets with the conditions they must meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier, the
-refusals and a stand-in for BatchedMujoco.rollout backed by the emulator (CPU tests of robot_config).
+refusals.  emu_sim.EmuSim runs BatchedMujoco.rollout on the emulated call (CPU tests of robot_config).
 
 A tier hands the cases its `run`:
   run(model, ctrl [n, T, nu], qpos0=None, qvel0=None, state_index=None, nstates=None, frame=None, want=OUTS, hold=1, final_only=0,
@@ -324,7 +324,7 @@ def refusal_args(case):
     return k
 
 
-# ---- case 8: robot_config.rollout.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or EmuRolloutSim.
+# ---- case 8: robot_config.rollout.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 CONFIG_K, CONFIG_T = 3, 2
 
 
@@ -360,24 +360,3 @@ def case_config(make_sim, model):
         pred = g["v"][:, list(cfg.arm)].astype(np.float64) + h * a
         worst = max(worst, verr(N(r["dq"])[:, k, 0][ok], pred[ok]))
     return worst
-
-
-class EmuRolloutSim(fb.EmuFdSim):
-    """EmuFdSim plus BatchedMujoco.rollout on the emulator (CPU tensors), through the product's own method: only the one launch
-    (_rollout) is replaced."""
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.launches_rollout = 0
-
-    def _rollout(self, ctrl, qpos, qvel, state_index, nstates, frame, want, **options):
-        import torch
-        N = lambda t: None if t is None else t.numpy()
-        self.launches_rollout += 1
-        r = rollout(self.model, N(ctrl), N(qpos), N(qvel), N(state_index), nstates, frame, tuple(want), options["hold"], options["final_only"],
-                    handle=(self.qpos.numpy(), self.qvel.numpy()))
-        return {k: torch.from_numpy(x.view(np.int32) if k == "status" else x) for k, x in r.items()}
-
-    from mujoco_jaco_amd.physics import BatchedMujoco as _B
-    rollout, _index = _B.rollout, _B._index
-    del _B

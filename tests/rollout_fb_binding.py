@@ -3,8 +3,8 @@ tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRU
 
 Also: the fp64 reference (the oracle with contacts disabled, the law evaluated in fp64 on the oracle's own state at each evaluation),
 the input sets -- rollout_binding's states and ctrl rows plus seeded gains and a reference trajectory -- with the conditions they must
-meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier, the refusals and a stand-in for
-BatchedMujoco.rollout_feedback backed by the emulator (CPU tests of robot_config).
+meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier and the refusals.  emu_sim.EmuSim runs
+BatchedMujoco.rollout_feedback on the emulated call (CPU tests of robot_config).
 
 A tier hands the cases two calls:
   run(model, ctrl [P, T, nu], qpos0=None, qvel0=None, kff=None, gain=None, xref=None, dofs=(), alpha=None, plan_index=None,
@@ -20,7 +20,6 @@ import numpy as np
 import emu_binding
 import fd_binding as fb
 import ik_binding as ib
-import joint_binding as jb
 import osc_binding as ob
 import rollout_binding as rb
 from fd_binding import bits, verr
@@ -377,7 +376,7 @@ def refusal_args(case):
     return k
 
 
-# ---- case 10: the robot_config tier.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or EmuFbSim.
+# ---- case 10: the robot_config tier.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 HOLD_MODELS = {"jaco2_reaching_torque": "EE", "jaco2_dual_torque": "EE_1"}
 HOLD_B, HOLD_OFF, HOLD_HORIZON, HOLD_KNOTS, HOLD_SUBSTEPS = 4, 0.05, 12, 40, 5
 HOLD_Q, HOLD_QV, HOLD_R = 1e4, 10.0, 1e-3  # LQR weights: joint angles, joint velocities, torques
@@ -453,27 +452,3 @@ def case_hold_posture(make_sim, model):
     assert (bits(N(ra["q"])[:, 0, 0]) == bits(N(r["q"])[:, -1])).all() and (bits(N(ra["u"])[:, 0]) == bits(N(r["u"]))).all()
     assert not (bits(N(ra["u"])[:, 1]) == bits(N(ra["u"])[:, 2])).all()
     return worst
-
-
-class EmuFbSim(rb.EmuRolloutSim):
-    """EmuRolloutSim plus BatchedMujoco.joint and BatchedMujoco.rollout_feedback on the emulator (CPU tensors), the latter through the
-    product's own method: only the one launch (_rollout_fb) is replaced."""
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.calls, self.launches_rollout_fb = [], 0
-
-    joint = jb.EmuJointSim.joint
-
-    def _rollout_fb(self, plan, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
-        import torch
-        N = lambda t: None if t is None else t.numpy()
-        self.launches_rollout_fb += 1
-        r = rollout_fb(self.model, N(plan["ctrl"]), N(qpos), N(qvel), N(plan.get("kff")), N(plan.get("gain")), N(plan.get("xref")), options["dofs"],
-                       N(alpha), N(plan_index), N(state_index), nstates, frame, tuple(want), options["hold"], options["final_only"],
-                       options["per_substep"], handle=(self.qpos.numpy(), self.qvel.numpy()), n=n)
-        return {k: torch.from_numpy(x.view(np.int32) if k == "status" else x) for k, x in r.items()}
-
-    from mujoco_jaco_amd.physics import BatchedMujoco as _B
-    rollout_feedback = _B.rollout_feedback
-    del _B

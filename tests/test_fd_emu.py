@@ -23,6 +23,7 @@ inside or outside its ctrlrange, every servo force further from a forcerange end
 import pytest
 
 import fd_binding as fb
+from emu_sim import EmuSim
 
 QACC_BOUND, QFRC_BOUND, QACC_DAMPED_BOUND = 8.2e-3, 2.7e-3, 8.2e-3
 ACT_BOUNDS = (4.8e-3, 1.2e-3, 1.3e-4)
@@ -38,7 +39,7 @@ def run(model, q, v, c, **k):
 
 
 def make_sim(model, q, v):
-    return fb.EmuFdSim(model, q, v)
+    return EmuSim(model, q, v)
 
 
 @pytest.mark.parametrize("model", (fb.MODEL,) + fb.SMALL)
@@ -102,7 +103,7 @@ def test_robot_config_messages_and_one_launch():
     sim = make_sim(fb.MODEL, g["q"], g["v"])
     cfg = BatchedMujocoConfig(sim)
     A, Bm, c = cfg.linearize(joints=["joint3", "joint0", "joint_thumb"], ctrl=torch.tensor(g["c"]))
-    assert sim.launches_fd == 1 and A.shape == (fb.B, 6, 6) and Bm.shape == (fb.B, 6, 2) and c.shape == (fb.B, 6)   # (the thumb has a servo, no motor)
+    assert sim.launches["jaco_fd"] == 1 and A.shape == (fb.B, 6, 6) and Bm.shape == (fb.B, 6, 2) and c.shape == (fb.B, 6)   # (the thumb has a servo, no motor)
     a = cfg.forward_dynamics(torch.tensor(g["c"]))
     assert (fb.bits(a.numpy()) == fb.bits(run(fb.MODEL, g["q"], g["v"], g["c"], want=("qacc",))["qacc"][:, :6])).all()
     lin = sim.linearize(torch.tensor(g["c"]), dofs=[2])

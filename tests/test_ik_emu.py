@@ -10,6 +10,7 @@ import pytest
 
 import ik_binding as ib
 import query_binding as qb
+from emu_sim import EmuSim
 from mujoco_jaco_amd import _lib
 
 MODEL = "jaco2_curtain_torque"
@@ -210,7 +211,7 @@ def test_robot_config_ik_lands_tx_on_the_target(default_model):
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
     M, tab, seeds = default_model
     n = 32
-    sim = ib.EmuIkSim(MODEL, seeds[:n], np.zeros((n, 21), np.float32))
+    sim = EmuSim(MODEL, seeds[:n], np.zeros((n, 21), np.float32))
     cfg = BatchedMujocoConfig(sim)
     P, Qt, G = ib.targets(MODEL, "EE", POINT, seeds[:n], 0.3)
     before = sim.qpos.clone()

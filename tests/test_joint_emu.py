@@ -25,6 +25,7 @@ import ik_binding as ib
 import joint_binding as jb
 import osc_binding as ob
 import query_binding as qb
+from emu_sim import EmuSim
 
 ALL_BOUND = 2.9e-5    # 3 x 9.70e-6 (emulator)
 WRAP_BOUND = 1.4e-4   # 3 x 4.74e-5
@@ -148,7 +149,7 @@ def test_batched_joint_mirrors_abr_control_on_the_emulator():
     import torch
     from mujoco_jaco_amd.robot_config import BatchedJoint, BatchedMujocoConfig
     g = jb.regular_inputs()
-    sim = jb.EmuJointSim(jb.MODEL, g["q"], g["v"])
+    sim = EmuSim(jb.MODEL, g["q"], g["v"])
     cfg = BatchedMujocoConfig(sim)
     ctl = cfg.joint()
     assert isinstance(ctl, BatchedJoint) and ctl.joints == ["joint%d" % i for i in range(6)] and ctl.dof_mask == 0b111111
@@ -201,7 +202,7 @@ def test_batched_joint_drives_both_arms_by_default():
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
     model = "jaco2_dual_torque"
     q, v = ob.states(model, 3)
-    sim = jb.EmuJointSim(model, q, v)
+    sim = EmuSim(model, q, v)
     ctl = BatchedMujocoConfig(sim, ee="EE_1").joint()
     assert ctl.joints == ["joint%d_%d" % (i, a) for a in (1, 2) for i in range(6)] and bin(ctl.dof_mask).count("1") == 12
     t = jb.targets(model, q)

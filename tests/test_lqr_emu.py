@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import lqr_binding as lb
+from emu_sim import EmuSim
 
 BOUNDS = dict(gain=6.3e-6, kff=7.1e-6, Vxx0=1.1e-5, Vx0=6.0e-6, dV=2.6e-6)
 EXCESS, EXCESS_FLOOR, DV_IDENTITY = 4.9e-12, -1e-13, 2.8e-6
@@ -32,7 +33,7 @@ HOLD_BOUNDS = (1.5e-6, 7.8e-4)   # test_rollout_fb_emu.ORACLE_BOUNDS' qpos and q
 
 @pytest.fixture(scope="module")
 def sim():
-    return lb.EmuLqrSim()
+    return EmuSim()
 
 
 def within(m, bounds=BOUNDS):
@@ -78,11 +79,11 @@ def test_refusals(sim, case):
 def test_one_launch_and_no_launch_for_nothing(sim):
     import torch
     g = lb.inputs("2x1x1")
-    before = sim.launches_lqr
+    before = sim.launches["jaco_lqr"]
     lb.call(sim, g)
-    assert sim.launches_lqr == before + 1
+    assert sim.launches["jaco_lqr"] == before + 1
     r = sim.lqr_backward(*[torch.as_tensor(g[k]) for k in ("A", "B", "lxx", "luu")], problem_index=[])
-    assert sim.launches_lqr == before + 1 and r["gain"].shape == (0, 1, 1, 2) and r["status"].shape == (0,)
+    assert sim.launches["jaco_lqr"] == before + 1 and r["gain"].shape == (0, 1, 1, 2) and r["status"].shape == (0,)
     rc, why = sim.raw(*_good_records(g, 0))
     assert rc == 0, why   # n == 0 is accepted (and launches nothing)
 
@@ -101,19 +102,19 @@ def _good_records(g, n):
 
 
 def test_robot_config_lqr_and_ilqr_backward():
-    m = lb.case_config(lb.config_sim)
+    m = lb.case_config(EmuSim)
     print("MEASURE lqr emu robot_config.lqr against lqr_gains: %.3g" % m)
     assert m <= BOUNDS["gain"], m
 
 
 def test_tvlqr_holds_a_posture_like_lqr_gains():
-    eq, ev = lb.case_hold(lb.config_sim)
+    eq, ev = lb.case_hold(EmuSim)
     print("MEASURE lqr emu posture hold: closed loops under lqr / lqr_gains differ by qpos %.3g, qvel %.3g" % (eq, ev))
     assert eq <= HOLD_BOUNDS[0] and ev <= HOLD_BOUNDS[1], (eq, ev)
 
 
 def test_one_ilqr_iteration_lowers_the_true_cost():
-    J0, J, dV, status = lb.case_ilqr(lb.config_sim)
+    J0, J, dV, status = lb.case_ilqr(EmuSim)
     print("MEASURE lqr emu ilqr: nominal cost %s, best cost / nominal %s, dV1 %s" % (J0, J.min(1) / J0, dV[:, 0]))
     assert not status.any(), status
     assert (dV[:, 0] < 0).all(), dV

@@ -18,6 +18,7 @@ import pytest
 
 import ik_binding as ib
 import osc_binding as ob
+from emu_sim import EmuSim
 
 MODEL = "jaco2_curtain_torque"
 B = 67
@@ -249,7 +250,7 @@ def test_batched_osc_mirrors_abr_control_on_the_emulator(regular):
     import torch
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig, BatchedOSC, quat_from_euler_rxyz
     g = regular
-    sim = ob.EmuOscSim(MODEL, g["q"], g["v"])
+    sim = EmuSim(MODEL, g["q"], g["v"])
     ctl = BatchedMujocoConfig(sim).osc()
     assert isinstance(ctl, BatchedOSC) and ctl.names == ("EE",)
     qt = quat_from_euler_rxyz(torch.tensor(g["T6"][:, 3:], dtype=torch.float64)).numpy()
@@ -280,7 +281,7 @@ def test_batched_osc_drives_both_arms_in_one_launch():
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig
     model, names = "jaco2_dual_torque", ("EE_1", "EE_2")
     q, v = ob.states(model, 3)
-    sim = ob.EmuOscSim(model, q, v)
+    sim = EmuSim(model, q, v)
     calls = []
     inner = sim.osc
     sim.osc = lambda *a, **k: (calls.append(len(a[0])), inner(*a, **k))[1]

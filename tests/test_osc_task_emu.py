@@ -25,6 +25,7 @@ import pytest
 import ik_binding as ib
 import osc_binding as ob
 import osc_task_binding as tb
+from emu_sim import EmuSim
 from osc_task_binding import ALL, NULL, POS
 
 MODEL = "jaco2_curtain_torque"
@@ -53,6 +54,11 @@ def bits(a):
 
 def frame_of(model, name):
     return ib.table_of(model).jaco_frame(name)
+
+
+def reached(sim, before=None):
+    """{entry: launches} of the entries an EmuSim reached (since the copy `before` of its counters)."""
+    return {k: n - (before or {}).get(k, 0) for k, n in sim.launches.items() if n != (before or {}).get(k, 0)}
 
 
 def motors(model, dofs):
@@ -261,7 +267,7 @@ def test_batched_osc_with_ctrlr_dof_and_null_controllers_reproduces_the_raw_call
     import torch
     from mujoco_jaco_amd.robot_config import BatchedMujocoConfig, BatchedOSC, Damping, RestingConfig
     g = inputs
-    sim = tb.EmuOscTaskSim(MODEL, g["q"], g["v"])
+    sim = EmuSim(MODEL, g["q"], g["v"])
     a, b, c = 0.3, -1.1, 2.0
     ctl = BatchedOSC(BatchedMujocoConfig(sim), ctrlr_dof=[1, 1, 1, 0, 0, 0], null_controllers=[Damping(10), RestingConfig([None, None, None, a, b, c], 20, 5)])
     frame0 = [ib.table_of(MODEL).jaco_frame("EE", point=np.zeros(3))]
@@ -269,7 +275,7 @@ def test_batched_osc_with_ctrlr_dof_and_null_controllers_reproduces_the_raw_call
     rest[:, 3:6] = np.float32([a, b, c])
     raw = tb.osc_task(MODEL, frame0, g["q"], g["v"], g["tp"], None, None, rest, axes=POS, rest_mask=0b111000, **NULL)["ctrl"]
     u = ctl.generate_pose(torch.tensor(g["tp"][:, 0]))
-    assert sim.entries == ["jaco_osc_task"] and (bits(u.numpy()) == bits(raw)).all()
+    assert reached(sim) == {"jaco_osc_task": 1} and (bits(u.numpy()) == bits(raw)).all()
     u6 = ctl.generate(torch.tensor(g["T6"][:, 0], dtype=torch.float32))   # abr_control's six-wide target: the angles are not used
     assert (bits(u6.numpy()) == bits(raw)).all()
     # a [B, chain length] tensor of rest angles holds every joint of the chain, per env
@@ -286,11 +292,11 @@ def test_batched_osc_with_ctrlr_dof_and_null_controllers_reproduces_the_raw_call
     with pytest.raises(ValueError, match="at most one RestingConfig"):
         BatchedOSC(BatchedMujocoConfig(sim), null_controllers=[RestingConfig([0.0] * 6, 1, 1)] * 2)
     # without the new arguments the controller hands sim.osc no task keyword: the call is jaco_osc
-    sim.entries.clear()
+    before = dict(sim.launches)
     plain = BatchedOSC(BatchedMujocoConfig(sim))
     assert plain.task == {}
     plain.generate_pose(torch.tensor(g["tp"][:, 0]), torch.tensor(g["tq"][:, 0]))
-    assert sim.entries == ["jaco_osc"]
+    assert reached(sim, before) == {"jaco_osc": 1}
 
 
 def test_batched_mujoco_osc_reaches_jaco_osc_unless_a_task_keyword_is_given():

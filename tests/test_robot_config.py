@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import query_binding as qb
+from emu_sim import EmuSim
 from mujoco_jaco_amd.modelc import blob, kin, rot
 from mujoco_jaco_amd.robot_config import BatchedMujocoConfig, FrameTable
 
@@ -68,7 +69,7 @@ def test_mocap_and_unknown_names_are_refused():
         T.jaco_frame("hand")
     with pytest.raises(ValueError, match="unknown"):
         T.jaco_frame("no_such_body")
-    sim = qb.EmuQuerySim("jaco2_curtain_torque", *qb.random_states(T.M, 2, 1))
+    sim = EmuSim("jaco2_curtain_torque", *qb.random_states(T.M, 2, 1))
     with pytest.raises(ValueError):
         BatchedMujocoConfig(sim).J("subgoal_reach")
 
@@ -76,21 +77,21 @@ def test_mocap_and_unknown_names_are_refused():
 def test_config_shapes_arm_and_caching_on_the_default_model():
     M = _model("jaco2_curtain_torque")
     q, v = qb.random_states(M, 6, 3)
-    sim = qb.EmuQuerySim("jaco2_curtain_torque", q, v)
+    sim = EmuSim("jaco2_curtain_torque", q, v)
     cfg = BatchedMujocoConfig(sim)
     assert cfg.arm == list(range(6)) and cfg.arm_qadr == list(range(6))
     J, Mq, g = cfg.J("EE"), cfg.M(), cfg.g()
     assert J.shape == (6, 6, 6) and Mq.shape == (6, 6, 6) and g.shape == (6, 6)
     assert cfg.J("EE", full=True).shape == (6, 6, 21) and cfg.M(full=True).shape == (6, 21, 21) and cfg.g(full=True).shape == (6, 21)
-    n = sim.launches
+    n = sim.launches["jaco_query"]
     R, quat, x = cfg.R("object_body"), cfg.quaternion("object_body"), cfg.Tx("object_body")
     assert R.shape == (6, 3, 3) and quat.shape == (6, 4) and x.shape == (6, 3)
-    assert sim.launches == n + 1   # a new name: one launch for every registered frame; then the cached result
+    assert sim.launches["jaco_query"] == n + 1   # a new name: one launch for every registered frame; then the cached result
     cfg.J("EE"), cfg.R("object_body"), cfg.M()
-    assert sim.launches == n + 1
+    assert sim.launches["jaco_query"] == n + 1
     sim.state_version += 1
     cfg.g()
-    assert sim.launches == n + 2
+    assert sim.launches["jaco_query"] == n + 2
     # the numbers are the query's: g = -qfrc_bias[arm]; the oracle's for poses and the quaternion (up to sign)
     r = sim.query([sim.frames.jaco_frame("EE")])
     assert torch.equal(cfg.g(), -r["qfrc_bias"][:, :6]) and torch.equal(cfg.M(), r["qM"][:, :6, :6])
@@ -112,13 +113,13 @@ def test_config_joint_override_is_spliced_into_qpos():
     """q = [B, n_arm] replaces the arm angles of the current state (qvel kept): the same outputs as a state with those angles."""
     M = _model("jaco2_curtain_torque")
     q, v = qb.random_states(M, 4, 8)
-    sim = qb.EmuQuerySim("jaco2_curtain_torque", q, v)
+    sim = EmuSim("jaco2_curtain_torque", q, v)
     cfg = BatchedMujocoConfig(sim)
     qa = torch.tensor(np.random.default_rng(9).uniform(-1, 1, (4, 6)), dtype=torch.float32)
     J_over, g_over = cfg.J("EE", q=qa), cfg.g(q=qa)
     q2 = q.copy()
     q2[:, :6] = qa.numpy()
-    cfg2 = BatchedMujocoConfig(qb.EmuQuerySim("jaco2_curtain_torque", q2, v))
+    cfg2 = BatchedMujocoConfig(EmuSim("jaco2_curtain_torque", q2, v))
     assert torch.equal(J_over, cfg2.J("EE")) and torch.equal(g_over, cfg2.g())
     assert not torch.equal(J_over, cfg.J("EE"))
 
@@ -126,7 +127,7 @@ def test_config_joint_override_is_spliced_into_qpos():
 def test_config_arms_of_the_two_arm_model():
     M = _model("jaco2_dual_torque")
     q, v = qb.random_states(M, 3, 4)
-    sim = qb.EmuQuerySim("jaco2_dual_torque", q, v)
+    sim = EmuSim("jaco2_dual_torque", q, v)
     c1, c2 = BatchedMujocoConfig(sim, ee="EE_1"), BatchedMujocoConfig(sim, ee="EE_2")
     assert len(c1.arm) == 6 and len(c2.arm) == 6 and not set(c1.arm) & set(c2.arm) and max(c1.arm + c2.arm) < 18
     J1, J2 = c1.J("EE_1", full=True), c1.J("EE_2", full=True)

@@ -21,6 +21,7 @@ import pytest
 
 import query_binding as qb
 import rollout_binding as rb
+from emu_sim import EmuSim
 
 ORACLE_BOUNDS = (7.7e-7, 3.2e-4)
 LONG_BOUNDS = (1.3e-7, 2.7e-5)
@@ -38,7 +39,7 @@ def query(model, qpos, qvel, frame):
 
 
 def make_sim(model, q, v):
-    return rb.EmuRolloutSim(model, q, v)
+    return EmuSim(model, q, v)
 
 
 def within(m, bounds):
@@ -114,4 +115,4 @@ def test_python_tier_messages():
     with pytest.raises(ValueError, match="jaco_rollout: nknots 2 x hold 0"):
         sim.rollout(torch.zeros(3, 2, 9), hold=0)
     r = sim.rollout(torch.as_tensor(g["c"][:3]), hold=2, final_only=True)
-    assert sim.launches_rollout == 2 and set(r) == {"qpos", "qvel", "status"} and r["qpos"].shape == (3, 1, 23)
+    assert sim.launches["jaco_rollout"] == 2 and set(r) == {"qpos", "qvel", "status"} and r["qpos"].shape == (3, 1, 23)

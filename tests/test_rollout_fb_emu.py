@@ -19,6 +19,7 @@ import pytest
 
 import rollout_binding as rb
 import rollout_fb_binding as fbb
+from emu_sim import EmuSim
 
 ORACLE_BOUNDS = (1.5e-6, 7.8e-4, 5.6e-4)
 LONG_BOUNDS = (2.4e-7, 9.9e-5, 3.8e-5)
@@ -34,7 +35,7 @@ def run_open(model, ctrl, qpos0=None, qvel0=None, **k):
 
 
 def make_sim(model, q, v):
-    return fbb.EmuFbSim(model, q, v)
+    return EmuSim(model, q, v)
 
 
 def within(m, bounds):
@@ -143,7 +144,7 @@ def test_python_tier_messages():
     with pytest.raises(ValueError, match="jaco_rollout_fb: dof 9 belongs to a free joint"):
         sim.rollout_feedback(torch.zeros(3, 2, 9), gain=torch.zeros(3, 2, 9, 4), x_ref=torch.zeros(3, 2, 4), dofs=[0, 9])
     r = sim.rollout_feedback(torch.as_tensor(g["c"][:3]), hold=2, per_substep=True, final_only=True)
-    assert sim.launches_rollout_fb == 2 and set(r) == {"qpos", "qvel", "status", "ctrl"} and r["qpos"].shape == (3, 1, 23) and r["ctrl"].shape == (3, 12, 9)
+    assert sim.launches["jaco_rollout_fb"] == 2 and set(r) == {"qpos", "qvel", "status", "ctrl"} and r["qpos"].shape == (3, 1, 23) and r["ctrl"].shape == (3, 12, 9)
     cfg = BatchedMujocoConfig(sim)
     with pytest.raises(ValueError, match=r"u has shape \(%d, 2, 9\), not \[%d, T, 6\]" % (n, n)):
         cfg.rollout_feedback(torch.zeros(n, 2, 9))
