@@ -483,6 +483,57 @@ typedef struct JacoRolloutFbOut { float* qpos; float* qvel; float* xpos; float* 
 int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
                     const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutFbOut* out, void* stream);
 
+/* ---- costed rollouts: jaco_rollout_fb with a per-rollout additive perturbation of the commanded ctrl and a running quadratic cost
+ * accumulated inside the kernel -- what a sampling planner (MPPI, CEM, random shooting) and iLQR's line search want of a rollout: one
+ * number, not the trajectory -- for n rollouts in ONE kernel launch (mujoco_jaco_amd/csrc/rollout_cost.h).  The state arguments, the
+ * plans (JacoRolloutPlan), the law, the substep, the six outputs of JacoRolloutFbOut, final_only and n == 0 are those of
+ * jaco_rollout_fb, word for word, with per_substep = 0: the law is evaluated once per knot.
+ * THE COMMANDED CTRL, at knot k of rollout i on plan p: u_a is the law's value in its stated fp32 order; then, if noise is given,
+ *   u_a = u_a + noise[i][k][a]                                                      (ONE fp32 add; this order is part of the interface)
+ * The sum is what the actuators get and what the ctrl output ([n][nknots][nu], before the actuator clamp) holds.
+ * THE COST.  With x the fp32 state on the option's dofs (the law's x_j, nx = 2 ndofs), pos the frame's position, T = nknots and
+ * g = goal_per_knot ? k : 0:
+ *   J_i = sum_{k=0}^{T-1} [ 1/2 sum_a wu[a] u_{k,a}^2 + 1/2 sum_j WX_k[j] (x_{k+1,j} - xgoal[p][g][j])^2 + 1/2 WP_k |pos_{k+1} - pgoal[p][g]|^2 ]
+ * where x_{k+1} and pos_{k+1} are the state and the pose after knot k -- the very words row k of the qpos / qvel / xpos outputs holds --
+ * and (WX_k, WP_k) = (wx, wp) for k < T - 1, (wxT, wpT) for the last knot.  Differences are NOT wrapped, as in the law.  The fp32 order
+ * of the sum is not part of the interface; that two runs of the same call agree bit for bit is, and that cost and terms do not depend
+ * on final_only or on which other outputs are asked for.
+ * Goals and noise (JacoRolloutGoal, a host record of device pointers, each optional; a NULL record is three NULLs): goals are indexed by
+ * the plan index p: xgoal [nplans][G][nx], pgoal [nplans][G][3], G = goal_per_knot ? nknots : 1; noise [n][nknots][nu].
+ * The weights travel by value in the options; all must be finite and >= 0, so that every term is non-negative.  The dofs are used when
+ * gain is given or a state weight (wx, wxT) is non-zero.  The pose of a knot is composed whenever a pose weight asks for it, whether or
+ * not xpos / xmat are asked for.
+ * Outputs: the six of JacoRolloutFbOut, plus cost [n] and terms [n][3] = the ctrl, state and pose parts of J (their sum is cost to
+ * rounding); at least one of the eight is required; the usual call passes cost and status.  A rollout whose status has JACO_FLAG_NAN gets
+ * cost = terms = +inf, so that a softmin ignores it.  A state_idx or plan_idx entry out of range: that rollout writes only its status
+ * word, with JACO_ROLLOUT_BAD_INDEX set.
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch (none for n == 0, which returns JACO_OK), no
+ * allocation, no synchronisation, no host copy; the options (dofs and weights included) and the frame travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for everything jaco_rollout_fb refuses (there is no per_substep; the outputs being the eight) and
+ * for goal_per_knot not 0 / 1; a model with nu > JACO_ROLLOUT_COST_MAX_NU; a weight that is negative or not finite; a non-zero state
+ * weight without xgoal or (gain not given) without dofs -- the dofs then checked as jaco_rollout_fb checks them; a non-zero pose weight
+ * without pgoal or without a frame. */
+#define JACO_ROLLOUT_COST_MAX_NU 18
+typedef struct JacoRolloutCostOptions {
+  int32_t nknots, hold, final_only, goal_per_knot;  /* as JacoRolloutOptions; goal_per_knot 0 / 1 */
+  int32_t ndofs;                                    /* 1 .. JACO_ROLLOUT_FB_MAX_DOFS; used with gain or a non-zero state weight */
+  int32_t dofs[JACO_ROLLOUT_FB_MAX_DOFS];           /* distinct hinge dofs */
+  float wx[2 * JACO_ROLLOUT_FB_MAX_DOFS];           /* running state weights, word j of x */
+  float wxT[2 * JACO_ROLLOUT_FB_MAX_DOFS];          /* the last knot's */
+  float wu[JACO_ROLLOUT_COST_MAX_NU];               /* ctrl weights, actuator a */
+  float wp, wpT;                                    /* running and last-knot pose weight */
+  int32_t reserved;
+} JacoRolloutCostOptions;
+typedef struct JacoRolloutGoal {                    /* device pointers, each or NULL */
+  const float* noise;  /* [n][nknots][nu] */
+  const float* xgoal;  /* [nplans][G][nx] */
+  const float* pgoal;  /* [nplans][G][3] */
+} JacoRolloutGoal;
+typedef struct JacoRolloutCostOut { float* qpos; float* qvel; float* xpos; float* xmat; uint32_t* status; float* ctrl; float* cost; float* terms; } JacoRolloutCostOut;
+int jaco_rollout_cost(JacoHandle* h, const JacoRolloutCostOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                      const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutGoal* goal_host,
+                      const JacoRolloutCostOut* out, void* stream);
+
 /* ---- the iLQR / TVLQR backward pass, batched: the feed-forward k_t and the gains K_t that jaco_rollout_fb consumes, from the linearisation
  * (jaco_fd) and the cost expansion along a trajectory, the whole T-knot recursion of every problem in ONE launch.
  * Solve i works on problem p = prob_idx[i] and runs t = T-1 .. 0.  Deviations follow dx_{t+1} = A_t dx_t + B_t du_t; the knot cost is

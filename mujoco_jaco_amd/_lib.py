@@ -155,6 +155,47 @@ class JacoRolloutFbOut(ctypes.Structure):
                 ("ctrl", ctypes.c_void_p)]
 
 
+JACO_ROLLOUT_COST_MAX_NU = 18
+JACO_FLAG_NAN, JACO_FLAG_SOLVER_MAXITER = 8, 16   # the status bits of a rollout (include/jaco_env.h): a NAN rollout costs +inf
+
+
+class JacoRolloutCostOptions(ctypes.Structure):
+    """JacoRolloutCostOptions of include/jaco_env.h; a fresh instance holds hold = 1, final_only = 0, goal_per_knot = 0, no dofs and zero
+    weights.  dofs: at most JACO_ROLLOUT_FB_MAX_DOFS hinge dofs; wx / wxT: at most 2 x that many state weights (running / last knot), wu:
+    at most JACO_ROLLOUT_COST_MAX_NU ctrl weights, each zero-filled to its array's length; wp / wpT: the pose weights."""
+    _fields_ = [("nknots", ctypes.c_int32), ("hold", ctypes.c_int32), ("final_only", ctypes.c_int32), ("goal_per_knot", ctypes.c_int32),
+                ("ndofs", ctypes.c_int32), ("dofs", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS),
+                ("wx", ctypes.c_float * (2 * JACO_ROLLOUT_FB_MAX_DOFS)), ("wxT", ctypes.c_float * (2 * JACO_ROLLOUT_FB_MAX_DOFS)),
+                ("wu", ctypes.c_float * JACO_ROLLOUT_COST_MAX_NU), ("wp", ctypes.c_float), ("wpT", ctypes.c_float), ("reserved", ctypes.c_int32)]
+    DEFAULTS = dict(nknots=0, hold=1, final_only=0, goal_per_knot=0, dofs=(), wx=(), wxT=(), wu=(), wp=0.0, wpT=0.0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown costed rollout option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        o = {**self.DEFAULTS, **options}
+        dofs = [int(d) for d in o.pop("dofs")]
+        if len(dofs) > JACO_ROLLOUT_FB_MAX_DOFS:
+            raise ValueError("%d dofs: a costed rollout takes at most %d" % (len(dofs), JACO_ROLLOUT_FB_MAX_DOFS))
+        arrays = {k: [float(w) for w in o.pop(k)] for k in ("wx", "wxT", "wu")}
+        for k, w in arrays.items():
+            if len(w) > len(getattr(self, k)):
+                raise ValueError("%d weights in %s: a costed rollout takes at most %d" % (len(w), k, len(getattr(self, k))))
+        super().__init__(ndofs=len(dofs), **o)
+        self.dofs[:len(dofs)] = dofs
+        for k, w in arrays.items():
+            getattr(self, k)[:len(w)] = w
+
+
+class JacoRolloutGoal(ctypes.Structure):
+    _fields_ = [("noise", ctypes.c_void_p), ("xgoal", ctypes.c_void_p), ("pgoal", ctypes.c_void_p)]
+
+
+class JacoRolloutCostOut(ctypes.Structure):
+    _fields_ = [("qpos", ctypes.c_void_p), ("qvel", ctypes.c_void_p), ("xpos", ctypes.c_void_p), ("xmat", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("ctrl", ctypes.c_void_p), ("cost", ctypes.c_void_p), ("terms", ctypes.c_void_p)]
+
+
 JACO_LQR_MAX_NX, JACO_LQR_MAX_NU = 36, 18
 JACO_LQR_BAD_INDEX = 0x80000   # jaco_lqr: the solve's problem index was outside [0, nprob); only its status word was written
 JACO_LQR_NOT_PD = 0x100000     # jaco_lqr: Quu + mu I not positive definite, or a non-finite number, at knot (status & 0xffff)
@@ -276,6 +317,7 @@ SYMBOLS = {
     "jaco_rollout": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout_fb": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_lqr": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
+    "jaco_rollout_cost": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h and lqr.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h and rollout_cost.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -75,3 +75,18 @@ static_assert(sizeof(JacoLqrOut) == sizeof(JacoLqrOutp) && offsetof(JacoLqrOut, 
                   offsetof(JacoLqrOut, Vxx0) == offsetof(JacoLqrOutp, Vxx0) && offsetof(JacoLqrOut, Vx0) == offsetof(JacoLqrOutp, Vx0) &&
                   offsetof(JacoLqrOut, status) == offsetof(JacoLqrOutp, status),
               "JacoLqrOut of the public header and the kernel's output record must agree");
+static_assert(sizeof(JacoRolloutCostOptions) == sizeof(JacoRolloutCostOpts) && offsetof(JacoRolloutCostOptions, nknots) == offsetof(JacoRolloutCostOpts, nknots) &&
+                  offsetof(JacoRolloutCostOptions, hold) == offsetof(JacoRolloutCostOpts, hold) && offsetof(JacoRolloutCostOptions, final_only) == offsetof(JacoRolloutCostOpts, final_only) &&
+                  offsetof(JacoRolloutCostOptions, goal_per_knot) == offsetof(JacoRolloutCostOpts, goal_per_knot) && offsetof(JacoRolloutCostOptions, ndofs) == offsetof(JacoRolloutCostOpts, ndofs) &&
+                  offsetof(JacoRolloutCostOptions, dofs) == offsetof(JacoRolloutCostOpts, dofs) && offsetof(JacoRolloutCostOptions, wx) == offsetof(JacoRolloutCostOpts, wx) &&
+                  offsetof(JacoRolloutCostOptions, wxT) == offsetof(JacoRolloutCostOpts, wxT) && offsetof(JacoRolloutCostOptions, wu) == offsetof(JacoRolloutCostOpts, wu) &&
+                  offsetof(JacoRolloutCostOptions, wp) == offsetof(JacoRolloutCostOpts, wp) && offsetof(JacoRolloutCostOptions, wpT) == offsetof(JacoRolloutCostOpts, wpT) &&
+                  JACO_ROLLOUT_COST_MAX_NU == JROLLOUT_COST_MAX_NU && 2 * JACO_ROLLOUT_FB_MAX_DOFS == JRC_NX,
+              "JacoRolloutCostOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoRolloutGoal) == sizeof(JacoRolloutCostGoal) && offsetof(JacoRolloutGoal, noise) == offsetof(JacoRolloutCostGoal, noise) &&
+                  offsetof(JacoRolloutGoal, xgoal) == offsetof(JacoRolloutCostGoal, xgoal) && offsetof(JacoRolloutGoal, pgoal) == offsetof(JacoRolloutCostGoal, pgoal),
+              "JacoRolloutGoal of the public header and the kernel's goal record must agree");
+static_assert(offsetof(JacoRolloutCostOut, qpos) == offsetof(JacoRolloutFbOut, qpos) && offsetof(JacoRolloutCostOut, status) == offsetof(JacoRolloutFbOut, status) &&
+                  offsetof(JacoRolloutCostOut, ctrl) == offsetof(JacoRolloutFbOut, ctrl) && offsetof(JacoRolloutCostOut, cost) == sizeof(JacoRolloutFbOut) &&
+                  offsetof(JacoRolloutCostOut, terms) == sizeof(JacoRolloutFbOut) + sizeof(float*) && offsetof(JacoRolloutCostArgs, F) == 0,
+              "JacoRolloutCostOut extends JacoRolloutFbOut; the costed kernel's block starts with the closed-loop kernel's");

@@ -1,5 +1,5 @@
-// From the C ABI's arguments to the kernel's argument block, for the nine query-style entries (jaco_query, jaco_ik, jaco_osc,
-// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr).  Host only: included by the library's host unit (jaco_env.hip)
+// From the C ABI's arguments to the kernel's argument block, for the ten query-style entries (jaco_query, jaco_ik, jaco_osc,
+// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost).  Host only: included by the library's host unit (jaco_env.hip)
 // and by the CPU tests' host build (tests/emu/emu_driver.cpp), after include/jaco_env.h, physics_kernel.h and abi_agreement.h -- the
 // public records are copied into the kernel-side records that restate them, which the feature headers (query.h ... rollout_fb.h)
 // cannot do: they do not see the public header.  kernels.hip does not include this file.
@@ -123,7 +123,7 @@ static inline std::string jaco_fd_bind(const JacoModelDev& m, const JacoFdOption
   return why;
 }
 
-// (the two rollouts: an accepted call with n = 0 launches nothing, which is the entry's to see to)
+// (the three rollouts: an accepted call with n = 0 launches nothing, which is the entry's to see to)
 static inline std::string jaco_rollout_bind(const JacoModelDev& m, const JacoRolloutOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx, int nstates,
                                             const float* qpos0, const float* qvel0, const float* ctrl, const JacoRolloutOut* out, int num_envs,
                                             const float* state_qpos, const float* state_qvel, JacoRolloutArgs* Q) {
@@ -147,6 +147,25 @@ static inline std::string jaco_rollout_fb_bind(const JacoModelDev& m, const Jaco
                                                   num_envs, reinterpret_cast<const JacoRolloutFbPlan*>(plan), out != nullptr, Q);
   if (!why.empty()) return "jaco_rollout_fb: " + why;
   if (!Q->R.qpos0) { Q->R.qpos0 = state_qpos; Q->R.qvel0 = state_qvel; }
+  return why;
+}
+
+static inline std::string jaco_rollout_cost_bind(const JacoModelDev& m, const JacoRolloutCostOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx,
+                                                 int nstates, const float* qpos0, const float* qvel0, const JacoRolloutPlan* plan, const JacoRolloutGoal* goal,
+                                                 const JacoRolloutCostOut* out, int num_envs, const float* state_qpos, const float* state_qvel,
+                                                 JacoRolloutCostArgs* Q) {
+  *Q = JacoRolloutCostArgs{};
+  JacoRolloutArgs& R = Q->F.R;
+  R.state_idx = state_idx; R.qpos0 = qpos0; R.qvel0 = qvel0;
+  if (out) {
+    R.qpos = out->qpos; R.qvel = out->qvel; R.xpos = out->xpos; R.xmat = out->xmat; R.status = out->status; Q->F.ctrl_out = out->ctrl;
+    Q->cost = out->cost; Q->terms = out->terms;
+  }
+  const std::string why = jaco_rollout_cost_resolve(m, reinterpret_cast<const JacoRolloutCostOpts*>(opt), reinterpret_cast<const JacoQueryFrame*>(frame), n, nstates,
+                                                    num_envs, reinterpret_cast<const JacoRolloutFbPlan*>(plan), reinterpret_cast<const JacoRolloutCostGoal*>(goal),
+                                                    out != nullptr, Q);
+  if (!why.empty()) return "jaco_rollout_cost: " + why;
+  if (!R.qpos0) { R.qpos0 = state_qpos; R.qvel0 = state_qvel; }
   return why;
 }
 #endif   // JACO_ENTRY_ARGS_LQR_ONLY

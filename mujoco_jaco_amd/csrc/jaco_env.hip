@@ -1042,6 +1042,19 @@ extern "C" int jaco_rollout_fb(JacoHandle* h, const JacoRolloutFbOptions* opt_ho
   return launch_entry(h, jaco_launch_rollout_fb, n, stream, Q);
 }
 
+// costed rollouts (rollout_cost.h): jaco_rollout_fb with the noise added and the running cost accumulated inside the kernel
+extern "C" int jaco_rollout_cost(JacoHandle* h, const JacoRolloutCostOptions* opt_host, const JacoFrame* frame_host, int n, const int32_t* state_idx_dev, int nstates,
+                                 const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutGoal* goal_host,
+                                 const JacoRolloutCostOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoRolloutCostArgs Q;
+  if (refused(h, jaco_rollout_cost_bind(h->model_host, opt_host, frame_host, n, state_idx_dev, nstates, qpos0_dev, qvel0_dev, plan_host, goal_host, out, h->num_envs,
+                                        h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
+  if (n == 0) return JACO_OK;
+  Q.F.R.model = h->model_dev;
+  return launch_entry(h, jaco_launch_rollout_cost, n, stream, Q);
+}
+
 // the iLQR / TVLQR backward pass (lqr.h): the whole recursion of every problem in one launch; the model is not read
 extern "C" int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream) {
   if (!h) return JACO_EINVAL;

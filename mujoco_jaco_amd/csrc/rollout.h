@@ -125,35 +125,55 @@ JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags
 
 // The frame's pose at the body poses in s.xpos / s.xmat (run_query's: frame_pose) into row `row` of the pose outputs: every lane
 // composes it (the world-fixed case is wave-uniform), lane k stores word k.
+// store = false: the pose is composed and nothing is stored (the costed kernel, for a knot whose row is not asked for).  Returns the position.
 template <class L>
-JDEV void rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lane) {
+JDEV v3 rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lane, bool store = true) {
   v3 p;
   m3 R;
   frame_pose(s, Q.fr, &p, &R);
   float w = lane == 0 ? p.x : (lane == 1 ? p.y : p.z), r = 0.f;
 #pragma unroll
   for (int k = 0; k < 9; k++) if (lane == k) r = R.m[k];
-  if (Q.xpos && lane < 3) Q.xpos[row * 3 + lane] = w;
-  if (Q.xmat && lane < 9) Q.xmat[row * 9 + lane] = r;
+  if (store && Q.xpos && lane < 3) Q.xpos[row * 3 + lane] = w;
+  if (store && Q.xmat && lane < 9) Q.xmat[row * 9 + lane] = r;
+  return p;
 }
 
-// The closed-loop kernel's block and law (rollout_fb.h), which the one loop below serves too.
+// The closed-loop kernel's block and law (rollout_fb.h) and the costed kernel's block and terms (rollout_cost.h), which the one loop
+// below serves too.  rollout_kind<A>: what block A adds to the open loop -- closed: the ctrl of a knot comes from rollout_fb_law and the
+// rollout follows a plan; costed: closed, plus the noise and the running cost.
 struct JacoRolloutFbArgs;
+struct JacoRolloutCostArgs;
 template <class L>
 JDEV void rollout_fb_law(const JacoRolloutFbArgs* Q, const JacoModelDev* m, L& s, int i, int p, int k, size_t erow, int lane);
-template <class A> inline constexpr bool rollout_closed = std::is_same<A, JacoRolloutFbArgs>::value;
-// the JacoRolloutArgs of either block: the block itself, or the closed-loop block's R
+template <class L>
+JDEV void rollout_cost_ctrl(const JacoRolloutCostArgs* Q, const JacoModelDev* m, L& s, int i, int k, int lane, float& acc);
+template <class L>
+JDEV void rollout_cost_state(const JacoRolloutCostArgs* Q, const JacoModelDev* m, const L& s, int p, int k, int lane, float& acc);
+JDEV void rollout_cost_pose(const JacoRolloutCostArgs* Q, int p, int k, int lane, const v3 pos, float& acc);
+JDEV void rollout_cost_finish(const JacoRolloutCostArgs* Q, int i, int lane, float acc, unsigned flags);
+template <class A> struct rollout_kind {
+  static constexpr bool costed = std::is_same<A, JacoRolloutCostArgs>::value;
+  static constexpr bool closed = costed || std::is_same<A, JacoRolloutFbArgs>::value;
+};
+// the JacoRolloutFbArgs of a closed block: the block itself, or the costed block's F
+template <class A>
+JDEV const JacoRolloutFbArgs* rollout_law_block(const A* Q) {
+  if constexpr (rollout_kind<A>::costed) return &Q->F; else return Q;
+}
+// the JacoRolloutArgs of any block: the block itself, or the closed-loop block's R
 template <class A>
 JDEV const JacoRolloutArgs* rollout_block(const A* Q) {
-  if constexpr (rollout_closed<A>) return &Q->R; else return Q;
+  if constexpr (rollout_kind<A>::closed) return &rollout_law_block(Q)->R; else return Q;
 }
 
-// The knot x hold loop of rollout i, for jaco_rollout (A = JacoRolloutArgs) and jaco_rollout_fb (A = JacoRolloutFbArgs).  The two differ
-// in where a knot's ctrl comes from -- its row of the ctrl sequences, loaded once per knot, or rollout_fb_law evaluated on the state in
-// LDS, per knot or per substep -- and in the closed-loop kernel's plan index.
+// The knot x hold loop of rollout i, for jaco_rollout (A = JacoRolloutArgs), jaco_rollout_fb (A = JacoRolloutFbArgs) and
+// jaco_rollout_cost (A = JacoRolloutCostArgs).  They differ in where a knot's ctrl comes from -- its row of the ctrl sequences, loaded once
+// per knot, or rollout_fb_law evaluated on the state in LDS, per knot or per substep -- in the closed-loop kernels' plan index, and in
+// the costed kernel's terms (rollout_cost.h says where they are formed and why there).
 template <class A, class L>
 JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
-  constexpr bool closed = rollout_closed<A>;
+  constexpr bool closed = rollout_kind<A>::closed, costed = rollout_kind<A>::costed;
   const A* Qp = kernarg_view(Q_);
   const JacoRolloutArgs* R = rollout_block(Qp);
   const JacoModelDev* m = opaque_ptr(R->model);
@@ -162,8 +182,9 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
   int p = 0;
   bool bad = src < 0 || src >= R->nstates;
   if constexpr (closed) {
-    p = wave_uniform_i(Qp->plan.plan_idx ? Qp->plan.plan_idx[i] : i);
-    bad = bad || p < 0 || p >= Qp->plan.nplans;
+    const auto* F = rollout_law_block(Qp);   // (JacoRolloutFbArgs, complete by the time this is instantiated)
+    p = wave_uniform_i(F->plan.plan_idx ? F->plan.plan_idx[i] : i);
+    bad = bad || p < 0 || p >= F->plan.nplans;
   }
   if (bad) {   // (as jaco_load_envs: neither a fault nor silence)
     if (lane == 0 && R->status) R->status[i] = JROLLOUT_BAD_INDEX;
@@ -175,7 +196,8 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
   const int nknots = R->nknots, hold = R->hold;
   const bool every = R->final_only == 0, pose = R->xpos != nullptr || R->xmat != nullptr;
   bool each = false;
-  if constexpr (closed) each = Qp->per_substep != 0;
+  if constexpr (closed && !costed) each = Qp->per_substep != 0;
+  float acc = 0.f;   // (the costed kernel's one accumulator per lane)
 #pragma nounroll
   for (int k = 0; k < nknots; k++) {
     if constexpr (!closed) {
@@ -192,10 +214,18 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
       m = opaque_ptr(R->model);
       lane = wave_opaque_i(lane);
       if constexpr (closed) {
-        if (each || sub == 0) rollout_fb_law(Qp, m, s, i, p, k, each ? ((size_t)i * nknots + k) * hold + sub : (size_t)i * nknots + k, lane);
+        if (each || sub == 0) {
+          rollout_fb_law(rollout_law_block(Qp), m, s, i, p, k, each ? ((size_t)i * nknots + k) * hold + sub : (size_t)i * nknots + k, lane);
+          if constexpr (costed) rollout_cost_ctrl(Qp, m, s, i, k, lane, acc);
+        }
       }
       entry_walk(m, s, lane);
-      if (pose && every && sub == 0 && k > 0) rollout_pose(*R, s, (size_t)i * nknots + (k - 1), lane);   // the previous knot's pose: this walk's
+      bool knot_pose = pose && every;
+      if constexpr (costed) knot_pose = knot_pose || Qp->wp != 0.f;
+      if (knot_pose && sub == 0 && k > 0) {   // the previous knot's pose: this walk's
+        const v3 pos = rollout_pose(*R, s, (size_t)i * nknots + (k - 1), lane, pose && every);
+        if constexpr (costed) rollout_cost_pose(Qp, p, k - 1, lane, pos, acc);
+      }
       rollout_substep(m, s, lane, flags);
     }
     if (every || k == nknots - 1) {
@@ -203,16 +233,22 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
       if (R->qpos && lane < nq) R->qpos[row * nq + lane] = s.qpos[lane];
       if (R->qvel && lane < nv) R->qvel[row * nv + lane] = s.qvel[lane];
     }
+    if constexpr (costed) rollout_cost_state(Qp, m, s, p, k, lane, acc);
   }
-  R = rollout_block(kernarg_view(Q_));
-  if (pose) {   // the last knot's pose needs a walk of its own
+  Qp = kernarg_view(Q_);
+  R = rollout_block(Qp);
+  bool last_pose = pose;
+  if constexpr (costed) last_pose = last_pose || Qp->wp != 0.f || Qp->wpT != 0.f;
+  if (last_pose) {   // the last knot's pose needs a walk of its own
     stage_walk(opaque_ptr(R->model), s, lane, false);
     wave_sync();
-    rollout_pose(*R, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
+    const v3 pos = rollout_pose(*R, s, every ? (size_t)i * nknots + (nknots - 1) : (size_t)i, lane);
+    if constexpr (costed) rollout_cost_pose(Qp, p, nknots - 1, lane, pos, acc);
   }
-  if (R->status) {   // the lanes' sticky flags, or-reduced over the wavefront
+  if (R->status || costed) {   // the lanes' sticky flags, or-reduced over the wavefront
     const unsigned f = wave_or(flags);
-    if (lane == 0) R->status[i] = f;
+    if (lane == 0 && R->status) R->status[i] = f;
+    if constexpr (costed) rollout_cost_finish(Qp, i, lane, acc, f);
   }
 }
 

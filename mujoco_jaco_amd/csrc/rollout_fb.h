@@ -48,19 +48,32 @@ struct JacoRolloutFbArgs {
   int dofs[JROLLOUT_FB_MAX_DOFS];
 };
 
-// The host half shared by jaco_rollout_fb (jaco_env.hip) and the emulator's entry: jaco_rollout_resolve's checks, then the plan's and
-// the law's.  The caller has filled in Q->R's state and output pointers and Q->ctrl_out as they were handed over.  Returns an empty
+// The dof list of the law -- and of jaco_rollout_cost's state term -- checked and put into the block.
+static inline std::string jaco_rollout_fb_dofs(const JacoModelDev& m, int ndofs, const int* dofs, JacoRolloutFbArgs* Q) {
+  if (ndofs < 1 || ndofs > JROLLOUT_FB_MAX_DOFS) return "ndofs " + std::to_string(ndofs) + " outside [1, " + std::to_string(JROLLOUT_FB_MAX_DOFS) + "]";
+  for (int j = 0; j < ndofs; j++) {
+    const int d = dofs[j];
+    if (d < 0 || d >= m.nv) return "dof " + std::to_string(d) + " outside [0, " + std::to_string(m.nv) + ")";
+    if (m.d_qadr[d] < 0) return "dof " + std::to_string(d) + " belongs to a free joint";
+    for (int k = 0; k < j; k++) if (dofs[k] == d) return "dof " + std::to_string(d) + " is listed twice";
+    Q->dofs[j] = d;
+  }
+  Q->ndofs = ndofs;
+  return std::string();
+}
+
+// The host half shared by jaco_rollout_fb (jaco_env.hip), the emulator's entry and, with its own rule for which outputs count
+// (any_output, and the message when none is there), jaco_rollout_cost_resolve: jaco_rollout_resolve's checks, then the plan's and the
+// law's.  The caller has filled in Q->R's state and output pointers and Q->ctrl_out as they were handed over.  Returns an empty
 // string, or what is wrong.
-static inline std::string jaco_rollout_fb_resolve(const JacoModelDev& m, const JacoRolloutFbOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
-                                                  const JacoRolloutFbPlan* plan, bool have_out, JacoRolloutFbArgs* Q) {
+static inline std::string jaco_rollout_fb_resolve_outputs(const JacoModelDev& m, const JacoRolloutFbOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
+                                                          const JacoRolloutFbPlan* plan, bool have_out, bool any_output, const char* no_output, JacoRolloutFbArgs* Q) {
   if (!plan) return "the plan is required";
   Q->R.ctrl = plan->ctrl;
   {
     JacoRolloutOpts ro{};
     if (o) { ro.nknots = o->nknots; ro.hold = o->hold; ro.final_only = o->final_only; }
-    const bool any = Q->R.qpos || Q->R.qvel || Q->R.xpos || Q->R.xmat || Q->R.status || Q->ctrl_out;   // (here status or ctrl alone will do)
-    const std::string why = jaco_rollout_resolve_outputs(m, o ? &ro : nullptr, frame, n, nstates, num_envs, have_out, any,
-                                                         "at least one of the outputs qpos, qvel, xpos, xmat, status and ctrl is required", &Q->R);
+    const std::string why = jaco_rollout_resolve_outputs(m, o ? &ro : nullptr, frame, n, nstates, num_envs, have_out, any_output, no_output, &Q->R);
     if (!why.empty()) return why;
   }
   if (o->per_substep != 0 && o->per_substep != 1) return "per_substep must be 0 or 1";
@@ -71,18 +84,16 @@ static inline std::string jaco_rollout_fb_resolve(const JacoModelDev& m, const J
   Q->plan = *plan;
   Q->per_substep = o->per_substep;
   Q->ndofs = 0;
-  if (plan->gain) {
-    if (o->ndofs < 1 || o->ndofs > JROLLOUT_FB_MAX_DOFS) return "ndofs " + std::to_string(o->ndofs) + " outside [1, " + std::to_string(JROLLOUT_FB_MAX_DOFS) + "]";
-    for (int j = 0; j < o->ndofs; j++) {
-      const int d = o->dofs[j];
-      if (d < 0 || d >= m.nv) return "dof " + std::to_string(d) + " outside [0, " + std::to_string(m.nv) + ")";
-      if (m.d_qadr[d] < 0) return "dof " + std::to_string(d) + " belongs to a free joint";
-      for (int k = 0; k < j; k++) if (o->dofs[k] == d) return "dof " + std::to_string(d) + " is listed twice";
-      Q->dofs[j] = d;
-    }
-    Q->ndofs = o->ndofs;
-  }
+  if (plan->gain) return jaco_rollout_fb_dofs(m, o->ndofs, o->dofs, Q);
   return std::string();
+}
+
+// jaco_rollout_fb's own: status or ctrl alone will do as an output.
+static inline std::string jaco_rollout_fb_resolve(const JacoModelDev& m, const JacoRolloutFbOpts* o, const JacoQueryFrame* frame, int n, int nstates, int num_envs,
+                                                  const JacoRolloutFbPlan* plan, bool have_out, JacoRolloutFbArgs* Q) {
+  return jaco_rollout_fb_resolve_outputs(m, o, frame, n, nstates, num_envs, plan, have_out,
+                                         Q->R.qpos || Q->R.qvel || Q->R.xpos || Q->R.xmat || Q->R.status || Q->ctrl_out,
+                                         "at least one of the outputs qpos, qvel, xpos, xmat, status and ctrl is required", Q);
 }
 
 // One evaluation of the law (the header's order of operations) for rollout i on plan p at knot k, into s.ctrl and row `erow` of the ctrl

@@ -67,6 +67,49 @@ class Contacts:
         return (fw * sgn[..., None]).sum(1)
 
 
+def _closed_loop_args(sim, what, ctrl, qpos, qvel, gain, x_ref, dofs, feedforward, alpha, plan_index, state_index, noise=None):
+    """The arguments BatchedMujoco.rollout_feedback and rollout_cost share (a function of the module, so that a stand-in sim which borrows
+    the two methods needs nothing but the launch methods), checked and made contiguous device tensors: {"plan": {"ctrl", "kff",
+    "gain", "xref"}, "alpha", "plan_index", "state_index", "qpos", "qvel", "nstates", "n", "T", "dofs", "noise"}.  n is the length
+    of whichever of plan_index, state_index, alpha and noise is given (all the same), else the number of plans."""
+    dev = sim.device
+    f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+    ctrl, gain, x_ref, kff, alpha, noise = f32(ctrl), f32(gain), f32(x_ref), f32(feedforward), f32(alpha), f32(noise)
+    if ctrl.dim() != 3 or ctrl.shape[2] != sim.nu:
+        raise ValueError("%s: ctrl has shape %s, not [P, T, %d]" % (what, tuple(ctrl.shape), sim.nu))
+    P, T = int(ctrl.shape[0]), int(ctrl.shape[1])
+    if kff is not None and kff.shape != ctrl.shape:
+        raise ValueError("%s: feedforward has shape %s, not ctrl's %s" % (what, tuple(kff.shape), tuple(ctrl.shape)))
+    dofs = [] if dofs is None else [int(d) for d in dofs]
+    if gain is not None:
+        nx = 2 * len(dofs)
+        if not dofs:
+            raise ValueError("%s: a gain needs dofs" % what)
+        if gain.shape != (P, T, sim.nu, nx):
+            raise ValueError("%s: gain has shape %s, not [%d, %d, %d, %d] (2 x %d dofs)" % (what, tuple(gain.shape), P, T, sim.nu, nx, len(dofs)))
+        if x_ref is None or x_ref.shape != (P, T, nx):
+            raise ValueError("%s: x_ref has shape %s, not [%d, %d, %d]" % (what, None if x_ref is None else tuple(x_ref.shape), P, T, nx))
+    if alpha is not None and kff is None:
+        raise ValueError("%s: alpha needs feedforward" % what)
+    if noise is not None and (noise.dim() != 3 or tuple(noise.shape[1:]) != (T, sim.nu)):
+        raise ValueError("%s: noise has shape %s, not [n, %d, %d]" % (what, tuple(noise.shape), T, sim.nu))
+    q, v = _rows(qpos, dev, sim.nq), _rows(qvel, dev, sim.nv)
+    if q is not None and v is not None and q.shape[0] != v.shape[0]:
+        raise ValueError("%s: %d qpos rows but %d qvel rows" % (what, q.shape[0], v.shape[0]))
+    nstates = sim.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
+    pidx, sidx = sim._index(plan_index), sim._index(state_index)
+    alpha = None if alpha is None else alpha.reshape(-1).contiguous()
+    counts = {k: t.numel() for k, t in (("plan_index", pidx), ("state_index", sidx), ("alpha", alpha)) if t is not None}
+    if noise is not None:
+        counts["noise"] = int(noise.shape[0])
+    if len(set(counts.values())) > 1:
+        raise ValueError("%s: %s" % (what, " but ".join("%d entries of %s" % (c, k) for k, c in counts.items())))
+    n = next(iter(counts.values())) if counts else P
+    c = lambda t: None if t is None else t.contiguous()
+    plan = {"ctrl": ctrl.contiguous(), "kff": c(kff), "gain": c(gain), "xref": c(x_ref) if gain is not None else None}
+    return dict(plan=plan, alpha=alpha, plan_index=pidx, state_index=sidx, qpos=q, qvel=v, nstates=nstates, n=n, T=T, dofs=dofs, noise=c(noise))
+
+
 class BatchedMujoco:
     def __init__(self, num_envs, robot_file="jaco2_curtain_torque", device=0, frame_skip=50, task=0, seed=0):
         if not torch.cuda.is_available():
@@ -422,40 +465,83 @@ class BatchedMujoco:
         Returns rollout()'s dict plus "ctrl" [n, E, nu]: the u of every evaluation as commanded (E = T, or T * hold with per_substep),
         all E rows also with final_only.  status: _lib.JACO_ROLLOUT_BAD_INDEX where plan_index or state_index was out of range.  One
         launch on the current stream, no synchronisation; the sim's state is not touched."""
-        dev = self.device
-        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
-        ctrl, gain, x_ref, kff, alpha = f32(ctrl), f32(gain), f32(x_ref), f32(feedforward), f32(alpha)
-        if ctrl.dim() != 3 or ctrl.shape[2] != self.nu:
-            raise ValueError("rollout_feedback: ctrl has shape %s, not [P, T, %d]" % (tuple(ctrl.shape), self.nu))
-        P, T = int(ctrl.shape[0]), int(ctrl.shape[1])
-        if kff is not None and kff.shape != ctrl.shape:
-            raise ValueError("rollout_feedback: feedforward has shape %s, not ctrl's %s" % (tuple(kff.shape), tuple(ctrl.shape)))
-        dofs = [] if dofs is None else [int(d) for d in dofs]
-        if gain is not None:
-            nx = 2 * len(dofs)
-            if not dofs:
-                raise ValueError("rollout_feedback: a gain needs dofs")
-            if gain.shape != (P, T, self.nu, nx):
-                raise ValueError("rollout_feedback: gain has shape %s, not [%d, %d, %d, %d] (2 x %d dofs)" % (tuple(gain.shape), P, T, self.nu, nx, len(dofs)))
-            if x_ref is None or x_ref.shape != (P, T, nx):
-                raise ValueError("rollout_feedback: x_ref has shape %s, not [%d, %d, %d]" % (None if x_ref is None else tuple(x_ref.shape), P, T, nx))
-        if alpha is not None and kff is None:
-            raise ValueError("rollout_feedback: alpha needs feedforward")
-        q, v = _rows(qpos, dev, self.nq), _rows(qvel, dev, self.nv)
-        if q is not None and v is not None and q.shape[0] != v.shape[0]:
-            raise ValueError("rollout_feedback: %d qpos rows but %d qvel rows" % (q.shape[0], v.shape[0]))
-        nstates = self.num_envs if q is None and v is None else (q if q is not None else v).shape[0]
-        pidx, sidx = self._index(plan_index), self._index(state_index)
-        alpha = None if alpha is None else alpha.reshape(-1).contiguous()
-        counts = {k: t.numel() for k, t in (("plan_index", pidx), ("state_index", sidx), ("alpha", alpha)) if t is not None}
-        if len(set(counts.values())) > 1:
-            raise ValueError("rollout_feedback: %s" % " but ".join("%d entries of %s" % (c, k) for k, c in counts.items()))
-        n = next(iter(counts.values())) if counts else P
+        a = _closed_loop_args(self, "rollout_feedback", ctrl, qpos, qvel, gain, x_ref, dofs, feedforward, alpha, plan_index, state_index)
         want = ("qpos", "qvel", "status", "ctrl") + (("xpos", "xmat") if frame is not None else ())
-        c = lambda t: None if t is None else t.contiguous()
-        plan = {"ctrl": ctrl.contiguous(), "kff": c(kff), "gain": c(gain), "xref": c(x_ref) if gain is not None else None}
-        return self._rollout_fb(plan, alpha, pidx, q, v, sidx, nstates, frame, want, n, nknots=T, hold=int(hold), final_only=int(bool(final_only)),
-                                per_substep=int(bool(per_substep)), dofs=dofs if gain is not None else ())
+        return self._rollout_fb(a["plan"], a["alpha"], a["plan_index"], a["qpos"], a["qvel"], a["state_index"], a["nstates"], frame, want, a["n"], nknots=a["T"],
+                                hold=int(hold), final_only=int(bool(final_only)), per_substep=int(bool(per_substep)), dofs=a["dofs"] if a["plan"]["gain"] is not None else ())
+
+    # ---- costed rollouts (jaco_rollout_cost: jaco_rollout_fb with noise added and the running cost accumulated inside the kernel, one launch)
+    def _rollout_cost(self, plan, goal, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        """One jaco_rollout_cost launch: {name: tensor} of the outputs in `want` (names of JacoRolloutCostOut), in the C ABI's layout.
+        plan: as _rollout_fb's; goal: {"noise": [n, nknots, nu], "xgoal": [P, G, nx], "pgoal": [P, G, 3]: tensors or None}; options: the
+        keywords of _lib.JacoRolloutCostOptions."""
+        dev = self.device
+        rows = 1 if options.get("final_only") else options["nknots"]
+        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
+                  "ctrl": (n, options["nknots"], self.nu), "cost": (n,), "terms": (n, 3)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
+        if n == 0:   # (no launch: jaco_rollout_cost returns JACO_OK for n == 0)
+            return res
+        out = _lib.JacoRolloutCostOut(*[_ptr(res.get(k)) for k in shapes])
+        rec = _lib.JacoRolloutPlan(_ptr(plan["ctrl"]), _ptr(plan.get("kff")), _ptr(plan.get("gain")), _ptr(plan.get("xref")), _ptr(alpha), _ptr(plan_index),
+                                   int(plan["ctrl"].shape[0]))
+        g = _lib.JacoRolloutGoal(_ptr(goal.get("noise")), _ptr(goal.get("xgoal")), _ptr(goal.get("pgoal")))
+        opt = _lib.JacoRolloutCostOptions(**options)
+        self._chk(self.L.jaco_rollout_cost(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
+                                           _ptr(qpos), _ptr(qvel), _ref(rec), _ref(g), _ref(out), self._stream()))
+        return res
+
+    def rollout_cost(self, ctrl, qpos=None, qvel=None, noise=None, gain=None, x_ref=None, dofs=None, feedforward=None, alpha=None, plan_index=None,
+                     state_index=None, hold=1, frame=None, x_goal=None, p_goal=None, wx=None, wx_final=None, wu=None, wp=0.0, wp_final=0.0,
+                     want=("cost", "terms", "status"), final_only=False):
+        """rollout_feedback() costed inside the kernel -- what MPPI, CEM, random shooting and iLQR's line search want of a rollout: one
+        number.  The plans, the law (evaluated once per knot), the states and the indices are rollout_feedback()'s.  noise [n, T, nu]:
+        added to the law's u in one fp32 add; the sum is applied and is what "ctrl" holds.  The cost of rollout i on plan p,
+            J = sum_k [ 1/2 sum_a wu[a] u_ka^2 + 1/2 sum_j WX_k[j] (x_(k+1)j - x_goal[p, g, j])^2 + 1/2 WP_k |pos_(k+1) - p_goal[p, g]|^2 ],
+        x = [qpos at the hinge dofs `dofs`, qvel at them] and pos the position of `frame` after knot k (the words row k of "qpos" /
+        "qvel" / "xpos" holds), (WX, WP) = (wx, wp) on the running knots and (wx_final, wp_final) on the last; differences are not
+        wrapped.  Goals: x_goal [P, 2 nd] or [P, T, 2 nd], p_goal [P, 3] or [P, T, 3] (one goal per plan, or one per plan and knot; both
+        the same way).  Weights: wx / wx_final [2 nd], wu [nu] (scalars broadcast), wp / wp_final scalars, all finite and >= 0; None: zeros.
+        Returns only the tensors named in `want`, of "cost" [n], "terms" [n, 3] (the ctrl, state and pose parts), "status" [n] and
+        rollout_feedback()'s "qpos", "qvel", "xpos", "xmat", "ctrl"; a rollout whose status has JACO_FLAG_NAN has cost = terms = +inf.
+        cost and terms do not depend on `want` or final_only, bit for bit.  One launch on the current stream, no synchronisation; the
+        sim's state is not touched."""
+        what = "rollout_cost"
+        a = _closed_loop_args(self, what, ctrl, qpos, qvel, gain, x_ref, dofs, feedforward, alpha, plan_index, state_index, noise)
+        dev, P, T, nx = self.device, int(a["plan"]["ctrl"].shape[0]), a["T"], 2 * len(a["dofs"])
+        known = ("qpos", "qvel", "xpos", "xmat", "status", "ctrl", "cost", "terms")
+        want = tuple(want)
+        if not want or set(want) - set(known):
+            raise ValueError("%s: want %s names none or not only outputs (%s)" % (what, want, ", ".join(known)))
+
+        def goal(t, width, name):
+            if t is None:
+                return None, None
+            t = torch.as_tensor(t, dtype=torch.float32, device=dev)
+            if tuple(t.shape) == (P, width):
+                return t.reshape(P, 1, width).contiguous(), 0
+            if tuple(t.shape) == (P, T, width):
+                return t.contiguous(), 1
+            raise ValueError("%s: %s has shape %s, not [%d, %d] or [%d, %d, %d]" % (what, name, tuple(t.shape), P, width, P, T, width))
+        xg, per_x = goal(x_goal, nx, "x_goal")
+        pg, per_p = goal(p_goal, 3, "p_goal")
+        if per_x is not None and per_p is not None and per_x != per_p:
+            raise ValueError("%s: x_goal is given per %s but p_goal per %s" % (what, *[("plan", "plan and knot")[m] for m in (per_x, per_p)]))
+
+        def weights(w, width, name):
+            if w is None:
+                return ()
+            w = np.asarray(torch.as_tensor(w).detach().cpu().numpy() if torch.is_tensor(w) else w, np.float64)
+            if w.ndim == 0:
+                w = np.full(width, float(w))
+            if w.shape != (width,):
+                raise ValueError("%s: %s has shape %s, not [%d]" % (what, name, tuple(w.shape), width))
+            return w
+        options = dict(nknots=T, hold=int(hold), final_only=int(bool(final_only)), goal_per_knot=int(bool(per_x or per_p)),
+                       dofs=a["dofs"] if (a["plan"]["gain"] is not None or xg is not None) else (),
+                       wx=weights(wx, nx, "wx"), wxT=weights(wx_final, nx, "wx_final"), wu=weights(wu, self.nu, "wu"), wp=float(wp), wpT=float(wp_final))
+        return self._rollout_cost(a["plan"], {"noise": a["noise"], "xgoal": xg, "pgoal": pg}, a["alpha"], a["plan_index"], a["qpos"], a["qvel"],
+                                  a["state_index"], a["nstates"], frame, want, a["n"], **options)
 
     # ---- the iLQR / TVLQR backward pass (jaco_lqr: the whole recursion of every problem in one launch)
     def _lqr(self, opt, prob, out, n):

@@ -409,6 +409,130 @@ class BatchedMujocoConfig:
         out["status"] = r["status"].reshape(B, A)
         return {key: t[:, 0] for key, t in out.items()} if alphas is None else out
 
+    def rollout_cost(self, u, noise=None, K=None, x_ref=None, k=None, alphas=None, joints=None, q_goal=None, dq_goal=None, ee_goal=None, w_q=0.0,
+                     w_dq=0.0, w_ee=0.0, w_u=0.0, w_q_final=None, w_dq_final=None, w_ee_final=None, ctrl=None, hold=1, q=None, dq=None,
+                     trajectories=False):
+        """rollout_feedback() costed inside the kernel, on the same joints (x = [q_J, dq_J], 2 n) and motor words (m): what a sampling
+        planner or iLQR's line search wants of a rollout.  Env b follows its plan (u [B, T, m], K, x_ref, k as rollout_feedback()) with
+        either noise [B, S, T, m] -- S samples per env, sample s applies u_t + noise[b, s, t] (one fp32 add onto the law's value) -- or
+        alphas [A] step sizes, not both; the S (or A) rollouts of an env share its plan, goals and state through indices, nothing is
+        copied.  The cost of a rollout:
+            sum_t [ 1/2 w_u |u_t|^2 + 1/2 sum_j w_q[j] (q_(t+1)j - q_goal[b, j])^2 + 1/2 sum_j w_dq[j] (dq_(t+1)j - dq_goal[b, j])^2
+                    + 1/2 w_ee |ee_(t+1) - ee_goal[b]|^2 ]
+        with the *_final weights on the last knot (None: the running weight).  Goals: q_goal / dq_goal [B, n] or [B, T, n] (one missing:
+        zeros, weight and all), ee_goal [B, 3] or [B, T, 3], all per env or all per env and knot.  Weights: scalars, or [n] (w_q, w_dq)
+        and [m] (w_u) vectors; u is the commanded motor words, before the actuators' clamp; the other ctrl words (ctrl [B, nu], None:
+        zeros) carry no cost.
+        {"cost": [B, S], "terms": [B, S, 3] (ctrl, state and pose parts), "status": [B, S]}, a non-finite rollout costing +inf; with
+        trajectories=True also rollout_feedback()'s "q", "dq", "ee_pos", "ee_mat", "u", every knot; without noise and alphas the S axis
+        is squeezed.  One jaco_rollout_cost launch (BatchedMujoco.rollout_cost); the sim's state is not touched."""
+        import torch
+        B, dev, nu = self.sim.num_envs, self.sim.device, self.sim.nu
+        dofs, qadr, acts = self._joint_subset(joints, "rollout_cost")
+        n, m = len(dofs), len(acts)
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+        u, K, x_ref, k, noise = f32(u), f32(K), f32(x_ref), f32(k), f32(noise)
+        if u.dim() != 3 or u.shape[0] != B or u.shape[2] != m:
+            raise ValueError("rollout_cost: u has shape %s, not [%d, T, %d]" % (tuple(u.shape), B, m))
+        T = int(u.shape[1])
+        if k is not None and k.shape != u.shape:
+            raise ValueError("rollout_cost: k has shape %s, not u's %s" % (tuple(k.shape), tuple(u.shape)))
+        if K is not None:
+            if K.shape != (B, T, m, 2 * n):
+                raise ValueError("rollout_cost: K has shape %s, not [%d, %d, %d, %d]" % (tuple(K.shape), B, T, m, 2 * n))
+            if x_ref is None or x_ref.shape != (B, T, 2 * n):
+                raise ValueError("rollout_cost: x_ref has shape %s, not [%d, %d, %d]" % (None if x_ref is None else tuple(x_ref.shape), B, T, 2 * n))
+        if alphas is not None and k is None:
+            raise ValueError("rollout_cost: alphas need k")
+        if alphas is not None and noise is not None:
+            raise ValueError("rollout_cost: noise or alphas, not both")
+        if noise is not None and (noise.dim() != 4 or noise.shape[0] != B or tuple(noise.shape[2:]) != (T, m)):
+            raise ValueError("rollout_cost: noise has shape %s, not [%d, S, %d, %d]" % (tuple(noise.shape), B, T, m))
+        base = torch.zeros(B, nu, dtype=torch.float32, device=dev) if ctrl is None else f32(ctrl).reshape(B, nu)
+        full = base[:, None, :].repeat(1, T, 1)
+        full[:, :, acts] = u
+        kff = gain = None
+        if k is not None:
+            kff = torch.zeros_like(full)
+            kff[:, :, acts] = k
+        if K is not None:
+            gain = torch.zeros(B, T, nu, 2 * n, dtype=torch.float32, device=dev)
+            gain[:, :, acts] = K
+        index = alpha = eps = None
+        S = 1
+        if alphas is not None:
+            alphas = f32(alphas).reshape(-1)
+            S = int(alphas.numel())
+            alpha = alphas.repeat(B)
+        if noise is not None:
+            S = int(noise.shape[1])
+            eps = torch.zeros(B * S, T, nu, dtype=torch.float32, device=dev)
+            eps[:, :, acts] = noise.reshape(B * S, T, m)
+        if alphas is not None or noise is not None:
+            index = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(S)
+        # the goals: x_goal = [q_goal, dq_goal], per env or per env and knot
+        goals = {name: f32(t) for name, t in (("q_goal", q_goal), ("dq_goal", dq_goal), ("ee_goal", ee_goal)) if t is not None}
+        for name, t in goals.items():
+            width = 3 if name == "ee_goal" else n
+            if tuple(t.shape) not in ((B, width), (B, T, width)):
+                raise ValueError("rollout_cost: %s has shape %s, not [%d, %d] or [%d, %d, %d]" % (name, tuple(t.shape), B, width, B, T, width))
+        if len({t.dim() for t in goals.values()}) > 1:
+            raise ValueError("rollout_cost: the goals (%s) are given all per env or all per env and knot" % ", ".join(goals))
+        x_goal = None
+        if "q_goal" in goals or "dq_goal" in goals:
+            like = goals.get("q_goal", goals.get("dq_goal"))
+            x_goal = torch.cat([goals.get("q_goal", torch.zeros_like(like)), goals.get("dq_goal", torch.zeros_like(like))], -1)
+
+        def vec(w, width, name):
+            w = np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, np.float64)
+            if w.ndim == 0:
+                return np.full(width, float(w))
+            if w.shape != (width,):
+                raise ValueError("rollout_cost: %s has shape %s, not [%d]" % (name, tuple(w.shape), width))
+            return w
+        on = lambda name, w: vec(w, n, name) * (name.split("_")[1] + "_goal" in goals)   # (a goal that is not given weighs nothing)
+        last = lambda w, running: running if w is None else w
+        wx = np.concatenate([on("w_q", w_q), on("w_dq", w_dq)])
+        wxT = np.concatenate([on("w_q_final", last(w_q_final, w_q)), on("w_dq_final", last(w_dq_final, w_dq))])
+        wu = np.zeros(nu)
+        wu[acts] = vec(w_u, m, "w_u")
+        pose = "ee_goal" in goals
+        qpos, qvel = self._spliced(q, dq)
+        want = ("cost", "terms", "status") + (("qpos", "qvel", "xpos", "xmat", "ctrl") if trajectories else ())
+        r = self.sim.rollout_cost(full, qpos, qvel, noise=eps, gain=gain, x_ref=x_ref, dofs=dofs, feedforward=kff, alpha=alpha, plan_index=index,
+                                  state_index=index, hold=hold, frame=self._frames[0], x_goal=x_goal if wx.any() or wxT.any() else None,
+                                  p_goal=goals.get("ee_goal"), wx=wx, wx_final=wxT, wu=wu, wp=float(w_ee) * pose,
+                                  wp_final=float(last(w_ee_final, w_ee)) * pose, want=want)
+        out = {"cost": r["cost"].reshape(B, S), "terms": r["terms"].reshape(B, S, 3), "status": r["status"].reshape(B, S)}
+        if trajectories:
+            tr = {"q": r["qpos"][..., qadr], "dq": r["qvel"][..., dofs], "ee_pos": r["xpos"], "ee_mat": r["xmat"], "u": r["ctrl"][..., acts]}
+            out.update({key: t.reshape(B, S, t.shape[-2], t.shape[-1]) for key, t in tr.items()})
+        return {key: t[:, 0] for key, t in out.items()} if index is None else out
+
+    def mppi_update(self, u, noise, cost, temperature, status=None):
+        """The MPPI update of the nominal from S costed samples per env: (u_new [B, T, m], weights [B, S]) with
+            w = softmax(-(cost - min cost) / temperature) over the samples,   u_new = u + sum_s w[b, s] noise[b, s]
+        for u [B, T, m], noise [B, S, T, m], cost [B, S] as rollout_cost(u, noise=noise) returns it.  A sample whose cost is not finite,
+        or whose status (rollout_cost's, optional) is anything but 0 or JACO_FLAG_SOLVER_MAXITER, gets weight 0; an env with no usable
+        sample keeps its u.  Batched torch on the sim's device, no synchronisation (small and memory-bound: not worth a kernel)."""
+        import torch
+        dev = self.sim.device
+        u, noise, cost = [torch.as_tensor(t, dtype=torch.float32, device=dev) for t in (u, noise, cost)]
+        if noise.dim() != 4 or tuple(noise.shape[:1] + noise.shape[2:]) != tuple(u.shape) or tuple(cost.shape) != tuple(noise.shape[:2]):
+            raise ValueError("mppi_update: u %s, noise %s and cost %s are not [B, T, m], [B, S, T, m] and [B, S]" % (tuple(u.shape), tuple(noise.shape), tuple(cost.shape)))
+        if not temperature > 0:
+            raise ValueError("mppi_update: the temperature %r is not positive" % (temperature,))
+        usable = torch.isfinite(cost)
+        if status is not None:
+            st = torch.as_tensor(status, device=dev).reshape(cost.shape)
+            usable = usable & ((st & ~_lib.JACO_FLAG_SOLVER_MAXITER) == 0)
+        c = torch.where(usable, cost, torch.full_like(cost, float("inf")))
+        lowest = torch.where(usable.any(1, keepdim=True), c.min(1, keepdim=True).values, torch.zeros_like(c[:, :1]))
+        e = torch.where(usable, torch.exp(-(c - lowest) / float(temperature)), torch.zeros_like(c))
+        w = e / e.sum(1, keepdim=True).clamp_min(1e-30)   # (the lowest usable sample contributes exp(0) = 1: the sum is >= 1, or 0 with no sample)
+        step = (w[:, :, None, None] * torch.where(usable[:, :, None, None], noise, torch.zeros_like(noise))).sum(1)
+        return u + step, w
+
     def ilqr_backward(self, A, B, lxx, luu, lux=None, lx=None, lu=None, Vxx=None, Vx=None, mu=None, joints=None, full=False):
         """The backward pass of iLQR on the joints and actuators that linearize(joints=...) and rollout_feedback(joints=...) use: x =
         [q_J, dq_J] (2 n), u the motor words of those joints in the same order (m).  A [B, T, 2 n, 2 n], B [B, T, 2 n, m]: linearize's,
