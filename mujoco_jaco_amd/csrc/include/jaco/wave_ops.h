@@ -2,6 +2,7 @@
 // so every "sync" below is wave-scoped.  All cross-lane calls must be reached by all 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <utility>
 
 #define JACO_WAVE 64
 #define JDEV __device__ __forceinline__
@@ -125,6 +126,77 @@ JDEV int row_argmax(float v, int idx, float* best) {
   return idx;
 }
 #undef JACO_ARGMAX_STEP
+
+// ---------------------------------------------------------------- row broadcasts folded into the arithmetic that reads them
+// The dense eliminations (physics_kernel.h ldl_block / ldl_block0_dual, env_logic.h gj_inverse6 / gj_solve6) update every element of a row with
+// "lane k's value of this register times my multiplier".  Where the whole block lies in one 16-lane row, a DPP operand (row_newbcast:K = lane K
+// of the lane's own row) reads that value inside the multiply-add itself: one VALU instruction instead of v_readlane_b32 + v_fma.
+// -DJACO_SOLVER_DPP=0 (A/B and bit-equality builds, tools/build_variant.sh solverbcast): the read-lane forms.
+#ifndef JACO_SOLVER_DPP
+#define JACO_SOLVER_DPP 1
+#endif
+// lane K of the lane's own row, in every lane.  The compiler folds this into a v_mul_f32 / v_add_f32 that reads it (v_mul_f32_dpp) and pads the
+// hazards itself; it does not fold it into an fma (v_mov_b32_dpp + v_fma_f32 stay two instructions), hence row_bcast_fnmac / row_bcast_fmac2 below.
+template <int K>
+JDEV float row_bcast(float v) { return dpp_f<0x150 + K>(v); }
+// a_i = fma(row_bcast<K>(a_i), -mul, a_i) for every argument, in the rows of RM (bit r = lanes 16 r .. 16 r + 15); the lanes of the other rows keep
+// their registers.  One statement for all of a pivot's elements: hipcc neither schedules nor pads what is inside an asm string, and a VGPR written
+// by the VALU needs two wait states before a DPP operand reads it (the s_nop 1 hipcc itself puts between a v_mul and a DPP reader of its result),
+// so the statement opens with that pad once; inside it no instruction reads what another has written.  Bits: fma(p, -m, a) = fma(-m, p, a).
+#define JROW_FNMAC(i) "v_fmac_f32_dpp %" #i ", %" #i ", -%[m] row_newbcast:%[k] row_mask:%[rm] bank_mask:0xf\n\t"
+#define JROW_IN : [m] "v"(mul), [k] "i"(K), [rm] "i"(RM)
+#define JROW_DEF template <int K, int RM> JDEV void row_bcast_fnmac
+JROW_DEF(float mul, float& a0) { asm volatile("s_nop 1\n\t" JROW_FNMAC(0) : "+v"(a0) JROW_IN); }
+JROW_DEF(float mul, float& a0, float& a1) { asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) : "+v"(a0), "+v"(a1) JROW_IN); }
+JROW_DEF(float mul, float& a0, float& a1, float& a2) { asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) : "+v"(a0), "+v"(a1), "+v"(a2) JROW_IN); }
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6, float& a7) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6) JROW_FNMAC(7)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6, float& a7, float& a8) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6) JROW_FNMAC(7) JROW_FNMAC(8)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(a8) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6, float& a7, float& a8, float& a9) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6) JROW_FNMAC(7) JROW_FNMAC(8) JROW_FNMAC(9)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(a8), "+v"(a9) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6, float& a7, float& a8, float& a9, float& a10) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6) JROW_FNMAC(7) JROW_FNMAC(8) JROW_FNMAC(9) JROW_FNMAC(10)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(a8), "+v"(a9), "+v"(a10) JROW_IN);
+}
+JROW_DEF(float mul, float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float& a6, float& a7, float& a8, float& a9, float& a10, float& a11) {
+  asm volatile("s_nop 1\n\t" JROW_FNMAC(0) JROW_FNMAC(1) JROW_FNMAC(2) JROW_FNMAC(3) JROW_FNMAC(4) JROW_FNMAC(5) JROW_FNMAC(6) JROW_FNMAC(7) JROW_FNMAC(8) JROW_FNMAC(9) JROW_FNMAC(10) JROW_FNMAC(11)
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(a8), "+v"(a9), "+v"(a10), "+v"(a11) JROW_IN);
+}
+#undef JROW_FNMAC
+#undef JROW_IN
+#undef JROW_DEF
+// the elements h[J0 + I...] of a row and its right-hand side b, as one statement
+template <int K, int RM, int J0, int N, int... I>
+JDEV void row_bcast_fnmac_cols(float (&h)[N], float& b, float mul, std::integer_sequence<int, I...>) { row_bcast_fnmac<K, RM>(mul, h[J0 + I]..., b); }
+// acc0 = fma(row_bcast<K>(x0), m0, acc0) and acc1 = fma(row_bcast<K>(x1), m1, acc1) in the rows of RM: the two sums of a dual back-substitution step
+template <int K, int RM>
+JDEV void row_bcast_fmac2(float& acc0, float x0, float m0, float& acc1, float x1, float m1) {
+  asm volatile("s_nop 1\n\t"
+               "v_fmac_f32_dpp %0, %2, %3 row_newbcast:%[k] row_mask:%[rm] bank_mask:0xf\n\t"
+               "v_fmac_f32_dpp %1, %4, %5 row_newbcast:%[k] row_mask:%[rm] bank_mask:0xf"
+               : "+v"(acc0), "+v"(acc1) : "v"(x0), "v"(m0), "v"(x1), "v"(m1), [k] "i"(K), [rm] "i"(RM));
+}
 
 JDEV unsigned long long wave_clock() { return __builtin_amdgcn_s_memtime(); }   // free-running shader clock
 JDEV int grid_size() { return (int)gridDim.x; }

@@ -17,6 +17,16 @@
 #include <stdint.h>
 #include <jaco/model_dev.h>
 #include <jaco/wave_ops.h>
+#ifdef JACO_EMULATED   // (the host emulator has no DPP operands: its builds keep the read-lane forms of the solver blocks, bit for bit what they were)
+#undef JACO_SOLVER_DPP
+#define JACO_SOLVER_DPP 0
+#endif
+// Kernels whose register budget the statements' operands would raise keep the read-lane forms too (profiles/solver_dpp.txt): in the 12-hinge
+// layout the huge tier's worker kernel (one more AGPR) and the open-loop rollout kernel (one more VGPR).
+#if defined(JACO_TU) && JNV == 18 && JB0 == 12 && (JACO_TU == 6 || JACO_TU == 15)
+#undef JACO_SOLVER_DPP
+#define JACO_SOLVER_DPP 0
+#endif
 
 // Three capacity tiers of the same kernel (DESIGN.md "Tiers"):
 //   light: <= 64 rows / 32 contacts / 64 candidates -> 1 constraint row per lane, ~17 KB LDS, the common case;
@@ -662,6 +672,59 @@ JDEV float add_rounded_product(float acc, float a, float b) {
 // this lane's row index if it is below HI, else -1 (no row of the block): `ldl_row > k` is "below pivot k, inside the block" in one compare
 template <int HI>
 JDEV int ldl_row(int lane) { return wave_opaque_i(lane < HI ? lane : -1); }
+#if JACO_SOLVER_DPP
+// The pivots K .. PE - 1 of a forward elimination over the columns up to CE, and the steps K .. LO of a back-substitution, for a block that lies
+// inside one 16-lane row (RM: that row's bit): ldl_block's loops below with the pivot as a template parameter, because the lane a DPP operand
+// reads is part of the instruction.  Per pivot one statement holds all the multiply-adds (wave_ops.h row_bcast_fnmac), elements in ascending order.
+template <int K, int PE, int CE, int RM>
+JDEV void ldl_fwd_row(float (&h)[JNV], float& b, float& dinv, bool& below, int row) {
+  if constexpr (K < PE) {
+    float dk = wave_bcast(h[K], K);
+    float inv = 1.f / dk;
+    dinv = below ? inv : dinv;
+    below = row > K;
+    float lik = below ? h[K] * inv : 0.f;
+    row_bcast_fnmac_cols<K % 16, RM, K + 1>(h, b, lik, std::make_integer_sequence<int, CE - 1 - K>{});
+    ldl_fwd_row<K + 1, PE, CE, RM>(h, b, dinv, below, row);
+  }
+}
+template <int K, int LO, int HI>
+JDEV void ldl_back_row(float (&h)[JNV], float z, float dinv, float& acc, float& x, int row) {
+  if constexpr (K >= LO) {
+    x = row > K ? x : z - dinv * acc;
+    acc = K == HI - 1 ? fmaf(h[K], row_bcast<K % 16>(x), 0.f) : add_rounded_product(acc, h[K], row_bcast<K % 16>(x));
+    ldl_back_row<K - 1, LO, HI>(h, z, dinv, acc, x, row);
+  }
+}
+// the trailing pivots of ldl_block0_dual (both systems) and its back-substitution (both sums fused multiply-adds, as they always compiled)
+template <int K, int B0>
+JDEV void ldl_dual_fwd_row(float (&h)[JNV], float (&g)[B0 - JLDL_NSH], float& b, float& bd, float& dinv, float& dinvd, bool& below, int row) {
+  if constexpr (K < B0) {
+    float dk = wave_bcast(h[K], K), dkd = wave_bcast(g[K - JLDL_NSH], K);
+    float inv = 1.f / dk, invd = 1.f / dkd;
+    dinv = below ? inv : dinv;
+    dinvd = below ? invd : dinvd;
+    below = row > K;
+    float lik = below ? h[K] * inv : 0.f, likd = below ? g[K - JLDL_NSH] * invd : 0.f;
+    row_bcast_fnmac_cols<K, 1, K + 1>(h, b, lik, std::make_integer_sequence<int, B0 - 1 - K>{});
+    row_bcast_fnmac_cols<K, 1, K + 1 - JLDL_NSH>(g, bd, likd, std::make_integer_sequence<int, B0 - 1 - K>{});
+    ldl_dual_fwd_row<K + 1, B0>(h, g, b, bd, dinv, dinvd, below, row);
+  }
+}
+template <int K, int B0>
+JDEV void ldl_dual_back_row(float (&h)[JNV], float (&g)[B0 - JLDL_NSH], float z, float zd, float dinv, float dinvd, float& acc, float& accd, float& x, float& xd, int row, int lane) {
+  if constexpr (K >= 0) {
+    x = row > K ? x : z - dinv * acc;
+    xd = row > K ? xd : zd - dinvd * accd;
+    const float hk = h[K];
+    float multd = hk;   // (the damped system's multiplier differs only inside the trailing block, and keeps its lane mask: see below)
+    if constexpr (K >= JLDL_NSH) { const float gk = g[K - JLDL_NSH]; multd = lane >= JLDL_NSH ? gk : hk; }
+    multd = lane < K ? multd : 0.f;
+    row_bcast_fmac2<K, 1>(acc, x, hk, accd, xd, multd);
+    ldl_dual_back_row<K - 1, B0>(h, g, z, zd, dinv, dinvd, acc, accd, x, xd, row, lane);
+  }
+}
+#endif
 template <bool FULL>
 JDEV float ldl_solve(float (&h)[JNV], float b, int lane) {
   float dinv = 1.f;
@@ -701,38 +764,67 @@ JDEV float ldl_block(float (&h)[JNV], float b, int lane) {
   const int row = ldl_row<HI>(lane);
   float dinv = 1.f;
   bool below = true;
+#if JACO_SOLVER_DPP
+  // A block inside one 16-lane row ([0, JB0) and [JB0, JB1) of the default layout): the pivot row's elements reach the multiply-adds as DPP
+  // operands (wave_ops.h row_bcast_fnmac: one statement per pivot, elements in ascending order as before), the back-substitution's x_k as the
+  // DPP operand of its rounded product.  The same expressions in every lane of the block's row; the lanes of the other rows, which added
+  // -0 * p_k before, are left alone.  The pivot itself still goes through v_readlane: the reciprocal wants it in every lane.
+  if constexpr (LO / 16 == (HI - 1) / 16) {
+    ldl_fwd_row<LO, HI, HI, 1 << (LO / 16)>(h, b, dinv, below, row);
+    float z = b * dinv, acc = 0.f, x = 0.f;
+    ldl_back_row<HI - 1, LO, HI>(h, z, dinv, acc, x, row);
+    return row >= LO ? x : 0.f;
+  } else
+#endif
+  {
 #pragma unroll
-  for (int k = LO; k < HI; k++) {
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = below ? inv : dinv;
-    below = row > k;
-    float lik = below ? h[k] * inv : 0.f;
-    float pk[JNV];
+    for (int k = LO; k < HI; k++) {
+      float dk = wave_bcast(h[k], k);
+      float inv = 1.f / dk;
+      dinv = below ? inv : dinv;
+      below = row > k;
+      float lik = below ? h[k] * inv : 0.f;
+      float pk[JNV];
 #pragma unroll
-    for (int j = k + 1; j < HI; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
+      for (int j = k + 1; j < HI; j++) pk[j] = wave_bcast(h[j], k);
+      const float bk = wave_bcast(b, k);
 #pragma unroll
-    for (int j = k + 1; j < HI; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
+      for (int j = k + 1; j < HI; j++) h[j] -= lik * pk[j];
+      b -= lik * bk;
+    }
+    float z = b * dinv, acc = 0.f, x = 0.f;
+#pragma unroll
+    for (int k = HI - 1; k >= LO; k--) {
+      x = row > k ? x : z - dinv * acc;
+      float xk = wave_bcast(x, k);
+      acc = k == HI - 1 ? fmaf(h[k], xk, 0.f) : add_rounded_product(acc, h[k], xk);
+    }
+    return row >= LO ? x : 0.f;
   }
-  float z = b * dinv, acc = 0.f, x = 0.f;
-#pragma unroll
-  for (int k = HI - 1; k >= LO; k--) {
-    x = row > k ? x : z - dinv * acc;
-    float xk = wave_bcast(x, k);
-    acc = k == HI - 1 ? fmaf(h[k], xk, 0.f) : add_rounded_product(acc, h[k], xk);
-  }
-  return row >= LO ? x : 0.f;
 }
 // Arm/finger block [0, JB0) with implicit joint damping: x = M^-1 b and xd = (M + diag(hd))^-1 b from ONE elimination where
 // the two matrices agree.  hd is non-zero only on the last JB0 - NSH dofs (the finger joints, leaves of the arm's tree), so
 // the first NSH pivots, their multipliers and the forward-substituted right-hand side are identical; only the trailing
 // (JB0 - NSH) x (JB0 - NSH) Schur complement differs (by hd on its diagonal).  Returns x, *xd_out = xd (0 outside the block).
+template <int B0 = JB0>   // (a parameter so that the one-row form below is compiled only where the block fits a row)
 JDEV float ldl_block0_dual(float (&h)[JNV], float b, float hd, int lane, float* xd_out) {
   const int row = ldl_row<JB0>(lane);
   float dinv = 1.f;
   bool below = true;
+#if JACO_SOLVER_DPP
+  // (the block inside lanes 0..15: DPP operands as in ldl_block; both back-substitution sums are fused multiply-adds here, as they compiled before)
+  if constexpr (B0 <= 16) {
+    ldl_fwd_row<0, JLDL_NSH, B0, 1>(h, b, dinv, below, row);
+    float g[B0 - JLDL_NSH], bd = b, dinvd = dinv;
+#pragma unroll
+    for (int j = JLDL_NSH; j < B0; j++) g[j - JLDL_NSH] = h[j] + (lane == j ? hd : 0.f);
+    ldl_dual_fwd_row<JLDL_NSH, B0>(h, g, b, bd, dinv, dinvd, below, row);
+    float z = b * dinv, zd = bd * dinvd, acc = 0.f, accd = 0.f, x = 0.f, xd = 0.f;
+    ldl_dual_back_row<B0 - 1, B0>(h, g, z, zd, dinv, dinvd, acc, accd, x, xd, row, lane);
+    *xd_out = row >= 0 ? xd : 0.f;
+    return row >= 0 ? x : 0.f;
+  }
+#endif
 #pragma unroll
   for (int k = 0; k < JLDL_NSH; k++) {
     float dk = wave_bcast(h[k], k);
