@@ -378,96 +378,7 @@ JDEV void jaco_reset_env(const JacoResetArgs& R, int e) {
 }
 
 // ---------------------------------------------------------------- a4/a5: operational-space controller on the wave
-// 6x6 Gauss-Jordan, one matrix row per lane (lanes 0..5), no pivoting (SPD input). B in: identity row; out: inverse row.
-#if JACO_SOLVER_DPP
-// Pivots K .. 5 with the pivot row as the DPP operand of the multiply-adds (wave_ops.h row_bcast_fnmac: rows 0..5 lie in the first 16-lane row; what
-// lanes 16..63 hold is no row of the matrix and is read by nobody).  A statement's instructions cannot be dropped one by one as dead, so only the
-// live ones are written: the columns of A right of the pivot (a column is last read at its own pivot), all of B.
-template <int K, int... I>
-JDEV void gj_elim_row(float (&A)[6], float (&B)[6], float f, std::integer_sequence<int, I...>) {
-  row_bcast_fnmac<K, 1>(f, A[K + 1 + I]..., B[0], B[1], B[2], B[3], B[4], B[5]);
-}
-template <int K, int... I>
-JDEV void gj_elim_row(float (&A)[6], float& b, float f, std::integer_sequence<int, I...>) { row_bcast_fnmac<K, 1>(f, A[K + 1 + I]..., b); }
-template <int K>
-JDEV void gj_inverse6_row(float (&A)[6], float (&B)[6], float& det, int lane) {
-  if constexpr (K < 6) {
-    float piv = wave_bcast(A[K], K);
-    det *= piv;
-    float inv = 1.f / piv, sc = lane == K ? inv : 1.f;
-#pragma unroll
-    for (int j = 0; j < 6; j++) { A[j] *= sc; B[j] *= sc; }
-    float f = lane == K ? 0.f : A[K];
-    gj_elim_row<K>(A, B, f, std::make_integer_sequence<int, 5 - K>{});
-    gj_inverse6_row<K + 1>(A, B, det, lane);
-  }
-}
-template <int K>
-JDEV void gj_solve6_row(float (&A)[6], float& b, float& det, int lane) {
-  if constexpr (K < 6) {
-    float piv = wave_bcast(A[K], K);
-    det *= piv;
-    float inv = 1.f / piv, sc = lane == K ? inv : 1.f;
-#pragma unroll
-    for (int j = 0; j < 6; j++) A[j] *= sc;
-    b *= sc;
-    float f = lane == K ? 0.f : A[K];
-    gj_elim_row<K>(A, b, f, std::make_integer_sequence<int, 5 - K>{});
-    gj_solve6_row<K + 1>(A, b, det, lane);
-  }
-}
-#endif
-// (A is left in no defined state; no caller reads it afterwards)
-JDEV float gj_inverse6(float (&A)[6], float (&B)[6], int lane) {
-  float det = 1.f;
-#if JACO_SOLVER_DPP
-  gj_inverse6_row<0>(A, B, det, lane);
-#else
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    float piv = wave_bcast(A[k], k);
-    det *= piv;
-    float inv = 1.f / piv, sc = lane == k ? inv : 1.f;
-#pragma unroll
-    for (int j = 0; j < 6; j++) { A[j] *= sc; B[j] *= sc; }
-    float f = lane == k ? 0.f : A[k];
-    float pa[6], pb[6];   // (broadcasts first, then the updates: physics_kernel.h ldl_solve)
-#pragma unroll
-    for (int j = 0; j < 6; j++) { pa[j] = wave_bcast(A[j], k); pb[j] = wave_bcast(B[j], k); }
-#pragma unroll
-    for (int j = 0; j < 6; j++) { A[j] -= f * pa[j]; B[j] -= f * pb[j]; }
-  }
-#endif
-  return det;
-}
-
-// Same elimination with a single right-hand side: returns det, b becomes (A^-1 b)[lane].
-JDEV float gj_solve6(float (&A)[6], float& b, int lane) {
-  float det = 1.f;
-#if JACO_SOLVER_DPP
-  gj_solve6_row<0>(A, b, det, lane);
-#else
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    float piv = wave_bcast(A[k], k);
-    det *= piv;
-    float inv = 1.f / piv, sc = lane == k ? inv : 1.f;
-#pragma unroll
-    for (int j = 0; j < 6; j++) A[j] *= sc;
-    b *= sc;
-    float f = lane == k ? 0.f : A[k];
-    float pa[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) pa[j] = wave_bcast(A[j], k);
-    const float pbk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = 0; j < 6; j++) A[j] -= f * pa[j];
-    b -= f * pbk;
-  }
-#endif
-  return det;
-}
-
+// (its 6x6 eliminations gj_inverse6 / gj_solve6: solver_blocks.h)
 // Pseudo-inverse of a symmetric PSD 6x6 matrix X (LDS, destroyed) with abr_control's rule "singular values < 0.005 are
 // dropped" (np.linalg.svd branch of OSC.generate): Jacobi eigen-decomposition, V accumulated in LDS, result in `out`.
 // Parallel (round-robin) ordering: each of the 5 rounds of a sweep applies 3 rotations on disjoint index pairs at once,

@@ -128,13 +128,10 @@ JDEV int row_argmax(float v, int idx, float* best) {
 #undef JACO_ARGMAX_STEP
 
 // ---------------------------------------------------------------- row broadcasts folded into the arithmetic that reads them
-// The dense eliminations (physics_kernel.h ldl_block / ldl_block0_dual, env_logic.h gj_inverse6 / gj_solve6) update every element of a row with
+// The dense eliminations (solver_blocks.h ldl_block / ldl_block0_dual, gj_inverse6 / gj_solve6) update every element of a row with
 // "lane k's value of this register times my multiplier".  Where the whole block lies in one 16-lane row, a DPP operand (row_newbcast:K = lane K
 // of the lane's own row) reads that value inside the multiply-add itself: one VALU instruction instead of v_readlane_b32 + v_fma.
-// -DJACO_SOLVER_DPP=0 (A/B and bit-equality builds, tools/build_variant.sh solverbcast): the read-lane forms.
-#ifndef JACO_SOLVER_DPP
-#define JACO_SOLVER_DPP 1
-#endif
+// (Which form a build takes: solver_blocks.h.)
 // lane K of the lane's own row, in every lane.  The compiler folds this into a v_mul_f32 / v_add_f32 that reads it (v_mul_f32_dpp) and pads the
 // hazards itself; it does not fold it into an fma (v_mov_b32_dpp + v_fma_f32 stay two instructions), hence row_bcast_fnmac / row_bcast_fmac2 below.
 template <int K>

@@ -17,16 +17,6 @@
 #include <stdint.h>
 #include <jaco/model_dev.h>
 #include <jaco/wave_ops.h>
-#ifdef JACO_EMULATED   // (the host emulator has no DPP operands: its builds keep the read-lane forms of the solver blocks, bit for bit what they were)
-#undef JACO_SOLVER_DPP
-#define JACO_SOLVER_DPP 0
-#endif
-// Kernels whose register budget the statements' operands would raise keep the read-lane forms too (profiles/solver_dpp.txt): in the 12-hinge
-// layout the huge tier's worker kernel (one more AGPR) and the open-loop rollout kernel (one more VGPR).
-#if defined(JACO_TU) && JNV == 18 && JB0 == 12 && (JACO_TU == 6 || JACO_TU == 15)
-#undef JACO_SOLVER_DPP
-#define JACO_SOLVER_DPP 0
-#endif
 
 // Three capacity tiers of the same kernel (DESIGN.md "Tiers"):
 //   light: <= 64 rows / 32 contacts / 64 candidates -> 1 constraint row per lane, ~17 KB LDS, the common case;
@@ -530,362 +520,8 @@ JDEV f2 comp_advance(float hi, float lo, float hh, float hl, float v, float v_lo
   return comp_add(hi, lo, p, pe + fmaf(hh, v_lo, hl * v));
 }
 
-// ---------------------------------------------------------------- LDL^T solve, one matrix row per lane
-// h[j] = A[lane][j] (lanes >= n must hold identity rows), b = rhs[lane]; returns x[lane]. Registers only.
-// FULL = false: A is block diagonal over the dof blocks [0,JB0) [JB0,JB1) [JB1,JNV) (always true for the mass
-// matrix; true for the Newton Hessian unless an active row couples two blocks): 66 instead of 210 eliminations.
-// The lane masks of the eliminations.  Forward pass: lane i is a row below pivot k when i > k (and i < HI: a singular pivot's inf stays out of
-// the other blocks' rows); that one predicate per pivot also says who takes 1 / d_k as its own (every lane with k <= i does, pivot after
-// pivot, so lane i ends with 1 / d_i) and, negated, who takes x in the back-substitution (every lane with i <= k does, k descending, so
-// lane i ends with the value of step k = i).  The back-substitution's sum needs no mask at all: lane i reads `acc` once, at step k = i,
-// before that step's add, and every add it has seen by then had i < k; what steps k <= i add afterwards (the row's own entries times x_k,
-// possibly inf or NaN in lanes outside the block) is never read -- x is taken before, lanes outside [LO, HI) never keep x, and the
-// return is masked.  The terms keep their rounding: the first is h x + 0 in one fma, the others a rounded product and an add, as the
-// masked sum compiled.  -DJACO_SOLVER_MASKS=1 (A/B and bit-equality builds, tools/build_variant.sh solvermasks): one compare per role and
-// the masked sum, as before.
-#ifndef JACO_SOLVER_MASKS
-#define JACO_SOLVER_MASKS 0
-#endif
-#define JLDL_NSH 6
-#if JACO_SOLVER_MASKS
-template <bool FULL>
-JDEV float ldl_solve(float (&h)[JNV], float b, int lane) {
-  float dinv = 1.f;
-#pragma unroll
-  for (int k = 0; k < JNV; k++) {
-    const int jend = FULL ? JNV : (k < JB0 ? JB0 : (k < JB1 ? JB1 : JNV));
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = lane == k ? inv : dinv;
-    float lik = lane > k ? h[k] * inv : 0.f;
-    // (all of the pivot row's broadcasts first, then the updates: a v_readlane straight in front of the VALU that reads its SGPR
-    // costs two wait states on gfx950, and the compiler pairs them up when the source does)
-    float pk[JNV];
-#pragma unroll
-    for (int j = k + 1; j < jend; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = k + 1; j < jend; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
-  }
-  // now: b = y (L y = rhs); h[k>lane] = d_lane * L[k][lane]
-  float z = b * dinv, acc = 0.f, x = 0.f;
-#pragma unroll
-  for (int k = JNV - 1; k >= 0; k--) {
-    x = lane == k ? z - dinv * acc : x;
-    float xk = wave_bcast(x, k);
-    acc += lane < k ? h[k] * xk : 0.f;
-  }
-  return x;
-}
-// Block-diagonal variant that factors only the dof blocks named in `mask` (bit 0: [0,JB0), bit 1: [JB0,JB1), bit 2: [JB1,JNV));
-// lanes of skipped blocks get x = 0.
-template <int LO, int HI>
-JDEV float ldl_block(float (&h)[JNV], float b, int lane) {
-  float dinv = 1.f;
-#pragma unroll
-  for (int k = LO; k < HI; k++) {
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = lane == k ? inv : dinv;
-    float lik = (lane > k && lane < HI) ? h[k] * inv : 0.f;
-    float pk[JNV];
-#pragma unroll
-    for (int j = k + 1; j < HI; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = k + 1; j < HI; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
-  }
-  float z = b * dinv, acc = 0.f, x = 0.f;
-#pragma unroll
-  for (int k = HI - 1; k >= LO; k--) {
-    x = lane == k ? z - dinv * acc : x;
-    float xk = wave_bcast(x, k);
-    acc += (lane < k && lane >= LO) ? h[k] * xk : 0.f;
-  }
-  return (lane >= LO && lane < HI) ? x : 0.f;
-}
-// Arm/finger block [0, JB0) with implicit joint damping: x = M^-1 b and xd = (M + diag(hd))^-1 b from ONE elimination where
-// the two matrices agree.  hd is non-zero only on the last JB0 - NSH dofs (the finger joints, leaves of the arm's tree), so
-// the first NSH pivots, their multipliers and the forward-substituted right-hand side are identical; only the trailing
-// (JB0 - NSH) x (JB0 - NSH) Schur complement differs (by hd on its diagonal).  Returns x, *xd_out = xd (0 outside the block).
-JDEV float ldl_block0_dual(float (&h)[JNV], float b, float hd, int lane, float* xd_out) {
-  float dinv = 1.f;
-#pragma unroll
-  for (int k = 0; k < JLDL_NSH; k++) {
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = lane == k ? inv : dinv;
-    float lik = (lane > k && lane < JB0) ? h[k] * inv : 0.f;
-    float pk[JNV];
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
-  }
-  // trailing block, twice: plain (h, b, dinv) and damped (g, bd, dinvd)
-  float g[JB0 - JLDL_NSH], bd = b, dinvd = dinv;
-#pragma unroll
-  for (int j = JLDL_NSH; j < JB0; j++) g[j - JLDL_NSH] = h[j] + (lane == j ? hd : 0.f);
-#pragma unroll
-  for (int k = JLDL_NSH; k < JB0; k++) {
-    float dk = wave_bcast(h[k], k), dkd = wave_bcast(g[k - JLDL_NSH], k);
-    float inv = 1.f / dk, invd = 1.f / dkd;
-    dinv = lane == k ? inv : dinv;
-    dinvd = lane == k ? invd : dinvd;
-    const bool below = lane > k && lane < JB0;
-    float lik = below ? h[k] * inv : 0.f, likd = below ? g[k - JLDL_NSH] * invd : 0.f;
-    float pk[JNV], pg[JNV];
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) { pk[j] = wave_bcast(h[j], k); pg[j] = wave_bcast(g[j - JLDL_NSH], k); }
-    const float bk = wave_bcast(b, k), bdk = wave_bcast(bd, k);
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) { h[j] -= lik * pk[j]; g[j - JLDL_NSH] -= likd * pg[j]; }
-    b -= lik * bk;
-    bd -= likd * bdk;
-  }
-  // back-substitution: h[k > lane] = d_lane * L[k][lane] (shared for k < NSH columns... rows < NSH use h for both systems)
-  float z = b * dinv, zd = bd * dinvd, acc = 0.f, accd = 0.f, x = 0.f, xd = 0.f;
-#pragma unroll
-  for (int k = JB0 - 1; k >= 0; k--) {
-    x = lane == k ? z - dinv * acc : x;
-    xd = lane == k ? zd - dinvd * accd : xd;
-    float xk = wave_bcast(x, k), xdk = wave_bcast(xd, k);
-    // multiplier of row k in column `lane`: the damped system's differs only inside the trailing block
-    float mult = lane < k ? h[k] : 0.f;
-    float multd = (lane < k) ? ((k >= JLDL_NSH && lane >= JLDL_NSH) ? g[k - JLDL_NSH] : h[k]) : 0.f;
-    acc += mult * xk;
-    accd += multd * xdk;
-  }
-  *xd_out = lane < JB0 ? xd : 0.f;
-  return lane < JB0 ? x : 0.f;
-}
-#else
-// acc + a * b with the product rounded on its own, whatever the build's contraction mode (fmul_rn alone does not stop the add from fusing)
-JDEV float add_rounded_product(float acc, float a, float b) {
-#pragma clang fp contract(off)
-  return acc + a * b;
-}
-// this lane's row index if it is below HI, else -1 (no row of the block): `ldl_row > k` is "below pivot k, inside the block" in one compare
-template <int HI>
-JDEV int ldl_row(int lane) { return wave_opaque_i(lane < HI ? lane : -1); }
-#if JACO_SOLVER_DPP
-// The pivots K .. PE - 1 of a forward elimination over the columns up to CE, and the steps K .. LO of a back-substitution, for a block that lies
-// inside one 16-lane row (RM: that row's bit): ldl_block's loops below with the pivot as a template parameter, because the lane a DPP operand
-// reads is part of the instruction.  Per pivot one statement holds all the multiply-adds (wave_ops.h row_bcast_fnmac), elements in ascending order.
-template <int K, int PE, int CE, int RM>
-JDEV void ldl_fwd_row(float (&h)[JNV], float& b, float& dinv, bool& below, int row) {
-  if constexpr (K < PE) {
-    float dk = wave_bcast(h[K], K);
-    float inv = 1.f / dk;
-    dinv = below ? inv : dinv;
-    below = row > K;
-    float lik = below ? h[K] * inv : 0.f;
-    row_bcast_fnmac_cols<K % 16, RM, K + 1>(h, b, lik, std::make_integer_sequence<int, CE - 1 - K>{});
-    ldl_fwd_row<K + 1, PE, CE, RM>(h, b, dinv, below, row);
-  }
-}
-template <int K, int LO, int HI>
-JDEV void ldl_back_row(float (&h)[JNV], float z, float dinv, float& acc, float& x, int row) {
-  if constexpr (K >= LO) {
-    x = row > K ? x : z - dinv * acc;
-    acc = K == HI - 1 ? fmaf(h[K], row_bcast<K % 16>(x), 0.f) : add_rounded_product(acc, h[K], row_bcast<K % 16>(x));
-    ldl_back_row<K - 1, LO, HI>(h, z, dinv, acc, x, row);
-  }
-}
-// the trailing pivots of ldl_block0_dual (both systems) and its back-substitution (both sums fused multiply-adds, as they always compiled)
-template <int K, int B0>
-JDEV void ldl_dual_fwd_row(float (&h)[JNV], float (&g)[B0 - JLDL_NSH], float& b, float& bd, float& dinv, float& dinvd, bool& below, int row) {
-  if constexpr (K < B0) {
-    float dk = wave_bcast(h[K], K), dkd = wave_bcast(g[K - JLDL_NSH], K);
-    float inv = 1.f / dk, invd = 1.f / dkd;
-    dinv = below ? inv : dinv;
-    dinvd = below ? invd : dinvd;
-    below = row > K;
-    float lik = below ? h[K] * inv : 0.f, likd = below ? g[K - JLDL_NSH] * invd : 0.f;
-    row_bcast_fnmac_cols<K, 1, K + 1>(h, b, lik, std::make_integer_sequence<int, B0 - 1 - K>{});
-    row_bcast_fnmac_cols<K, 1, K + 1 - JLDL_NSH>(g, bd, likd, std::make_integer_sequence<int, B0 - 1 - K>{});
-    ldl_dual_fwd_row<K + 1, B0>(h, g, b, bd, dinv, dinvd, below, row);
-  }
-}
-template <int K, int B0>
-JDEV void ldl_dual_back_row(float (&h)[JNV], float (&g)[B0 - JLDL_NSH], float z, float zd, float dinv, float dinvd, float& acc, float& accd, float& x, float& xd, int row, int lane) {
-  if constexpr (K >= 0) {
-    x = row > K ? x : z - dinv * acc;
-    xd = row > K ? xd : zd - dinvd * accd;
-    const float hk = h[K];
-    float multd = hk;   // (the damped system's multiplier differs only inside the trailing block, and keeps its lane mask: see below)
-    if constexpr (K >= JLDL_NSH) { const float gk = g[K - JLDL_NSH]; multd = lane >= JLDL_NSH ? gk : hk; }
-    multd = lane < K ? multd : 0.f;
-    row_bcast_fmac2<K, 1>(acc, x, hk, accd, xd, multd);
-    ldl_dual_back_row<K - 1, B0>(h, g, z, zd, dinv, dinvd, acc, accd, x, xd, row, lane);
-  }
-}
-#endif
-template <bool FULL>
-JDEV float ldl_solve(float (&h)[JNV], float b, int lane) {
-  float dinv = 1.f;
-  bool below = true;   // of the pivot before: lane >= k
-#pragma unroll
-  for (int k = 0; k < JNV; k++) {
-    const int jend = FULL ? JNV : (k < JB0 ? JB0 : (k < JB1 ? JB1 : JNV));
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = below ? inv : dinv;
-    below = lane > k;
-    float lik = below ? h[k] * inv : 0.f;
-    // (all of the pivot row's broadcasts first, then the updates: a v_readlane straight in front of the VALU that reads its SGPR
-    // costs two wait states on gfx950, and the compiler pairs them up when the source does)
-    float pk[JNV];
-#pragma unroll
-    for (int j = k + 1; j < jend; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = k + 1; j < jend; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
-  }
-  // now: b = y (L y = rhs); h[k>lane] = d_lane * L[k][lane]
-  float z = b * dinv, acc = 0.f, x = 0.f;   // (lanes >= JNV never take x: 0)
-#pragma unroll
-  for (int k = JNV - 1; k >= 0; k--) {
-    x = lane > k ? x : z - dinv * acc;
-    float xk = wave_bcast(x, k);
-    acc = k == JNV - 1 ? fmaf(h[k], xk, 0.f) : add_rounded_product(acc, h[k], xk);
-  }
-  return x;
-}
-// Block-diagonal variant that factors only the dof blocks named in `mask` (bit 0: [0,JB0), bit 1: [JB0,JB1), bit 2: [JB1,JNV));
-// lanes of skipped blocks get x = 0.
-template <int LO, int HI>
-JDEV float ldl_block(float (&h)[JNV], float b, int lane) {
-  const int row = ldl_row<HI>(lane);
-  float dinv = 1.f;
-  bool below = true;
-#if JACO_SOLVER_DPP
-  // A block inside one 16-lane row ([0, JB0) and [JB0, JB1) of the default layout): the pivot row's elements reach the multiply-adds as DPP
-  // operands (wave_ops.h row_bcast_fnmac: one statement per pivot, elements in ascending order as before), the back-substitution's x_k as the
-  // DPP operand of its rounded product.  The same expressions in every lane of the block's row; the lanes of the other rows, which added
-  // -0 * p_k before, are left alone.  The pivot itself still goes through v_readlane: the reciprocal wants it in every lane.
-  if constexpr (LO / 16 == (HI - 1) / 16) {
-    ldl_fwd_row<LO, HI, HI, 1 << (LO / 16)>(h, b, dinv, below, row);
-    float z = b * dinv, acc = 0.f, x = 0.f;
-    ldl_back_row<HI - 1, LO, HI>(h, z, dinv, acc, x, row);
-    return row >= LO ? x : 0.f;
-  } else
-#endif
-  {
-#pragma unroll
-    for (int k = LO; k < HI; k++) {
-      float dk = wave_bcast(h[k], k);
-      float inv = 1.f / dk;
-      dinv = below ? inv : dinv;
-      below = row > k;
-      float lik = below ? h[k] * inv : 0.f;
-      float pk[JNV];
-#pragma unroll
-      for (int j = k + 1; j < HI; j++) pk[j] = wave_bcast(h[j], k);
-      const float bk = wave_bcast(b, k);
-#pragma unroll
-      for (int j = k + 1; j < HI; j++) h[j] -= lik * pk[j];
-      b -= lik * bk;
-    }
-    float z = b * dinv, acc = 0.f, x = 0.f;
-#pragma unroll
-    for (int k = HI - 1; k >= LO; k--) {
-      x = row > k ? x : z - dinv * acc;
-      float xk = wave_bcast(x, k);
-      acc = k == HI - 1 ? fmaf(h[k], xk, 0.f) : add_rounded_product(acc, h[k], xk);
-    }
-    return row >= LO ? x : 0.f;
-  }
-}
-// Arm/finger block [0, JB0) with implicit joint damping: x = M^-1 b and xd = (M + diag(hd))^-1 b from ONE elimination where
-// the two matrices agree.  hd is non-zero only on the last JB0 - NSH dofs (the finger joints, leaves of the arm's tree), so
-// the first NSH pivots, their multipliers and the forward-substituted right-hand side are identical; only the trailing
-// (JB0 - NSH) x (JB0 - NSH) Schur complement differs (by hd on its diagonal).  Returns x, *xd_out = xd (0 outside the block).
-template <int B0 = JB0>   // (a parameter so that the one-row form below is compiled only where the block fits a row)
-JDEV float ldl_block0_dual(float (&h)[JNV], float b, float hd, int lane, float* xd_out) {
-  const int row = ldl_row<JB0>(lane);
-  float dinv = 1.f;
-  bool below = true;
-#if JACO_SOLVER_DPP
-  // (the block inside lanes 0..15: DPP operands as in ldl_block; both back-substitution sums are fused multiply-adds here, as they compiled before)
-  if constexpr (B0 <= 16) {
-    ldl_fwd_row<0, JLDL_NSH, B0, 1>(h, b, dinv, below, row);
-    float g[B0 - JLDL_NSH], bd = b, dinvd = dinv;
-#pragma unroll
-    for (int j = JLDL_NSH; j < B0; j++) g[j - JLDL_NSH] = h[j] + (lane == j ? hd : 0.f);
-    ldl_dual_fwd_row<JLDL_NSH, B0>(h, g, b, bd, dinv, dinvd, below, row);
-    float z = b * dinv, zd = bd * dinvd, acc = 0.f, accd = 0.f, x = 0.f, xd = 0.f;
-    ldl_dual_back_row<B0 - 1, B0>(h, g, z, zd, dinv, dinvd, acc, accd, x, xd, row, lane);
-    *xd_out = row >= 0 ? xd : 0.f;
-    return row >= 0 ? x : 0.f;
-  }
-#endif
-#pragma unroll
-  for (int k = 0; k < JLDL_NSH; k++) {
-    float dk = wave_bcast(h[k], k);
-    float inv = 1.f / dk;
-    dinv = below ? inv : dinv;
-    below = row > k;
-    float lik = below ? h[k] * inv : 0.f;
-    float pk[JNV];
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) pk[j] = wave_bcast(h[j], k);
-    const float bk = wave_bcast(b, k);
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) h[j] -= lik * pk[j];
-    b -= lik * bk;
-  }
-  // trailing block, twice: plain (h, b, dinv) and damped (g, bd, dinvd)
-  float g[JB0 - JLDL_NSH], bd = b, dinvd = dinv;
-#pragma unroll
-  for (int j = JLDL_NSH; j < JB0; j++) g[j - JLDL_NSH] = h[j] + (lane == j ? hd : 0.f);
-#pragma unroll
-  for (int k = JLDL_NSH; k < JB0; k++) {
-    float dk = wave_bcast(h[k], k), dkd = wave_bcast(g[k - JLDL_NSH], k);
-    float inv = 1.f / dk, invd = 1.f / dkd;
-    dinv = below ? inv : dinv;
-    dinvd = below ? invd : dinvd;
-    below = row > k;
-    float lik = below ? h[k] * inv : 0.f, likd = below ? g[k - JLDL_NSH] * invd : 0.f;
-    float pk[JNV], pg[JNV];
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) { pk[j] = wave_bcast(h[j], k); pg[j] = wave_bcast(g[j - JLDL_NSH], k); }
-    const float bk = wave_bcast(b, k), bdk = wave_bcast(bd, k);
-#pragma unroll
-    for (int j = k + 1; j < JB0; j++) { h[j] -= lik * pk[j]; g[j - JLDL_NSH] -= likd * pg[j]; }
-    b -= lik * bk;
-    bd -= likd * bdk;
-  }
-  // back-substitution: h[k > lane] = d_lane * L[k][lane] (shared for k < NSH columns... rows < NSH use h for both systems)
-  float z = b * dinv, zd = bd * dinvd, acc = 0.f, accd = 0.f, x = 0.f, xd = 0.f;
-#pragma unroll
-  for (int k = JB0 - 1; k >= 0; k--) {
-    x = row > k ? x : z - dinv * acc;
-    xd = row > k ? xd : zd - dinvd * accd;
-    float xk = wave_bcast(x, k), xdk = wave_bcast(xd, k);
-    // multiplier of row k in column `lane`: the damped system's differs only inside the trailing block.  It is a select already and
-    // keeps its lane mask: with both sums unmasked the rollout kernels of the 30-dof layout need 144 registers instead of 126
-    // (tests/test_rollout_cost_budget.py holds them to 128), with either one masked they need what they did
-    float multd = (lane < k) ? ((k >= JLDL_NSH && lane >= JLDL_NSH) ? g[k - JLDL_NSH] : h[k]) : 0.f;
-    acc += h[k] * xk;
-    accd += multd * xdk;
-  }
-  *xd_out = row >= 0 ? xd : 0.f;
-  return row >= 0 ? x : 0.f;
-}
-#endif
-JDEV float ldl_solve_blocks(float (&h)[JNV], float b, int lane, int mask) {
-  float x = 0.f;
-  if (mask & 1) x += ldl_block<0, JB0>(h, b, lane);
-  if (mask & 2) x += ldl_block<JB0, JB1>(h, b, lane);
-  if (mask & 4) x += ldl_block<JB1, JNV>(h, b, lane);
-  return x;
-}
+// ---------------------------------------------------------------- dense solver blocks: LDL^T one row per lane, 6x6 Gauss-Jordan
+#include "solver_blocks.h"
 // inclusive prefix sum over lanes (6 ds_bpermute steps)
 JDEV int wave_scan_incl(int v, int lane) {
 #pragma unroll
@@ -894,10 +530,6 @@ JDEV int wave_scan_incl(int v, int lane) {
     v += lane >= o ? t : 0;
   }
   return v;
-}
-JDEV void load_rows(float (&h)[JNV], const float* M, int nv, int lane) {
-#pragma unroll
-  for (int j = 0; j < JNV; j++) h[j] = lane < nv ? M[lane * JNV + j] : (lane == j ? 1.f : 0.f);
 }
 
 // ---------------------------------------------------------------- stage K: kinematic tree

@@ -1,7 +1,7 @@
-"""GPU tier: the dense solver blocks' lean forms (physics_kernel.h JACO_SOLVER_MASKS: one lane predicate per pivot, the back-substitution
+"""GPU tier: the dense solver blocks' lean forms (solver_blocks.h: one lane predicate per pivot, the back-substitution
 sum without a lane mask) on the device.
 
-If the build with the earlier forms (tools/build_variant.sh solvermasks -DJACO_SOLVER_MASKS=1) lies next to the product library: 256 envs
+If the build with the earlier forms (solver_blocks_masks.h; tools/build_variant.sh solvermasks -DJACO_SOLVER_MASKS=1) lies next to the product library: 256 envs
 x 4 env steps x frame_skip 2 of the picking reset distribution (the case of tests/test_gpu_newton_regime.py: one env in eight gets
 small actions -- side rows, bigger tiers -- and seed 41 holds a hand-in-pedestal reset) on both libraries, each in a fresh child process
 with its own time limit, must agree bit for bit on qpos, qvel, qacc, obs, reward and done after every env step.

@@ -1,5 +1,5 @@
 """GPU tier: the dense solver blocks and the controller's 6x6 eliminations with the pivot row as a DPP operand of the multiply-adds
-(wave_ops.h JACO_SOLVER_DPP: ldl_block, ldl_block0_dual, gj_inverse6, gj_solve6) against the read-lane forms, on the device.
+(solver_blocks.h JACO_SOLVER_DPP: ldl_block, ldl_block0_dual, gj_inverse6, gj_solve6) against the read-lane forms, on the device.
 
 If the build with the read-lane forms (tools/build_variant.sh solverbcast, -DJACO_SOLVER_DPP=0) lies next to the product library, both
 libraries run, each in a fresh child process with its own time limit, and must agree bit for bit:

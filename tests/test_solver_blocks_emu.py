@@ -1,6 +1,9 @@
-"""CPU tier: the dense solver blocks (physics_kernel.h ldl_solve / ldl_block / ldl_block0_dual, env_logic.h gj_inverse6 / gj_solve6), each
-called on one wave of the emulator, in both forms of the sources: the default one (one lane predicate per pivot, the back-substitution
-sum without a lane mask) and -DJACO_SOLVER_MASKS=1 (one compare per role, the masked sum: what the kernel did before).
+"""CPU tier: the dense solver blocks (solver_blocks.h: ldl_solve / ldl_block / ldl_block0_dual, gj_inverse6 / gj_solve6), each called
+on one wave of the emulator, in both forms of the sources: the default one (one lane predicate per pivot, the back-substitution sum
+without a lane mask) and -DJACO_SOLVER_MASKS=1 (solver_blocks_masks.h: one compare per role, the masked sum: what the kernel did
+before).  Every case runs in the three layouts (default, 12-hinge, 30-dof: the last two run the read-lane forms of ldl_block and
+ldl_block0_dual with blocks that cross a 16-lane row); a routine whose block is empty in a layout (the 12-hinge one has no third
+block) is skipped there.
 
 Every case: what each of the 64 lanes holds afterwards -- x, the dual's damped x, the matrix rows -- is equal bit for bit between the
 two forms; x is 0 outside the block; the rows of the lanes outside the block are the ones handed in.  On the well-conditioned cases
@@ -19,23 +22,44 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu_solver")
-FORMS = ("libjaco_emu_solver.so", "libjaco_emu_solver_masks.so")
+FORMS = ("libjaco_emu_solver%s.so", "libjaco_emu_solver_masks%s.so")
+LAYOUTS = ("", "_d12", "_d30")
 F32P = ctypes.POINTER(ctypes.c_float)
-_libs = []
+_libs = {}
+_layout = [""]
+
+
+def per_layout(name, values):
+    """Every value in every layout; the default layout's cases keep the ids they had."""
+    return pytest.mark.parametrize("layout," + name, [pytest.param(l, v, id=(l[1:] + "-" if l else "") + str(v)) for l in LAYOUTS for v in values])
 
 
 def libs():
-    if not _libs:
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR] + list(FORMS))
-        for k, name in enumerate(FORMS):
+    """The two forms' libraries of the layout the running test chose."""
+    layout = _layout[0]
+    if layout not in _libs:
+        names = [f % layout for f in FORMS]
+        subprocess.check_call(["make", "-s", "-C", EMU_DIR] + names)
+        pair = []
+        for k, name in enumerate(names):
             L = ctypes.CDLL(os.path.join(EMU_DIR, name))
             d = (ctypes.c_int * 5)()
             L.emu_solver_dims(d)
             assert d[4] == k, "%s holds the wrong form" % name
             L.dims = tuple(d[:4])
-            _libs.append(L)
-        assert _libs[0].dims == _libs[1].dims
-    return _libs
+            pair.append(L)
+        assert pair[0].dims == pair[1].dims
+        _libs[layout] = pair
+    return _libs[layout]
+
+
+def block(layout, which):
+    """Chooses the layout for this test; the routine's [lo, hi), or a skip where the layout gives it no dofs."""
+    _layout[0] = layout
+    lo, hi = ranges()[which]
+    if lo == hi:
+        pytest.skip("routine %d: the block [%d, %d) is empty in this layout" % (which, lo, hi))
+    return lo, hi
 
 
 def _p(a):
@@ -101,7 +125,8 @@ def check_block(which, H, b, hd, x, xd, Ho, reference=True):
     A64 = H[lo:hi, lo:hi].astype(np.float64)
     if which == 6:   # block diagonal by contract: the coupling entries are not read
         for a, c in ((0, b0), (b0, b1), (b1, nv)):
-            assert rel(x[a:c], np.linalg.solve(A64[a:c, a:c], b[a:c].astype(np.float64))) < 1e-5
+            if a < c:   # (a layout may leave a sub-block empty)
+                assert rel(x[a:c], np.linalg.solve(A64[a:c, a:c], b[a:c].astype(np.float64))) < 1e-5
     else:
         assert rel(x[lo:hi], np.linalg.solve(A64, b[lo:hi].astype(np.float64))) < 1e-5
     if which == 4:
@@ -117,9 +142,10 @@ def damping(rng):
     return hd
 
 
-@pytest.mark.parametrize("which", range(7))
-def test_random_spd_with_the_other_blocks_rows_in_the_registers(which):
+@per_layout("which", range(7))
+def test_random_spd_with_the_other_blocks_rows_in_the_registers(layout, which):
     """A dense SPD matrix over all dofs: a block routine solves its diagonal block and leaves the rest alone."""
+    block(layout, which)
     nv = libs()[0].dims[0]
     for seed in range(4):
         rng = np.random.default_rng([which, seed])
@@ -136,11 +162,11 @@ def test_random_spd_with_the_other_blocks_rows_in_the_registers(which):
         check_block(which, H, b, hd, x, xd, Ho)
 
 
-@pytest.mark.parametrize("which", range(7))
-def test_near_singular_pivot_same_bits(which):
+@per_layout("which", range(7))
+def test_near_singular_pivot_same_bits(layout, which):
     """The block's third pivot comes out 1e-7 of its neighbours: the two forms still agree in every bit, and nothing leaves the block."""
+    lo, hi = block(layout, which)
     nv = libs()[0].dims[0]
-    lo, hi = ranges()[which]
     rng = np.random.default_rng([which, 99])
     A = spd(rng, nv)
     k = lo + 2
@@ -153,12 +179,12 @@ def test_near_singular_pivot_same_bits(which):
     assert not x[out].any() and not xd[out].any() and Ho[out].tobytes() == H[out].tobytes()
 
 
-@pytest.mark.parametrize("which", range(7))
-def test_inf_in_lanes_outside_the_block(which):
+@per_layout("which", range(7))
+def test_inf_in_lanes_outside_the_block(layout, which):
     """inf where the routine must not look: in the block's columns of the rows outside it and in their right-hand sides (for the two
     ldl_solve forms, whose block is all dofs, that is the lanes above JNV).  The block's answer is the clean one."""
+    lo, hi = block(layout, which)
     nv = libs()[0].dims[0]
-    lo, hi = ranges()[which]
     rng = np.random.default_rng([which, 7])
     A = spd(rng, nv)
     if which == 6:
@@ -201,8 +227,9 @@ def gj_inputs(rng, junk):
     return A, B
 
 
-@pytest.mark.parametrize("junk", ["zero", "random", "inf"])
-def test_gj_inverse6_and_gj_solve6(junk):
+@per_layout("junk", ["zero", "random", "inf"])
+def test_gj_inverse6_and_gj_solve6(layout, junk):
+    _layout[0] = layout
     for seed in range(4):
         rng = np.random.default_rng([seed, 6])
         A, B = gj_inputs(rng, junk)
@@ -223,5 +250,7 @@ def test_gj_near_singular_pivot_same_bits():
     rng = np.random.default_rng(5)
     A, B = gj_inputs(rng, "random")
     A[2, :6] = A[0, :6]; A[:6, 2] = A[:6, 0]; A[2, 2] = A[0, 0] * (1 + 1e-7)
-    both_gj(0, A, B)
-    both_gj(1, A, B)
+    for layout in LAYOUTS:   # (no parameter: the test keeps its id)
+        _layout[0] = layout
+        both_gj(0, A, B)
+        both_gj(1, A, B)
