@@ -534,6 +534,57 @@ int jaco_rollout_cost(JacoHandle* h, const JacoRolloutCostOptions* opt_host, con
                       const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutPlan* plan_host, const JacoRolloutGoal* goal_host,
                       const JacoRolloutCostOut* out, void* stream);
 
+/* ---- rollouts under the operational-space controller: jaco_rollout with the motor words of the ctrl computed inside the kernel by
+ * jaco_osc's law towards a plan of frame targets -- "where is the hand after 50 substeps of driving towards this pose?", the rollout of
+ * a planner that samples end-effector targets, the env's own substep loop (OSC towards a target, then a substep) -- for n rollouts in
+ * ONE kernel launch (mujoco_jaco_amd/csrc/rollout_osc.h).  The state arguments (state_idx_dev, nstates, qpos0_dev, qvel0_dev), the
+ * substep, the outputs qpos / qvel / xpos / xmat, final_only and n == 0 are those of jaco_rollout, word for word; the frames, their
+ * active dofs, the gains and the law are those of jaco_osc.
+ * Plans (JacoRolloutOscPlan, a host record of device pointers): rollout i follows plan p = plan_idx[i] (int32 [n]; NULL = plan i, so
+ * n <= nplans); K target samples of one env share its state row through state_idx, and rollouts share plans through plan_idx:
+ *   ctrl        [nplans][nknots][nu]           the base ctrl rows, or NULL = zeros: gripper commands and the other arm's words;
+ *   target_pos  [nplans][nknots][nframes][3]   the target of frame f in knot k (required);
+ *   target_quat [nplans][nknots][nframes][4]   unit quaternions, w first, normalised again in the kernel (required).
+ * THE LAW, at an evaluation in knot k: the row ctrl[p][k] with, for every frame f, jaco_osc's u_d (same formula, same fp32 code, on
+ * frames_host[f], target_pos[p][k][f], target_quat[p][k][f] and the options' gains) written at the motor actuator of every active dof d;
+ * every other word goes through bit for bit.  It is evaluated INSIDE the substep, on that substep's own mass matrix, bias and body
+ * poses -- fresh, as jaco_osc's are on the state it is handed, not one substep stale as the reference's controller reads them -- so it
+ * costs no forward pass of its own.  per_substep = 1: before every substep's actuator stage (the env's own loop); per_substep = 0: in
+ * the first substep of a knot, held over the knot.  The actuator stage clamps u afterwards, as it clamps any ctrl.
+ * Outputs (JacoRolloutFbOut; at least one of the six pointers is required): qpos, qvel, xpos, xmat as jaco_rollout -- the pose of the
+ * ONE frame out_frame_host (NULL: no pose outputs), which may or may not be a controlled frame -- and
+ *   ctrl [n][E][nu], E = nknots (per_substep = 0) or nknots * hold: the commanded row of every evaluation (before the clamp), all E rows
+ *                 whether or not final_only is set;
+ *   status [n] uint32: JACO_FLAG_NAN / JACO_FLAG_SOLVER_MAXITER as jaco_rollout, JACO_ROLLOUT_OSC_SINGULAR0 / _SINGULAR1 when any
+ *                 evaluation of frame 0 / 1 took the pseudo-inverse branch (jaco_osc's status), or JACO_ROLLOUT_BAD_INDEX.
+ * A state_idx or plan_idx entry out of range: that rollout writes only its status word, with JACO_ROLLOUT_BAD_INDEX set.
+ * Not here: task axes and null-space terms (jaco_osc_task), an in-kernel cost, contacts -- the prediction is jaco_rollout's, the arm in
+ * free space with joint limits.
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch (none for n == 0, which returns JACO_OK), no
+ * allocation, no synchronisation, no host copy; the options and the frames travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for everything jaco_rollout refuses (a NULL plan->ctrl is NOT refused; the outputs being the
+ * six); a NULL plan; per_substep not 0 / 1; nplans < 1; n > nplans with a NULL plan_idx; the options' nframes != nframes; and for
+ * everything jaco_osc refuses of frames, gains and active sets, the arrays required being target_pos and target_quat. */
+#define JACO_ROLLOUT_OSC_SINGULAR0 0x200000u   /* status: frame 0 used the pseudo-inverse branch at some evaluation */
+#define JACO_ROLLOUT_OSC_SINGULAR1 0x400000u   /* ... frame 1 */
+typedef struct JacoRolloutOscOptions {
+  int32_t nknots, hold, final_only, per_substep;  /* as JacoRolloutFbOptions */
+  int32_t nframes;                                /* 1 .. JACO_OSC_MAX_FRAMES: the frames of a target row */
+  int32_t reserved;
+  float kp, ko, kv, vmax_xyz, vmax_abg;           /* as JacoOscOptions: 50, 180, 20, 0.4, 1.0472 */
+  uint64_t dof_mask;                              /* 0 = every hinge dof on the frame's chain */
+} JacoRolloutOscOptions;
+typedef struct JacoRolloutOscPlan {               /* device pointers */
+  const float* ctrl;         /* [nplans][nknots][nu]            or NULL: zeros */
+  const float* target_pos;   /* [nplans][nknots][nframes][3]    required */
+  const float* target_quat;  /* [nplans][nknots][nframes][4]    required */
+  const int32_t* plan_idx;   /* [n] or NULL: plan i, so n <= nplans */
+  int32_t nplans;
+} JacoRolloutOscPlan;
+int jaco_rollout_osc(JacoHandle* h, const JacoRolloutOscOptions* opt_host, const JacoFrame* frames_host, int nframes, const JacoFrame* out_frame_host, int n,
+                     const int32_t* state_idx_dev, int nstates, const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutOscPlan* plan_host,
+                     const JacoRolloutFbOut* out, void* stream);
+
 /* ---- the iLQR / TVLQR backward pass, batched: the feed-forward k_t and the gains K_t that jaco_rollout_fb consumes, from the linearisation
  * (jaco_fd) and the cost expansion along a trajectory, the whole T-knot recursion of every problem in ONE launch.
  * Solve i works on problem p = prob_idx[i] and runs t = T-1 .. 0.  Deviations follow dx_{t+1} = A_t dx_t + B_t du_t; the knot cost is

@@ -196,6 +196,29 @@ class JacoRolloutCostOut(ctypes.Structure):
                 ("ctrl", ctypes.c_void_p), ("cost", ctypes.c_void_p), ("terms", ctypes.c_void_p)]
 
 
+JACO_ROLLOUT_OSC_SINGULAR0, JACO_ROLLOUT_OSC_SINGULAR1 = 0x200000, 0x400000   # jaco_rollout_osc's status: frame 0 / 1 took the pseudo-inverse branch at some evaluation
+
+
+class JacoRolloutOscOptions(ctypes.Structure):
+    """JacoRolloutOscOptions of include/jaco_env.h; a fresh instance holds hold = 1, final_only = 0, per_substep = 1, one frame and
+    JacoOscOptions' gains."""
+    _fields_ = [("nknots", ctypes.c_int32), ("hold", ctypes.c_int32), ("final_only", ctypes.c_int32), ("per_substep", ctypes.c_int32),
+                ("nframes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("kp", ctypes.c_float), ("ko", ctypes.c_float), ("kv", ctypes.c_float),
+                ("vmax_xyz", ctypes.c_float), ("vmax_abg", ctypes.c_float), ("dof_mask", ctypes.c_uint64)]
+    DEFAULTS = dict(nknots=0, hold=1, final_only=0, per_substep=1, nframes=1, **JacoOscOptions.DEFAULTS)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown OSC rollout option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        super().__init__(**{**self.DEFAULTS, **options})
+
+
+class JacoRolloutOscPlan(ctypes.Structure):
+    _fields_ = [("ctrl", ctypes.c_void_p), ("target_pos", ctypes.c_void_p), ("target_quat", ctypes.c_void_p), ("plan_idx", ctypes.c_void_p),
+                ("nplans", ctypes.c_int32)]
+
+
 JACO_LQR_MAX_NX, JACO_LQR_MAX_NU = 36, 18
 JACO_LQR_BAD_INDEX = 0x80000   # jaco_lqr: the solve's problem index was outside [0, nprob); only its status word was written
 JACO_LQR_NOT_PD = 0x100000     # jaco_lqr: Quu + mu I not positive definite, or a non-finite number, at knot (status & 0xffff)
@@ -318,6 +341,7 @@ SYMBOLS = {
     "jaco_rollout_fb": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_lqr": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
     "jaco_rollout_cost": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_rollout_osc": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h and rollout_cost.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h, rollout_cost.h and rollout_osc.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -90,3 +90,18 @@ static_assert(offsetof(JacoRolloutCostOut, qpos) == offsetof(JacoRolloutFbOut, q
                   offsetof(JacoRolloutCostOut, ctrl) == offsetof(JacoRolloutFbOut, ctrl) && offsetof(JacoRolloutCostOut, cost) == sizeof(JacoRolloutFbOut) &&
                   offsetof(JacoRolloutCostOut, terms) == sizeof(JacoRolloutFbOut) + sizeof(float*) && offsetof(JacoRolloutCostArgs, F) == 0,
               "JacoRolloutCostOut extends JacoRolloutFbOut; the costed kernel's block starts with the closed-loop kernel's");
+static_assert(sizeof(JacoRolloutOscOptions) == sizeof(JacoRolloutOscOpts) && offsetof(JacoRolloutOscOptions, nknots) == offsetof(JacoRolloutOscOpts, nknots) &&
+                  offsetof(JacoRolloutOscOptions, hold) == offsetof(JacoRolloutOscOpts, hold) && offsetof(JacoRolloutOscOptions, final_only) == offsetof(JacoRolloutOscOpts, final_only) &&
+                  offsetof(JacoRolloutOscOptions, per_substep) == offsetof(JacoRolloutOscOpts, per_substep) && offsetof(JacoRolloutOscOptions, nframes) == offsetof(JacoRolloutOscOpts, nframes) &&
+                  offsetof(JacoRolloutOscOptions, kp) == offsetof(JacoRolloutOscOpts, kp) && offsetof(JacoRolloutOscOptions, ko) == offsetof(JacoRolloutOscOpts, ko) &&
+                  offsetof(JacoRolloutOscOptions, kv) == offsetof(JacoRolloutOscOpts, kv) && offsetof(JacoRolloutOscOptions, vmax_xyz) == offsetof(JacoRolloutOscOpts, vmax_xyz) &&
+                  offsetof(JacoRolloutOscOptions, vmax_abg) == offsetof(JacoRolloutOscOpts, vmax_abg) && offsetof(JacoRolloutOscOptions, dof_mask) == offsetof(JacoRolloutOscOpts, dof_mask),
+              "JacoRolloutOscOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoRolloutOscPlan) == sizeof(JacoRolloutOscTargets) && offsetof(JacoRolloutOscPlan, ctrl) == offsetof(JacoRolloutOscTargets, ctrl) &&
+                  offsetof(JacoRolloutOscPlan, target_pos) == offsetof(JacoRolloutOscTargets, target_pos) &&
+                  offsetof(JacoRolloutOscPlan, target_quat) == offsetof(JacoRolloutOscTargets, target_quat) &&
+                  offsetof(JacoRolloutOscPlan, plan_idx) == offsetof(JacoRolloutOscTargets, plan_idx) && offsetof(JacoRolloutOscPlan, nplans) == offsetof(JacoRolloutOscTargets, nplans),
+              "JacoRolloutOscPlan of the public header and the kernel's plan record must agree");
+static_assert(JACO_ROLLOUT_OSC_SINGULAR0 == JROLLOUT_OSC_SINGULAR0 && JACO_ROLLOUT_OSC_SINGULAR1 == (JROLLOUT_OSC_SINGULAR0 << 1) && JACO_OSC_MAX_FRAMES == 2 &&
+                  (JACO_ROLLOUT_OSC_SINGULAR0 & (JACO_ROLLOUT_BAD_INDEX | JACO_FLAG_NAN | JACO_FLAG_SOLVER_MAXITER)) == 0 && offsetof(JacoRolloutOscArgs, R) == 0,
+              "the singular bits of the public header and rollout_osc.h must agree and lie clear of the rollout's other status bits");

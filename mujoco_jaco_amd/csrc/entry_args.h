@@ -1,5 +1,5 @@
-// From the C ABI's arguments to the kernel's argument block, for the ten query-style entries (jaco_query, jaco_ik, jaco_osc,
-// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost).  Host only: included by the library's host unit (jaco_env.hip)
+// From the C ABI's arguments to the kernel's argument block, for the eleven query-style entries (jaco_query, jaco_ik, jaco_osc,
+// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost, jaco_rollout_osc).  Host only: included by the library's host unit (jaco_env.hip)
 // and by the CPU tests' host build (tests/emu/emu_driver.cpp), after include/jaco_env.h, physics_kernel.h and abi_agreement.h -- the
 // public records are copied into the kernel-side records that restate them, which the feature headers (query.h ... rollout_fb.h)
 // cannot do: they do not see the public header.  kernels.hip does not include this file.
@@ -123,7 +123,7 @@ static inline std::string jaco_fd_bind(const JacoModelDev& m, const JacoFdOption
   return why;
 }
 
-// (the three rollouts: an accepted call with n = 0 launches nothing, which is the entry's to see to)
+// (the four rollouts: an accepted call with n = 0 launches nothing, which is the entry's to see to)
 static inline std::string jaco_rollout_bind(const JacoModelDev& m, const JacoRolloutOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx, int nstates,
                                             const float* qpos0, const float* qvel0, const float* ctrl, const JacoRolloutOut* out, int num_envs,
                                             const float* state_qpos, const float* state_qvel, JacoRolloutArgs* Q) {
@@ -166,6 +166,20 @@ static inline std::string jaco_rollout_cost_bind(const JacoModelDev& m, const Ja
                                                     out != nullptr, Q);
   if (!why.empty()) return "jaco_rollout_cost: " + why;
   if (!R.qpos0) { R.qpos0 = state_qpos; R.qvel0 = state_qvel; }
+  return why;
+}
+
+static inline std::string jaco_rollout_osc_bind(const JacoModelDev& m, const JacoRolloutOscOptions* opt, const JacoFrame* frames, int nframes, const JacoFrame* out_frame,
+                                                int n, const int32_t* state_idx, int nstates, const float* qpos0, const float* qvel0, const JacoRolloutOscPlan* plan,
+                                                const JacoRolloutFbOut* out, int num_envs, const float* state_qpos, const float* state_qvel, JacoRolloutOscArgs* Q) {
+  *Q = JacoRolloutOscArgs{};
+  Q->R.state_idx = state_idx; Q->R.qpos0 = qpos0; Q->R.qvel0 = qvel0;
+  if (out) { Q->R.qpos = out->qpos; Q->R.qvel = out->qvel; Q->R.xpos = out->xpos; Q->R.xmat = out->xmat; Q->R.status = out->status; Q->O.ctrl_out = out->ctrl; }
+  const std::string why = jaco_rollout_osc_resolve(m, reinterpret_cast<const JacoRolloutOscOpts*>(opt), reinterpret_cast<const JacoQueryFrame*>(frames), nframes,
+                                                   reinterpret_cast<const JacoQueryFrame*>(out_frame), n, nstates, num_envs,
+                                                   reinterpret_cast<const JacoRolloutOscTargets*>(plan), out != nullptr, Q);
+  if (!why.empty()) return "jaco_rollout_osc: " + why;
+  if (!Q->R.qpos0) { Q->R.qpos0 = state_qpos; Q->R.qvel0 = state_qvel; }
   return why;
 }
 #endif   // JACO_ENTRY_ARGS_LQR_ONLY

@@ -1055,6 +1055,19 @@ extern "C" int jaco_rollout_cost(JacoHandle* h, const JacoRolloutCostOptions* op
   return launch_entry(h, jaco_launch_rollout_cost, n, stream, Q);
 }
 
+// rollouts under the operational-space controller (rollout_osc.h): jaco_rollout with jaco_osc's law evaluated inside the substep
+extern "C" int jaco_rollout_osc(JacoHandle* h, const JacoRolloutOscOptions* opt_host, const JacoFrame* frames_host, int nframes, const JacoFrame* out_frame_host, int n,
+                                const int32_t* state_idx_dev, int nstates, const float* qpos0_dev, const float* qvel0_dev, const JacoRolloutOscPlan* plan_host,
+                                const JacoRolloutFbOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoRolloutOscArgs Q;
+  if (refused(h, jaco_rollout_osc_bind(h->model_host, opt_host, frames_host, nframes, out_frame_host, n, state_idx_dev, nstates, qpos0_dev, qvel0_dev, plan_host, out,
+                                       h->num_envs, h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
+  if (n == 0) return JACO_OK;
+  Q.R.model = h->model_dev;
+  return launch_entry(h, jaco_launch_rollout_osc, n, stream, Q);
+}
+
 // the iLQR / TVLQR backward pass (lqr.h): the whole recursion of every problem in one launch; the model is not read
 extern "C" int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream) {
   if (!h) return JACO_EINVAL;

@@ -43,13 +43,15 @@ struct JacoOscArgs {
   JacoOscOpts opt;
 };
 
-// The host half shared by jaco_osc (jaco_env.hip) and the emulator's entry: every argument check; then the frame table, the options,
-// the saturation levels and each frame's active dof set (hinge dofs on the chain of its body, intersected with dof_mask when that is
-// non-zero) into the argument block, whose pointers the caller has filled in.  Returns an empty string, or what is wrong.
-static inline std::string jaco_osc_resolve(const JacoModelDev& m, const JacoQueryFrame* frames, int nframes, const JacoOscOpts& o, JacoOscArgs* Q) {
+// The controller's part of a host half, shared by jaco_osc_resolve below and jaco_rollout_osc_resolve (rollout_osc.h), with the entry's
+// own rule for which arrays must be there (have_arrays, and the message when they are not): the checks of frames, gains, active sets and
+// saturation levels; then the frame table, the options, the saturation levels and each frame's active dof set (hinge dofs on the chain of
+// its body, intersected with dof_mask when that is non-zero) into the block.  Returns an empty string, or what is wrong.
+static inline std::string jaco_osc_resolve_law(const JacoModelDev& m, const JacoQueryFrame* frames, int nframes, const JacoOscOpts& o, bool have_arrays,
+                                               const char* no_arrays, JacoOscArgs* Q) {
   if (nframes < 1 || nframes > JOSC_MAXFRAMES || !frames)
     return "nframes " + std::to_string(nframes) + " outside [1, " + std::to_string(JOSC_MAXFRAMES) + "]";
-  if (!Q->target_pos || !Q->target_quat || !Q->ctrl_out) return "the target positions, the target quaternions and the output ctrl are required";
+  if (!have_arrays) return no_arrays;
   if (!(o.kp > 0.f) || !(o.ko > 0.f) || !(o.kv > 0.f) || !(o.vmax_xyz > 0.f) || !(o.vmax_abg > 0.f)) return "kp, ko, kv, vmax_xyz and vmax_abg must be positive";
   unsigned hinge = 0u, motor = 0u, seen = 0u;
   for (int d = 0; d < m.nv; d++) if (m.d_qadr[d] >= 0) hinge |= 1u << d;
@@ -72,6 +74,13 @@ static inline std::string jaco_osc_resolve(const JacoModelDev& m, const JacoQuer
   Q->sat_xyz = o.vmax_xyz / o.kp * o.kv;
   Q->sat_abg = o.vmax_abg / o.ko * o.kv;
   return std::string();
+}
+
+// The host half shared by jaco_osc (jaco_env.hip) and the emulator's entry: every argument check, then what jaco_osc_resolve_law puts
+// into the argument block, whose pointers the caller has filled in.  Returns an empty string, or what is wrong.
+static inline std::string jaco_osc_resolve(const JacoModelDev& m, const JacoQueryFrame* frames, int nframes, const JacoOscOpts& o, JacoOscArgs* Q) {
+  return jaco_osc_resolve_law(m, frames, nframes, o, Q->target_pos && Q->target_quat && Q->ctrl_out,
+                              "the target positions, the target quaternions and the output ctrl are required", Q);
 }
 
 struct OscGains { float kp, ko, kv, sat_xyz, sat_abg; };

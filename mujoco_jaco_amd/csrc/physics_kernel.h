@@ -2825,3 +2825,4 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #include "rollout_fb.h"     // 16  jaco_rollout_fb: closed-loop rollouts
 #include "lqr.h"            // 17  jaco_lqr: the iLQR / TVLQR backward pass
 #include "rollout_cost.h"   // 18  jaco_rollout_cost: rollouts costed inside the kernel
+#include "rollout_osc.h"    // 19  jaco_rollout_osc: rollouts under the operational-space controller

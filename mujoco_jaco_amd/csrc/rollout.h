@@ -78,11 +78,32 @@ static inline std::string jaco_rollout_resolve(const JacoModelDev& m, const Jaco
 
 // A substep after its first half (entry_walk: the tree walk and the zeroing of s.M), from the subtree sums to the position update:
 // run_env's contact-free substep body, stage by stage.
+// law: what runs between entry_mass_bias and stage_actuation -- s.M, s.bias, s.cdof and the body poses are this substep's own there and the
+// row area s.J is free (stage_mass_bias is done with it, stage_limit_rows writes it only afterwards) -- and leaves the ctrl in s.ctrl.
+// rollout_no_law: nothing (the ctrl was put there before the walk).  With a law the actuator and per-dof constants are fetched after it,
+// not held in registers across it.
+struct JacoRolloutOscArgs;
 template <class L>
-JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags) {
+JDEV void rollout_osc_law(const JacoRolloutOscArgs* Q, const JacoModelDev* m, L& s, int p, int k, size_t erow, int lane, unsigned& flags);
+struct rollout_no_law { static constexpr bool present = false; };
+struct rollout_osc_hook {   // rollout_osc_law (rollout_osc.h) on plan p at knot k into row erow of the ctrl output, when `on`
+  static constexpr bool present = true;
+  const JacoRolloutOscArgs* Q; int p, k; size_t erow; bool on;
+};
+template <class L, class Law = rollout_no_law>
+JDEV void rollout_substep(const JacoModelDev* m, L& s, int lane, unsigned& flags, const Law law = Law()) {   // (by value: by reference the costed kernel's schedule moves)
   const int nv = m->nv;
-  const ActParams actp = act_fetch(m, lane);
-  const StagePrefetch pf = entry_mass_bias(m, s, lane);
+  ActParams actp;
+  StagePrefetch pf;
+  if constexpr (!Law::present) {
+    actp = act_fetch(m, lane);
+    pf = entry_mass_bias(m, s, lane);
+  } else {
+    entry_mass_bias(m, s, lane);
+    if (law.on) rollout_osc_law(law.Q, m, s, law.p, law.k, law.erow, lane, flags);
+    actp = act_fetch(m, lane);
+    pf = stage_prefetch(m, lane);
+  }
   stage_actuation(m, s, lane, actp);
   stage_limit_rows(m, s, lane, pf);
   wave_sync();
@@ -141,7 +162,8 @@ JDEV v3 rollout_pose(const JacoRolloutArgs& Q, const L& s, size_t row, int lane,
 
 // The closed-loop kernel's block and law (rollout_fb.h) and the costed kernel's block and terms (rollout_cost.h), which the one loop
 // below serves too.  rollout_kind<A>: what block A adds to the open loop -- closed: the ctrl of a knot comes from rollout_fb_law and the
-// rollout follows a plan; costed: closed, plus the noise and the running cost.
+// rollout follows a plan; costed: closed, plus the noise and the running cost.  The operational-space block and law (rollout_osc.h) too --
+// osc: the rollout follows a plan of targets and the motor words of the ctrl come from rollout_osc_law, evaluated INSIDE the substep.
 struct JacoRolloutFbArgs;
 struct JacoRolloutCostArgs;
 template <class L>
@@ -155,25 +177,29 @@ JDEV void rollout_cost_finish(const JacoRolloutCostArgs* Q, int i, int lane, flo
 template <class A> struct rollout_kind {
   static constexpr bool costed = std::is_same<A, JacoRolloutCostArgs>::value;
   static constexpr bool closed = costed || std::is_same<A, JacoRolloutFbArgs>::value;
+  static constexpr bool osc = std::is_same<A, JacoRolloutOscArgs>::value;
 };
 // the JacoRolloutFbArgs of a closed block: the block itself, or the costed block's F
 template <class A>
 JDEV const JacoRolloutFbArgs* rollout_law_block(const A* Q) {
   if constexpr (rollout_kind<A>::costed) return &Q->F; else return Q;
 }
-// the JacoRolloutArgs of any block: the block itself, or the closed-loop block's R
+// the JacoRolloutArgs of any block: the block itself, or the closed-loop / operational-space block's R
 template <class A>
 JDEV const JacoRolloutArgs* rollout_block(const A* Q) {
-  if constexpr (rollout_kind<A>::closed) return &rollout_law_block(Q)->R; else return Q;
+  if constexpr (rollout_kind<A>::closed) return &rollout_law_block(Q)->R;
+  else if constexpr (rollout_kind<A>::osc) return &Q->R;
+  else return Q;
 }
 
-// The knot x hold loop of rollout i, for jaco_rollout (A = JacoRolloutArgs), jaco_rollout_fb (A = JacoRolloutFbArgs) and
-// jaco_rollout_cost (A = JacoRolloutCostArgs).  They differ in where a knot's ctrl comes from -- its row of the ctrl sequences, loaded once
-// per knot, or rollout_fb_law evaluated on the state in LDS, per knot or per substep -- in the closed-loop kernels' plan index, and in
+// The knot x hold loop of rollout i, for jaco_rollout (A = JacoRolloutArgs), jaco_rollout_fb (A = JacoRolloutFbArgs),
+// jaco_rollout_cost (A = JacoRolloutCostArgs) and jaco_rollout_osc (A = JacoRolloutOscArgs).  They differ in where a knot's ctrl comes from
+// -- its row of the ctrl sequences, loaded once per knot, rollout_fb_law evaluated on the state in LDS, per knot or per substep, or
+// rollout_osc_law evaluated inside the substep on its mass matrix, bias and poses -- in the plan index of all but the first, and in
 // the costed kernel's terms (rollout_cost.h says where they are formed and why there).
 template <class A, class L>
 JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
-  constexpr bool closed = rollout_kind<A>::closed, costed = rollout_kind<A>::costed;
+  constexpr bool closed = rollout_kind<A>::closed, costed = rollout_kind<A>::costed, osc = rollout_kind<A>::osc;
   const A* Qp = kernarg_view(Q_);
   const JacoRolloutArgs* R = rollout_block(Qp);
   const JacoModelDev* m = opaque_ptr(R->model);
@@ -186,6 +212,10 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
     p = wave_uniform_i(F->plan.plan_idx ? F->plan.plan_idx[i] : i);
     bad = bad || p < 0 || p >= F->plan.nplans;
   }
+  if constexpr (osc) {
+    p = wave_uniform_i(Qp->plan_idx ? Qp->plan_idx[i] : i);
+    bad = bad || p < 0 || p >= Qp->nplans;
+  }
   if (bad) {   // (as jaco_load_envs: neither a fault nor silence)
     if (lane == 0 && R->status) R->status[i] = JROLLOUT_BAD_INDEX;
     return;
@@ -196,11 +226,11 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
   const int nknots = R->nknots, hold = R->hold;
   const bool every = R->final_only == 0, pose = R->xpos != nullptr || R->xmat != nullptr;
   bool each = false;
-  if constexpr (closed && !costed) each = Qp->per_substep != 0;
+  if constexpr ((closed && !costed) || osc) each = Qp->per_substep != 0;
   float acc = 0.f;   // (the costed kernel's one accumulator per lane)
 #pragma nounroll
   for (int k = 0; k < nknots; k++) {
-    if constexpr (!closed) {
+    if constexpr (!closed && !osc) {
       if (lane < nu) s.ctrl[lane] = R->ctrl[((size_t)i * nknots + k) * nu + lane];
       wave_sync();
     }
@@ -226,7 +256,10 @@ JDEV void run_rollout(const A& Q_, L& s, int i, int lane) {
         const v3 pos = rollout_pose(*R, s, (size_t)i * nknots + (k - 1), lane, pose && every);
         if constexpr (costed) rollout_cost_pose(Qp, p, k - 1, lane, pos, acc);
       }
-      rollout_substep(m, s, lane, flags);
+      if constexpr (osc) {
+        const rollout_osc_hook law{Qp, p, k, each ? ((size_t)i * nknots + k) * hold + sub : (size_t)i * nknots + k, each || sub == 0};
+        rollout_substep(m, s, lane, flags, law);
+      } else rollout_substep(m, s, lane, flags);
     }
     if (every || k == nknots - 1) {
       const size_t row = every ? (size_t)i * nknots + k : (size_t)i;

@@ -67,17 +67,30 @@ class Contacts:
         return (fw * sgn[..., None]).sum(1)
 
 
-def _closed_loop_args(sim, what, ctrl, qpos, qvel, gain, x_ref, dofs, feedforward, alpha, plan_index, state_index, noise=None):
-    """The arguments BatchedMujoco.rollout_feedback and rollout_cost share (a function of the module, so that a stand-in sim which borrows
-    the two methods needs nothing but the launch methods), checked and made contiguous device tensors: {"plan": {"ctrl", "kff",
-    "gain", "xref"}, "alpha", "plan_index", "state_index", "qpos", "qvel", "nstates", "n", "T", "dofs", "noise"}.  n is the length
-    of whichever of plan_index, state_index, alpha and noise is given (all the same), else the number of plans."""
+def _closed_loop_args(sim, what, ctrl, qpos, qvel, gain, x_ref, dofs, feedforward, alpha, plan_index, state_index, noise=None, targets=None):
+    """The arguments BatchedMujoco.rollout_feedback, rollout_cost and rollout_osc share (a function of the module, so that a stand-in sim
+    which borrows the methods needs nothing but the launch methods), checked and made contiguous device tensors: {"plan": {"ctrl", "kff",
+    "gain", "xref", "target_pos", "target_quat"}, "alpha", "plan_index", "state_index", "qpos", "qvel", "nstates", "n", "T", "dofs",
+    "noise"}.  n is the length of whichever of plan_index, state_index, alpha and noise is given (all the same), else the number of
+    plans.  targets = (target_pos [P, T, F, 3], target_quat [P, T, F, 4], F) (rollout_osc): the plans are the targets', and ctrl
+    [P, T, nu] may be None."""
     dev = sim.device
     f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
     ctrl, gain, x_ref, kff, alpha, noise = f32(ctrl), f32(gain), f32(x_ref), f32(feedforward), f32(alpha), f32(noise)
-    if ctrl.dim() != 3 or ctrl.shape[2] != sim.nu:
-        raise ValueError("%s: ctrl has shape %s, not [P, T, %d]" % (what, tuple(ctrl.shape), sim.nu))
-    P, T = int(ctrl.shape[0]), int(ctrl.shape[1])
+    tp = tq = None
+    if targets is not None:
+        tp, tq, F = f32(targets[0]), f32(targets[1]), int(targets[2])
+        if tp.dim() != 4 or tuple(tp.shape[2:]) != (F, 3):
+            raise ValueError("%s: target_pos has shape %s, not [P, T, %d, 3]" % (what, tuple(tp.shape), F))
+        P, T = int(tp.shape[0]), int(tp.shape[1])
+        if tuple(tq.shape) != (P, T, F, 4):
+            raise ValueError("%s: target_quat has shape %s, not [%d, %d, %d, 4]" % (what, tuple(tq.shape), P, T, F))
+        if ctrl is not None and tuple(ctrl.shape) != (P, T, sim.nu):
+            raise ValueError("%s: ctrl has shape %s, not [%d, %d, %d]" % (what, tuple(ctrl.shape), P, T, sim.nu))
+    else:
+        if ctrl.dim() != 3 or ctrl.shape[2] != sim.nu:
+            raise ValueError("%s: ctrl has shape %s, not [P, T, %d]" % (what, tuple(ctrl.shape), sim.nu))
+        P, T = int(ctrl.shape[0]), int(ctrl.shape[1])
     if kff is not None and kff.shape != ctrl.shape:
         raise ValueError("%s: feedforward has shape %s, not ctrl's %s" % (what, tuple(kff.shape), tuple(ctrl.shape)))
     dofs = [] if dofs is None else [int(d) for d in dofs]
@@ -106,7 +119,7 @@ def _closed_loop_args(sim, what, ctrl, qpos, qvel, gain, x_ref, dofs, feedforwar
         raise ValueError("%s: %s" % (what, " but ".join("%d entries of %s" % (c, k) for k, c in counts.items())))
     n = next(iter(counts.values())) if counts else P
     c = lambda t: None if t is None else t.contiguous()
-    plan = {"ctrl": ctrl.contiguous(), "kff": c(kff), "gain": c(gain), "xref": c(x_ref) if gain is not None else None}
+    plan = {"ctrl": c(ctrl), "kff": c(kff), "gain": c(gain), "xref": c(x_ref) if gain is not None else None, "target_pos": c(tp), "target_quat": c(tq)}
     return dict(plan=plan, alpha=alpha, plan_index=pidx, state_index=sidx, qpos=q, qvel=v, nstates=nstates, n=n, T=T, dofs=dofs, noise=c(noise))
 
 
@@ -542,6 +555,50 @@ class BatchedMujoco:
                        wx=weights(wx, nx, "wx"), wxT=weights(wx_final, nx, "wx_final"), wu=weights(wu, self.nu, "wu"), wp=float(wp), wpT=float(wp_final))
         return self._rollout_cost(a["plan"], {"noise": a["noise"], "xgoal": xg, "pgoal": pg}, a["alpha"], a["plan_index"], a["qpos"], a["qvel"],
                                   a["state_index"], a["nstates"], frame, want, a["n"], **options)
+
+    # ---- rollouts under the operational-space controller (jaco_rollout_osc: jaco_rollout with jaco_osc's law inside the substep, one launch)
+    def _rollout_osc(self, frames, plan, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        """One jaco_rollout_osc launch: {name: tensor} of the outputs in `want` (names of JacoRolloutFbOut), in the C ABI's layout.
+        frames: the controlled _lib.JacoFrame list; plan: {"ctrl": [P, nknots, nu] or None, "target_pos": [P, nknots, F, 3], "target_quat":
+        [P, nknots, F, 4]}; frame: the output frame or None; options: the keywords of _lib.JacoRolloutOscOptions (nframes is set here)."""
+        dev, nf = self.device, len(frames)
+        rows = 1 if options.get("final_only") else options["nknots"]
+        evals = options["nknots"] * (options["hold"] if options.get("per_substep", 1) else 1)
+        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
+                  "ctrl": (n, max(evals, 0), self.nu)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
+        if n == 0:   # (no launch: jaco_rollout_osc returns JACO_OK for n == 0)
+            return res
+        out = _lib.JacoRolloutFbOut(*[_ptr(res.get(k)) for k in shapes])
+        rec = _lib.JacoRolloutOscPlan(_ptr(plan.get("ctrl")), _ptr(plan["target_pos"]), _ptr(plan["target_quat"]), _ptr(plan_index), int(plan["target_pos"].shape[0]))
+        opt = _lib.JacoRolloutOscOptions(nframes=nf, **options)
+        arr = (_lib.JacoFrame * max(nf, 1))(*frames)
+        self._chk(self.L.jaco_rollout_osc(self.h, _ref(opt), _ref(arr), nf, None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
+                                          _ptr(qpos), _ptr(qvel), _ref(rec), _ref(out), self._stream()))
+        return res
+
+    def rollout_osc(self, frames, target_pos, target_quat, qpos=None, qvel=None, ctrl=None, plan_index=None, state_index=None, hold=1, per_substep=True,
+                    frame=None, final_only=False, **options):
+        """rollout() under the operational-space controller: where are the arm and the hand after T x hold substeps of driving `frames`
+        (one or two _lib.JacoFrame, as osc()) towards target_pos [P, T, F, 3] / target_quat [P, T, F, 4] (unit quaternions, w first)?
+        The motor words of the ctrl are osc()'s law, evaluated inside the kernel on each substep's own mass matrix, bias and poses --
+        before every substep (per_substep=True: the env's own loop of "OSC towards the target, then a substep"), or in the first substep
+        of a knot and held for its `hold` substeps (False).  ctrl [P, T, nu]: the base rows the torques are written into (None:
+        zeros); only the motor actuators of the frames' active dofs change, gripper commands and the other arm's words go through.
+        Rollout i follows plan plan_index[i] (None: plan i) from state row state_index[i] (None: row i) of qpos / qvel (as rollout()):
+        n is the length of whichever index is given (both the same), else P; K target samples of an env share its state row.
+        options: kp, ko, kv, vmax_xyz, vmax_abg, dof_mask (include/jaco_env.h).  No task axes, no null-space terms, no contacts.
+        Returns rollout_feedback()'s dict: "qpos", "qvel", "status", "ctrl" [n, E, nu] (the commanded row of every evaluation, E = T * hold
+        or T, all rows also with final_only) and, with frame (one _lib.JacoFrame, controlled or not), "xpos", "xmat".  status carries
+        _lib.JACO_ROLLOUT_OSC_SINGULAR0 / _SINGULAR1 when frame 0 / 1 took the pseudo-inverse branch at some evaluation.  One launch on
+        the current stream, no synchronisation; the sim's state is not touched."""
+        if isinstance(frames, _lib.JacoFrame):
+            frames = [frames]
+        a = _closed_loop_args(self, "rollout_osc", ctrl, qpos, qvel, None, None, None, None, None, plan_index, state_index,
+                              targets=(target_pos, target_quat, len(frames)))
+        want = ("qpos", "qvel", "status", "ctrl") + (("xpos", "xmat") if frame is not None else ())
+        return self._rollout_osc(list(frames), a["plan"], a["plan_index"], a["qpos"], a["qvel"], a["state_index"], a["nstates"], frame, want, a["n"],
+                                 nknots=a["T"], hold=int(hold), final_only=int(bool(final_only)), per_substep=int(bool(per_substep)), **options)
 
     # ---- the iLQR / TVLQR backward pass (jaco_lqr: the whole recursion of every problem in one launch)
     def _lqr(self, opt, prob, out, n):

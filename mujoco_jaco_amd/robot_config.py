@@ -704,6 +704,50 @@ class BatchedOSC:
         t = torch.as_tensor(target, dtype=torch.float32, device=self.sim.device).reshape(self.sim.num_envs, len(self.names), 6)
         return self.generate_pose(t[..., :3], quat_from_euler_rxyz(t[..., 3:]), q, dq, ctrl)
 
+    def rollout_pose(self, pos, quat, hold=1, per_substep=True, q=None, dq=None, ctrl=None, final_only=False):
+        """Where does this controller take the arm?  K candidate target sequences per env, pos [B, K, T, 3] / quat [B, K, T, 4] (unit
+        quaternions, w first; [B, K, T, n_names, .] with two names: both arms driven), each knot's target followed for `hold` substeps
+        with the controller evaluated inside the kernel before every substep (per_substep=False: once per knot, held), from the sim's
+        state (or q / dq, the controlled chains' angles / velocities spliced into it).  The K candidates of an env share its state row
+        through a state index: nothing is copied.  ctrl [B, nu]: the row the torques are written into at every evaluation (default
+        zeros) -- gripper commands stay as given.  Contact-free, with joint limits (BatchedMujoco.rollout_osc: one jaco_rollout_osc
+        launch; the sim's state is not touched).
+        {"q": [B, K, T, n_arm], "dq": likewise: the robot config's joints after each knot; "ee_pos": [B, K, T, 3], "ee_mat": [B, K, T, 9]:
+        the pose of the controller's first frame; "u": [B, K, E, nu]: the commanded ctrl row of every evaluation (E = T * hold, or T
+        without per_substep; all of them also with final_only); "status": [B, K], with _lib.JACO_ROLLOUT_OSC_SINGULAR0 / 1 where a frame
+        took the pseudo-inverse branch}; final_only=True: T = 1, the last knot.  Runs the plain controller: one built with ctrlr_dof
+        or null_controllers is refused."""
+        import torch
+        if self.task:
+            raise ValueError("BatchedOSC.rollout runs the plain controller: this one was built with ctrlr_dof or null_controllers (jaco_osc_task), "
+                             "which the rollout kernel does not evaluate")
+        B, dev, nf, cfg = self.sim.num_envs, self.sim.device, len(self.names), self.robot_config
+        pos, quat = torch.as_tensor(pos, dtype=torch.float32, device=dev), torch.as_tensor(quat, dtype=torch.float32, device=dev)
+        if pos.dim() not in (4, 5) or pos.shape[0] != B or pos.shape[-1] != 3 or (pos.dim() == 5 and pos.shape[3] != nf) or (pos.dim() == 4 and nf != 1):
+            raise ValueError("rollout: the target positions have shape %s, not [%d, K, T, 3] (one name) or [%d, K, T, %d, 3]" % (tuple(pos.shape), B, B, nf))
+        K, T = int(pos.shape[1]), int(pos.shape[2])
+        if tuple(quat.shape) != tuple(pos.shape[:-1]) + (4,):
+            raise ValueError("rollout: the target quaternions have shape %s, not %s" % (tuple(quat.shape), tuple(pos.shape[:-1]) + (4,)))
+        base = None
+        if ctrl is not None:
+            base = torch.as_tensor(ctrl, dtype=torch.float32, device=dev).reshape(B, 1, 1, self.sim.nu).expand(B, K, T, self.sim.nu).reshape(B * K, T, self.sim.nu)
+        qpos, qvel = self._state(q, dq)
+        index = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(K)
+        r = self.sim.rollout_osc(self.frames, pos.reshape(B * K, T, nf, 3), quat.reshape(B * K, T, nf, 4), qpos, qvel, ctrl=base, state_index=index, hold=hold,
+                                 per_substep=per_substep, frame=self.frames[0], final_only=final_only, **self.options)
+        out = {"q": r["qpos"][..., cfg.arm_qadr], "dq": r["qvel"][..., cfg.arm], "ee_pos": r["xpos"], "ee_mat": r["xmat"], "u": r["ctrl"]}
+        out = {k: t.reshape(B, K, t.shape[-2], t.shape[-1]) for k, t in out.items()}
+        out["status"] = r["status"].reshape(B, K)
+        return out
+
+    def rollout(self, target, hold=1, per_substep=True, q=None, dq=None, ctrl=None, final_only=False):
+        """rollout_pose() in abr_control's convention: target [B, K, T, 6] ([B, K, T, n_names, 6]) = position + 'rxyz' Euler angles."""
+        import torch
+        t = torch.as_tensor(target, dtype=torch.float32, device=self.sim.device)
+        if t.shape[-1] != 6:
+            raise ValueError("rollout: target has shape %s, not [B, K, T, 6] or [B, K, T, n_names, 6]" % (tuple(t.shape),))
+        return self.rollout_pose(t[..., :3], quat_from_euler_rxyz(t[..., 3:]), hold, per_substep, q, dq, ctrl, final_only)
+
 
 class BatchedJoint:
     """abr_control's Joint(robot_config, kp, kv) over a BatchedMujocoConfig: .generate() returns the ctrl rows of every env from ONE
