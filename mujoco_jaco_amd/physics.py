@@ -32,6 +32,12 @@ def _ref(rec):
     return ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p)
 
 
+def _plan_record(plan, alpha, plan_index):
+    """The JacoRolloutPlan of jaco_rollout_fb and jaco_rollout_cost from their launch methods' arguments."""
+    return _lib.JacoRolloutPlan(_ptr(plan["ctrl"]), _ptr(plan.get("kff")), _ptr(plan.get("gain")), _ptr(plan.get("xref")), _ptr(alpha), _ptr(plan_index),
+                                int(plan["ctrl"].shape[0]))
+
+
 class Contacts:
     """One contact record (BatchedMujoco.contacts): the fields of include/jaco_env.h JacoContact as [B, K, ...] device tensors."""
 
@@ -402,20 +408,30 @@ class BatchedMujoco:
         return {"qacc": r["qacc"], "dq": r["dqacc_dqpos"].transpose(1, 2), "dv": r["dqacc_dqvel"].transpose(1, 2), "du": r["dqacc_dctrl"].transpose(1, 2)}
 
     # ---- open-loop rollouts (jaco_rollout: n rollouts of T knots x hold contact-free substeps, one launch)
+    def _launch_rollout(self, entry, Options, Out, options, head, frame, n, state_index, nstates, qpos, qvel, inputs, want):
+        """What the launches of the rollout family share: {name: tensor} of the outputs in `want`, allocated from the family's shape
+        table (`Out`, the entry's JacoRollout*Out record, holds the first of its names); no launch for n == 0 (every entry returns
+        JACO_OK then); else entry(handle, options, *head, frame, n, state_index, nstates, qpos, qvel, *inputs, out, stream), its return
+        code checked.  Options: the entry's options record, built from the keywords `options`; head, inputs: what the entry takes
+        before the output frame and after the states, as the C ABI's pointers."""
+        T = options["nknots"]
+        rows = 1 if options.get("final_only") else T
+        evals = T * (options["hold"] if options.get("per_substep", Options.DEFAULTS.get("per_substep")) else 1)
+        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
+                  "ctrl": (n, max(evals, 0), self.nu), "cost": (n,), "terms": (n, 3)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=self.device) for k in want}
+        if n == 0:   # (no launch: the entry returns JACO_OK for n == 0)
+            return res
+        opt, out = Options(**options), Out(*[_ptr(res.get(k)) for k, _ in Out._fields_])
+        self._chk(entry(self.h, _ref(opt), *head, None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates), _ptr(qpos), _ptr(qvel), *inputs,
+                        _ref(out), self._stream()))
+        return res
+
     def _rollout(self, ctrl, qpos, qvel, state_index, nstates, frame, want, **options):
         """One jaco_rollout launch: {name: tensor} of the outputs in `want` (names of JacoRolloutOut), in the C ABI's layout.  ctrl
         [n, nknots, nu] fp32, qpos / qvel [nstates, ..] fp32 or None, state_index [n] int32 or None: contiguous device tensors."""
-        n, dev = ctrl.shape[0], self.device
-        rows = 1 if options.get("final_only") else options["nknots"]
-        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,)}
-        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
-        if n == 0:   # (no launch: jaco_rollout returns JACO_OK for n == 0)
-            return res
-        out = _lib.JacoRolloutOut(*[_ptr(res.get(k)) for k in shapes])
-        opt = _lib.JacoRolloutOptions(**options)
-        self._chk(self.L.jaco_rollout(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
-                                      _ptr(qpos), _ptr(qvel), _ptr(ctrl), _ref(out), self._stream()))
-        return res
+        return self._launch_rollout(self.L.jaco_rollout, _lib.JacoRolloutOptions, _lib.JacoRolloutOut, options, (), frame, ctrl.shape[0], state_index, nstates,
+                                    qpos, qvel, (_ptr(ctrl),), want)
 
     def rollout(self, ctrl, qpos=None, qvel=None, state_index=None, hold=1, frame=None, final_only=False):
         """What happens over the next T x hold substeps if the ctrl sequences ctrl [n, T, nu] are applied?  mujoco.rollout.rollout,
@@ -448,21 +464,9 @@ class BatchedMujoco:
         """One jaco_rollout_fb launch: {name: tensor} of the outputs in `want` (names of JacoRolloutFbOut), in the C ABI's layout.  plan:
         {"ctrl": [P, nknots, nu], "kff", "gain", "xref": tensors or None}; alpha [n] fp32, plan_index / state_index [n] int32, qpos / qvel
         [nstates, ..] fp32, each or None: contiguous device tensors."""
-        dev = self.device
-        rows = 1 if options.get("final_only") else options["nknots"]
-        evals = options["nknots"] * (options["hold"] if options.get("per_substep") else 1)
-        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
-                  "ctrl": (n, max(evals, 0), self.nu)}
-        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
-        if n == 0:   # (no launch: jaco_rollout_fb returns JACO_OK for n == 0)
-            return res
-        out = _lib.JacoRolloutFbOut(*[_ptr(res.get(k)) for k in shapes])
-        rec = _lib.JacoRolloutPlan(_ptr(plan["ctrl"]), _ptr(plan.get("kff")), _ptr(plan.get("gain")), _ptr(plan.get("xref")), _ptr(alpha), _ptr(plan_index),
-                                   int(plan["ctrl"].shape[0]))
-        opt = _lib.JacoRolloutFbOptions(**options)
-        self._chk(self.L.jaco_rollout_fb(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
-                                         _ptr(qpos), _ptr(qvel), _ref(rec), _ref(out), self._stream()))
-        return res
+        rec = _plan_record(plan, alpha, plan_index)
+        return self._launch_rollout(self.L.jaco_rollout_fb, _lib.JacoRolloutFbOptions, _lib.JacoRolloutFbOut, options, (), frame, n, state_index, nstates,
+                                    qpos, qvel, (_ref(rec),), want)
 
     def rollout_feedback(self, ctrl, qpos=None, qvel=None, gain=None, x_ref=None, dofs=None, feedforward=None, alpha=None, plan_index=None,
                          state_index=None, hold=1, per_substep=False, frame=None, final_only=False):
@@ -488,21 +492,10 @@ class BatchedMujoco:
         """One jaco_rollout_cost launch: {name: tensor} of the outputs in `want` (names of JacoRolloutCostOut), in the C ABI's layout.
         plan: as _rollout_fb's; goal: {"noise": [n, nknots, nu], "xgoal": [P, G, nx], "pgoal": [P, G, 3]: tensors or None}; options: the
         keywords of _lib.JacoRolloutCostOptions."""
-        dev = self.device
-        rows = 1 if options.get("final_only") else options["nknots"]
-        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
-                  "ctrl": (n, options["nknots"], self.nu), "cost": (n,), "terms": (n, 3)}
-        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
-        if n == 0:   # (no launch: jaco_rollout_cost returns JACO_OK for n == 0)
-            return res
-        out = _lib.JacoRolloutCostOut(*[_ptr(res.get(k)) for k in shapes])
-        rec = _lib.JacoRolloutPlan(_ptr(plan["ctrl"]), _ptr(plan.get("kff")), _ptr(plan.get("gain")), _ptr(plan.get("xref")), _ptr(alpha), _ptr(plan_index),
-                                   int(plan["ctrl"].shape[0]))
+        rec = _plan_record(plan, alpha, plan_index)
         g = _lib.JacoRolloutGoal(_ptr(goal.get("noise")), _ptr(goal.get("xgoal")), _ptr(goal.get("pgoal")))
-        opt = _lib.JacoRolloutCostOptions(**options)
-        self._chk(self.L.jaco_rollout_cost(self.h, _ref(opt), None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
-                                           _ptr(qpos), _ptr(qvel), _ref(rec), _ref(g), _ref(out), self._stream()))
-        return res
+        return self._launch_rollout(self.L.jaco_rollout_cost, _lib.JacoRolloutCostOptions, _lib.JacoRolloutCostOut, options, (), frame, n, state_index, nstates,
+                                    qpos, qvel, (_ref(rec), _ref(g)), want)
 
     def rollout_cost(self, ctrl, qpos=None, qvel=None, noise=None, gain=None, x_ref=None, dofs=None, feedforward=None, alpha=None, plan_index=None,
                      state_index=None, hold=1, frame=None, x_goal=None, p_goal=None, wx=None, wx_final=None, wu=None, wp=0.0, wp_final=0.0,
@@ -561,21 +554,11 @@ class BatchedMujoco:
         """One jaco_rollout_osc launch: {name: tensor} of the outputs in `want` (names of JacoRolloutFbOut), in the C ABI's layout.
         frames: the controlled _lib.JacoFrame list; plan: {"ctrl": [P, nknots, nu] or None, "target_pos": [P, nknots, F, 3], "target_quat":
         [P, nknots, F, 4]}; frame: the output frame or None; options: the keywords of _lib.JacoRolloutOscOptions (nframes is set here)."""
-        dev, nf = self.device, len(frames)
-        rows = 1 if options.get("final_only") else options["nknots"]
-        evals = options["nknots"] * (options["hold"] if options.get("per_substep", 1) else 1)
-        shapes = {"qpos": (n, rows, self.nq), "qvel": (n, rows, self.nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,),
-                  "ctrl": (n, max(evals, 0), self.nu)}
-        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=dev) for k in want}
-        if n == 0:   # (no launch: jaco_rollout_osc returns JACO_OK for n == 0)
-            return res
-        out = _lib.JacoRolloutFbOut(*[_ptr(res.get(k)) for k in shapes])
+        nf = len(frames)
         rec = _lib.JacoRolloutOscPlan(_ptr(plan.get("ctrl")), _ptr(plan["target_pos"]), _ptr(plan["target_quat"]), _ptr(plan_index), int(plan["target_pos"].shape[0]))
-        opt = _lib.JacoRolloutOscOptions(nframes=nf, **options)
         arr = (_lib.JacoFrame * max(nf, 1))(*frames)
-        self._chk(self.L.jaco_rollout_osc(self.h, _ref(opt), _ref(arr), nf, None if frame is None else _ref(frame), n, _ptr(state_index), int(nstates),
-                                          _ptr(qpos), _ptr(qvel), _ref(rec), _ref(out), self._stream()))
-        return res
+        return self._launch_rollout(self.L.jaco_rollout_osc, _lib.JacoRolloutOscOptions, _lib.JacoRolloutFbOut, dict(options, nframes=nf), (_ref(arr), nf), frame, n,
+                                    state_index, nstates, qpos, qvel, (_ref(rec),), want)
 
     def rollout_osc(self, frames, target_pos, target_quat, qpos=None, qvel=None, ctrl=None, plan_index=None, state_index=None, hold=1, per_substep=True,
                     frame=None, final_only=False, **options):

@@ -1,9 +1,9 @@
 // TEST INFRASTRUCTURE: runs the unmodified kernel source under the lockstep wavefront emulator.
 // Built by tests/emu/Makefile into every libjaco_emu*.so; used by CPU-side (-m "not gpu") kernel checks: ctrl-level steps (with the
-// contact record of jaco_set_contact_record, or with the low words a handle keeps), env-level calls, the eight query-style entries
-// (jaco_query, jaco_ik, jaco_osc, jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb) and the host build of the env
-// snapshots (jaco_save_envs / jaco_load_envs).  The argument checks and the reset of one env are the library's own host halves
-// (entry_args.h over query.h ... rollout_fb.h, physics_kernel.h, env_logic.h, model_blob.cpp), called here as jaco_env.hip calls them.
+// contact record of jaco_set_contact_record, or with the low words a handle keeps), env-level calls, the ten query-style entries that read
+// the model (jaco_query, jaco_ik, jaco_osc, jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_rollout_cost,
+// jaco_rollout_osc) and the host build of the env snapshots (jaco_save_envs / jaco_load_envs).  The argument checks and the reset of one env are the library's own host halves
+// (entry_args.h over query.h ... rollout_osc.h, physics_kernel.h, env_logic.h, model_blob.cpp), called here as jaco_env.hip calls them.
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -185,10 +185,10 @@ extern "C" int emu_step_lo(const void* blob, long blob_size, int nenv, int nsub,
   return emu_launch(A, nullptr);
 }
 
-// ---- the eight query-style entries.  Each is its library entry with the handle taken away: jaco_<entry>_bind of entry_args.h, the very
+// ---- the ten query-style entries.  Each is its library entry with the handle taken away: jaco_<entry>_bind of entry_args.h, the very
 // function jaco_env.hip calls, turns the arguments into the kernel's block (every check, the defaults, the records by value) or refuses;
 // the block gets the host copy of the model and the kernel runs over the grid the library launches, one wavefront per env (per rollout).
-// Where the library falls back to the handle's fp32 state, the two rollouts are handed it as handle_qpos / handle_qvel [num_envs][..];
+// Where the library falls back to the handle's fp32 state, the rollouts are handed it as handle_qpos / handle_qvel [num_envs][..];
 // the other entries are always called with their state.
 template <class Kernel>
 static int run_grid(int grid, Kernel kernel) {   // (the kernels read only blockIdx)
@@ -283,6 +283,29 @@ extern "C" int emu_rollout_fb(const void* blob, long blob_size, const JacoRollou
   if (!why.empty()) return refuse(why);
   Q.R.model = &g_model;
   return run_grid(n, [&]() { jaco_rollout_fb_kernel(Q); });
+}
+
+extern "C" int emu_rollout_cost(const void* blob, long blob_size, const JacoRolloutCostOptions* opt, const JacoFrame* frame, int n, const int32_t* state_idx,
+                                int nstates, const float* qpos0, const float* qvel0, const JacoRolloutPlan* plan, const JacoRolloutGoal* goal,
+                                const JacoRolloutCostOut* out, int num_envs, const float* handle_qpos, const float* handle_qvel) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoRolloutCostArgs Q;
+  const std::string why = jaco_rollout_cost_bind(g_model, opt, frame, n, state_idx, nstates, qpos0, qvel0, plan, goal, out, num_envs, handle_qpos, handle_qvel, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.F.R.model = &g_model;
+  return run_grid(n, [&]() { jaco_rollout_cost_kernel(Q); });
+}
+
+extern "C" int emu_rollout_osc(const void* blob, long blob_size, const JacoRolloutOscOptions* opt, const JacoFrame* frames, int nframes, const JacoFrame* out_frame, int n,
+                               const int32_t* state_idx, int nstates, const float* qpos0, const float* qvel0, const JacoRolloutOscPlan* plan,
+                               const JacoRolloutFbOut* out, int num_envs, const float* handle_qpos, const float* handle_qvel) {
+  if (load_model(blob, blob_size)) return -1;
+  JacoRolloutOscArgs Q;
+  const std::string why = jaco_rollout_osc_bind(g_model, opt, frames, nframes, out_frame, n, state_idx, nstates, qpos0, qvel0, plan, out, num_envs, handle_qpos,
+                                                handle_qvel, &Q);
+  if (!why.empty()) return refuse(why);
+  Q.R.model = &g_model;
+  return run_grid(n, [&]() { jaco_rollout_osc_kernel(Q); });
 }
 
 // ---- env snapshots: the table and the save / load routines of snapshot.h -- the very header the GPU kernels jaco_save_envs_kernel /

@@ -4,9 +4,10 @@ Runs the *unmodified* HIP kernel source (mujoco_jaco_amd/csrc/physics_kernel.h) 
 against a lockstep 64-lane wavefront emulator, so kernel logic can be checked against the oracle
 without a GPU.  Not a product path: the product library refuses to run without a HIP device.
 One library per layout / build option holds every entry: ctrl-level steps (with the contact record),
-env-level calls, the eight query-style entries (tests/query_binding.py, ik_binding.py, osc_binding.py, osc_task_binding.py,
-joint_binding.py, fd_binding.py, rollout_binding.py, rollout_fb_binding.py; emu_sim.py puts them under BatchedMujoco's own public
-methods as one stand-in sim), and one set of option switches.  lib() is the only
+env-level calls, the ten query-style entries that read the model (tests/query_binding.py, ik_binding.py, osc_binding.py,
+osc_task_binding.py, joint_binding.py, fd_binding.py, rollout_binding.py, rollout_fb_binding.py, rollout_cost_binding.py,
+rollout_osc_binding.py; emu_sim.py puts them under BatchedMujoco's own public methods as one stand-in sim), and one set of option
+switches.  lib() is the only
 place that builds and loads such a library and declares the argument types of its emu_* entries.  The switches are process-wide
 state of a library that every entry shares: whoever flips one puts it back (try / finally), so that no test depends on what ran
 before it.
@@ -55,6 +56,8 @@ def lib(layout=""):
         L.emu_fd.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, vp, fp, fp, fp, vp]
         L.emu_rollout.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
         L.emu_rollout_fb.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.emu_rollout_cost.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]
+        L.emu_rollout_osc.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
         L.emu_step_lo.argtypes = [ctypes.c_char_p, ctypes.c_long, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         L.emu_last_error.restype = ctypes.c_char_p
         L.emu_qpos0.argtypes = [ctypes.c_char_p, ctypes.c_long, fp]

@@ -1,7 +1,7 @@
 """BatchedMujoco on the wavefront emulator -- TEST INFRASTRUCTURE ONLY.
 
 EmuSim(model, qpos, qvel) is what robot_config (BatchedMujocoConfig, BatchedOSC, BatchedJoint) and the cases of the *_binding.py files need
-of a BatchedMujoco, on CPU tensors: every public entry method is BatchedMujoco's own, and only the eight launch methods under them are
+of a BatchedMujoco, on CPU tensors: every public entry method is BatchedMujoco's own, and only the ten launch methods under them are
 replaced, each by the emulated entry of its *_binding.py file.  So the CPU tier runs the product's argument handling, defaults, choice of
 entry and result shaping, and no line of them is restated here.
 
@@ -19,11 +19,14 @@ import osc_binding as ob
 import osc_task_binding as tb
 import query_binding as qb
 import rollout_binding as rb
+import rollout_cost_binding as cb
 import rollout_fb_binding as fbb
+import rollout_osc_binding as rob
 from mujoco_jaco_amd.physics import BatchedMujoco
 from mujoco_jaco_amd.robot_config import FrameTable
 
-ENTRIES = ("jaco_query", "jaco_ik", "jaco_osc", "jaco_osc_task", "jaco_joint", "jaco_fd", "jaco_rollout", "jaco_rollout_fb", "jaco_lqr")
+ENTRIES = ("jaco_query", "jaco_ik", "jaco_osc", "jaco_osc_task", "jaco_joint", "jaco_fd", "jaco_rollout", "jaco_rollout_fb",
+           "jaco_rollout_cost", "jaco_rollout_osc", "jaco_lqr")
 
 
 def _np(t):
@@ -94,6 +97,21 @@ class EmuSim:
                                        _np(plan.get("xref")), options["dofs"], _np(alpha), _np(plan_index), _np(state_index), nstates, frame,
                                        tuple(want), options["hold"], options["final_only"], options["per_substep"], handle=self._state(None, None), n=n))
 
+    def _rollout_cost(self, plan, goal, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        self.launches["jaco_rollout_cost"] += 1
+        w = {k: options[k] for k in ("wx", "wxT", "wu", "wp", "wpT")}
+        return _tensors(cb.rollout_cost(self.model, _np(plan["ctrl"]), _np(qpos), _np(qvel), _np(goal.get("noise")), _np(goal.get("xgoal")), _np(goal.get("pgoal")), w,
+                                        options["goal_per_knot"], _np(plan.get("kff")), _np(plan.get("gain")), _np(plan.get("xref")), options["dofs"], _np(alpha),
+                                        _np(plan_index), _np(state_index), nstates, frame, tuple(want), options["hold"], options["final_only"],
+                                        handle=self._state(None, None), n=n))
+
+    def _rollout_osc(self, frames, plan, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
+        self.launches["jaco_rollout_osc"] += 1
+        o = dict(options)
+        T = o.pop("nknots")
+        return _tensors(rob.rollout_osc(self.model, list(frames), _np(plan["target_pos"]), _np(plan["target_quat"]), _np(plan.get("ctrl")), _np(qpos), _np(qvel),
+                                        _np(plan_index), _np(state_index), nstates, frame, tuple(want), handle=self._state(None, None), n=n, nknots=T, **o))
+
     def _lqr(self, opt, prob, out, n):
         self.launches["jaco_lqr"] += 1
         lb.lqr(opt, prob, out, n)
@@ -104,4 +122,5 @@ class EmuSim:
     query, ik, osc, joint = BatchedMujoco.query, BatchedMujoco.ik, BatchedMujoco.osc, BatchedMujoco.joint
     forward_dynamics, linearize = BatchedMujoco.forward_dynamics, BatchedMujoco.linearize
     rollout, rollout_feedback, lqr_backward = BatchedMujoco.rollout, BatchedMujoco.rollout_feedback, BatchedMujoco.lqr_backward
+    rollout_cost, rollout_osc = BatchedMujoco.rollout_cost, BatchedMujoco.rollout_osc
     _index = BatchedMujoco._index

@@ -3,7 +3,8 @@ tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRU
 
 Also: the fp64 reference (the oracle with contacts disabled: per rollout qpos / qvel and a zero warm start, then step(ctrl_k, hold) per
 knot), the input sets with the conditions they must meet asserted on the fp64 side, the cases shared by the CPU and the GPU tier, the
-refusals.  emu_sim.EmuSim runs BatchedMujoco.rollout on the emulated call (CPU tests of robot_config).
+refusals.  emu_sim.EmuSim runs BatchedMujoco.rollout on the emulated call (CPU tests of robot_config).  And what the four entries of
+the family (jaco_rollout, _fb, _cost, _osc) share on both tiers: the prelude of a call (Tier, prelude) and the bad-index case (bad_index).
 
 A tier hands the cases its `run`:
   run(model, ctrl [n, T, nu], qpos0=None, qvel0=None, state_index=None, nstates=None, frame=None, want=OUTS, hold=1, final_only=0,
@@ -27,12 +28,85 @@ SENTINEL, STATUS_SENTINEL = 7.0, 0x7777
 BAD_INDEX = product_lib.JACO_ROLLOUT_BAD_INDEX
 
 
-def shapes(n, rows, nq, nv):
-    return {"qpos": (n, rows, nq), "qvel": (n, rows, nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,)}
+# ---- what every call of the rollout family does before its one foreign call, for the four emulated entries (rollout here, rollout_fb,
+# rollout_cost, rollout_osc of their *_binding.py files) and for their GPU twins (the abi_call of tests/test_gpu_rollout*.py)
+class Tier:
+    """What the two tiers of a call differ in.  array(a, dtype) -> a as the tier's contiguous array of that numpy dtype; full(shape,
+    value, dtype) -> an array filled with value; address(array) -> where it lies, as a c_void_p; min_rows: the rollouts the outputs have
+    rows for when n <= 0 (the emulator: none; the GPU: one, so that no output pointer is NULL)."""
+
+    def __init__(self, array, full, address, min_rows):
+        self.array, self.full, self.address, self.min_rows = array, full, address, min_rows
+
+    def f32(self, a):
+        return None if a is None else self.array(a, np.float32)
+
+    def i32(self, a):
+        return None if a is None else self.array(a, np.int32)
+
+    def ptr(self, a):
+        return None if a is None else self.address(a)
+
+    def blank(self, shape, status=False):
+        """An output array as a call is handed it: the sentinel in every word."""
+        return self.full(shape, STATUS_SENTINEL, np.uint32) if status else self.full(shape, SENTINEL, np.float32)
 
 
-def blank(shape, status=False):
-    return np.full(shape, STATUS_SENTINEL, np.uint32) if status else np.full(shape, SENTINEL, np.float32)
+HOST = Tier(np.ascontiguousarray, np.full, lambda a: ctypes.c_void_p(a.ctypes.data), 0)
+
+
+def ref(record, absent=False):
+    """The address of a ctypes record (or of an array of them) as the C ABI's untyped pointer; NULL for None or with `absent`."""
+    return None if record is None or absent else ctypes.cast(ctypes.pointer(record), ctypes.c_void_p)
+
+
+def count(nplans, per_rollout=(), n=None):
+    """n of a call: given, or the length of the first per-rollout array that is there, or the number of plans."""
+    if n is not None:
+        return n
+    for a in per_rollout:
+        if a is not None:
+            return len(a)
+    return nplans
+
+
+def shapes(n, rows, evals, nq, nv, nu):
+    """The family's outputs: jaco_rollout's five, "ctrl" of the closed loops, "cost" and "terms" of the costed one."""
+    return {"qpos": (n, rows, nq), "qvel": (n, rows, nv), "xpos": (n, rows, 3), "xmat": (n, rows, 9), "status": (n,), "ctrl": (n, evals, nu),
+            "cost": (n,), "terms": (n, 3)}
+
+
+def prelude(tier, dims, want, nplans, knots, q0, v0, num_envs, per_rollout=(), n=None, nknots=None, nstates=None, hold=1, final_only=0, per_substep=0):
+    """(n, nknots, nstates, {output in `want`: the tier's array, sentinel-filled}) of one call.  dims = (nq, nv, nu); nplans, knots: what
+    the plan arrays say; q0 / v0: the tier's state override arrays or None; num_envs: the handle's; per_rollout: the tier's per-rollout
+    arrays in the order their length decides n; n / nknots / nstates: the overrides (refusals)."""
+    n = count(nplans, per_rollout, n)
+    nknots = knots if nknots is None else nknots
+    if nstates is None:
+        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else num_envs)
+    rows = 1 if final_only == 1 else max(nknots, 1)
+    evals = max(nknots, 1) * (max(hold, 1) if per_substep == 1 else 1)
+    sh = shapes(max(n, tier.min_rows), rows, evals, *dims)
+    return n, nknots, nstates, {k: tier.blank(sh[k], k == "status") for k in want}
+
+
+def emu_model(model, handle):
+    """What an emulated call needs of its model and its handle: (the layout's library, the blob, (nq, nv, nu), num_envs, the handle's fp32
+    qpos, qvel); handle None: no envs, NULL state."""
+    blob, layout, nu = ob._model_info(model)
+    M = ib.load_model(model)
+    hq, hv = (None, None) if handle is None else (HOST.f32(handle[0]), HOST.f32(handle[1]))
+    return emu_binding.lib(layout), blob, (int(M["nq"][0]), int(M["nv"][0]), nu), 0 if hq is None else hq.shape[0], hq, hv
+
+
+def checked(L, rc, entry, res):
+    """res, or the refusal's ValueError with the outputs the call was handed in .outputs."""
+    try:
+        emu_binding.check(L, rc, entry)
+    except ValueError as e:
+        e.outputs = res
+        raise
+    return res
 
 
 def rollout(model, ctrl, qpos0=None, qvel0=None, state_index=None, nstates=None, frame=None, want=OUTS, hold=1, final_only=0, handle=None,
@@ -40,35 +114,16 @@ def rollout(model, ctrl, qpos0=None, qvel0=None, state_index=None, nstates=None,
     """Emulated jaco_rollout: {output: array} in the C ABI's layout.  n / nknots: override what the ctrl array says (refusals);
     no_opt / no_out / no_ctrl hand NULL pointers.  Raises ValueError with the library's message when the call is refused, with the
     outputs it was handed in .outputs."""
-    blob, layout, nu = ob._model_info(model)
-    M = ib.load_model(model)
-    nq, nv = int(M["nq"][0]), int(M["nv"][0])
-    L = emu_binding.lib(layout)
-    ctrl = np.ascontiguousarray(ctrl, np.float32)
-    n = ctrl.shape[0] if n is None else n
-    nknots = ctrl.shape[1] if nknots is None else nknots
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-    q0, v0 = f32(qpos0), f32(qvel0)
-    hq, hv = (None, None) if handle is None else (f32(handle[0]), f32(handle[1]))
-    num_envs = 0 if hq is None else hq.shape[0]
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else num_envs)
-    idx = None if state_index is None else np.ascontiguousarray(state_index, np.int32)
-    rows = 1 if final_only == 1 else max(nknots, 1)
-    sh = shapes(max(n, 0), rows, nq, nv)
-    res = {k: blank(sh[k], k == "status") for k in want}
-    p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+    L, blob, dims, num_envs, hq, hv = emu_model(model, handle)
+    p = HOST.ptr
+    ctrl, q0, v0, idx = HOST.f32(ctrl), HOST.f32(qpos0), HOST.f32(qvel0), HOST.i32(state_index)
+    n, nknots, nstates, res = prelude(HOST, dims, want, ctrl.shape[0], ctrl.shape[1], q0, v0, num_envs, n=n, nknots=nknots, nstates=nstates, hold=hold,
+                                      final_only=final_only)
     out = product_lib.JacoRolloutOut(*[p(res.get(k)) for k in OUTS])
     opt = product_lib.JacoRolloutOptions(nknots=nknots, hold=hold, final_only=final_only)
-    rc = L.emu_rollout(blob, len(blob), None if no_opt else ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                       None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, p(idx), nstates, p(q0), p(v0),
-                       None if no_ctrl else p(ctrl), None if no_out else ctypes.cast(ctypes.pointer(out), ctypes.c_void_p), num_envs, p(hq), p(hv))
-    try:
-        emu_binding.check(L, rc, "emu_rollout")
-    except ValueError as e:
-        e.outputs = res
-        raise
-    return res
+    rc = L.emu_rollout(blob, len(blob), ref(opt, no_opt), ref(frame), n, p(idx), nstates, p(q0), p(v0), None if no_ctrl else p(ctrl), ref(out, no_out),
+                       num_envs, p(hq), p(hv))
+    return checked(L, rc, "emu_rollout", res)
 
 
 def emu_steps(model, q, v, ctrl, hold):
@@ -265,20 +320,38 @@ def case_self_consistency(run, model=MODEL):
     same(run(model, c, None, None, frame=ee, hold=hold, handle=(q, v)), full)
 
 
+BAD_STATES, BAD_PLANS = 7, 4   # the states and the plans the bad-index case's entries point into
+
+
+def bad_index(call, outs, plans):
+    """The bad-index case of the four entries: index entries -1 and one past the end among valid ones have JACO_ROLLOUT_BAD_INDEX in
+    their status words and their rows of every output in `outs` untouched; every other rollout is bitwise what it is without the bad
+    entries.  call(keep, **indices) -> the tier's result on BAD_STATES states (and, with `plans`, BAD_PLANS plans) with those index
+    arrays -- state_index, with `plans` also plan_index --, `keep`: the rollouts of the full call it makes (rows of a per-rollout input)."""
+    m, P = BAD_STATES, BAD_PLANS
+    sidx = np.array([0, 3, -1, 6, m, 2, 2, 5, 1, 4], np.int32)
+    pidx = np.array([0, 1, 2, P, 3, -1, 2, 0, 3, 1], np.int32)
+    if plans:
+        index, bad = dict(plan_index=pidx, state_index=sidx), (sidx < 0) | (sidx >= m) | (pidx < 0) | (pidx >= P)
+        assert bad.sum() == 4
+    else:   # (jaco_rollout: one sequence per rollout, nine of them)
+        sidx = sidx[:-1]
+        index, bad = dict(state_index=sidx), (sidx < 0) | (sidx >= m)
+    r = call(np.arange(len(sidx)), **index)
+    ok = call(np.flatnonzero(~bad), **{k: x[~bad] for k, x in index.items()})
+    assert (r["status"][bad] == BAD_INDEX).all() and (r["status"][~bad] == 0).all()
+    for key in outs:
+        if key != "status":
+            assert (bits(r[key][bad]) == bits(np.float32(SENTINEL))).all(), key
+            assert (bits(r[key][~bad]) == bits(ok[key])).all(), key
+
+
 def case_bad_index(run, model=MODEL):
     """Case 5: state_index entries -1 and nstates among valid ones: JACO_ROLLOUT_BAD_INDEX in their status words, their rows untouched,
     every other rollout bitwise what it is without the bad entries."""
     g = shared(model)
-    m, ee = 7, frames(model)[1]
-    idx = np.array([0, 3, -1, 6, m, 2, 2, 5, 1], np.int32)
-    bad = (idx < 0) | (idx >= m)
-    c = g["c"][:len(idx)]
-    r = run(model, c, g["q"][:m], g["v"][:m], state_index=idx, frame=ee, hold=g["hold"])
-    ok = run(model, c[~bad], g["q"][:m], g["v"][:m], state_index=idx[~bad], frame=ee, hold=g["hold"])
-    assert (r["status"][bad] == BAD_INDEX).all() and (r["status"][~bad] == 0).all()
-    for k in OUTS[:4]:
-        assert (bits(r[k][bad]) == bits(np.float32(SENTINEL))).all(), k
-        assert (bits(r[k][~bad]) == bits(ok[k])).all(), k
+    m, ee = BAD_STATES, frames(model)[1]
+    bad_index(lambda keep, **index: run(model, g["c"][keep], g["q"][:m], g["v"][:m], frame=ee, hold=g["hold"], **index), OUTS, plans=False)
 
 
 # ---- the refusals: one argument set per JACO_EINVAL case of include/jaco_env.h, for the emulator's entry and the library's alike

@@ -1,10 +1,10 @@
 """The costed rollout kernel (mujoco_jaco_amd/csrc/rollout_cost.h, jaco_rollout_cost) under the wavefront emulator (emu_rollout_cost of
-tests/emu_rollout_cost/libjaco_emu_rollout_cost{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 cost reference (the header's formula evaluated in fp64 on a call's own fp32 outputs), the input sets --
 rollout_fb_binding.shared's states, plans and gains as they are, plus seeded goals distinct per plan, weights and noise -- the cases
-shared by the CPU and the GPU tier, the refusals, and CostEmuSim: emu_sim.EmuSim with the one launch method _rollout_cost added, so
-that BatchedMujoco.rollout_cost and robot_config run on the emulated call.
+shared by the CPU and the GPU tier and the refusals.  emu_sim.EmuSim runs BatchedMujoco.rollout_cost on the emulated call (CPU tests of
+robot_config).
 
 A tier hands the cases three calls:
   run(model, ctrl [P, T, nu], qpos0=None, qvel0=None, noise=None, xgoal=None, pgoal=None, weights=None, goal_per_knot=0, kff=None,
@@ -13,46 +13,18 @@ A tier hands the cases three calls:
   run_fb: rollout_fb_binding's `run` (jaco_rollout_fb on the same tier);  run_open: its `run_open` (jaco_rollout).
 Every output array is handed in filled with SENTINEL (status: STATUS_SENTINEL), so what a call leaves untouched shows.
 """
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 
-import emu_binding
-import emu_sim
 import fd_binding as fb
-import ik_binding as ib
-import osc_binding as ob
 import rollout_binding as rb
 import rollout_fb_binding as fbb
 from fd_binding import bits
 from mujoco_jaco_amd import _lib as product_lib
-from mujoco_jaco_amd.physics import BatchedMujoco
-from rollout_binding import BAD_INDEX, SENTINEL, STATUS_SENTINEL, same
+from rollout_binding import SENTINEL, STATUS_SENTINEL, same
 
 OUTS = ("qpos", "qvel", "xpos", "xmat", "status", "ctrl", "cost", "terms")
 COST = ("cost", "terms", "status")
 FLAG_NAN = product_lib.JACO_FLAG_NAN
-EMU_DIR = os.path.join(emu_binding.ROOT, "tests", "emu_rollout_cost")
-_libs = {}
-
-
-def lib(layout=""):
-    """The emulator build of one layout with the emu_rollout_cost entry (and everything emu_binding.lib has: it includes that driver)."""
-    if layout not in _libs:
-        name = "libjaco_emu_rollout_cost%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.emu_rollout_cost.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
-
-
-def shapes(n, rows, nknots, nq, nv, nu):
-    return dict(fbb.shapes(n, rows, nknots, nq, nv, nu), cost=(n,), terms=(n, 3))
 
 
 def weight_options(weights):
@@ -79,35 +51,17 @@ def rollout_cost(model, ctrl, qpos0=None, qvel0=None, noise=None, xgoal=None, pg
     """Emulated jaco_rollout_cost: {output: array} in the C ABI's layout.  n / nknots / nplans / ndofs override what the arrays say
     (refusals); no_* hand NULL pointers.  Raises ValueError with the library's message when the call is refused, with the outputs it was
     handed in .outputs."""
-    blob, layout, nu = ob._model_info(model)
-    M = ib.load_model(model)
-    nq, nv = int(M["nq"][0]), int(M["nv"][0])
-    L = lib(layout)
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
-    ctrl, kff, gain, xref, alpha, q0, v0, noise, xgoal, pgoal = [f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0, noise, xgoal, pgoal)]
-    pidx, sidx = i32(plan_index), i32(state_index)
-    if n is None:
-        n = fbb.count(ctrl, alpha, pidx, sidx) if noise is None else noise.shape[0]
-    nknots = ctrl.shape[1] if nknots is None else nknots
-    hq, hv = (None, None) if handle is None else (f32(handle[0]), f32(handle[1]))
-    num_envs = 0 if hq is None else hq.shape[0]
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else num_envs)
-    sh = shapes(max(n, 0), 1 if final_only == 1 else max(nknots, 1), max(nknots, 1), nq, nv, nu)
-    res = {k: rb.blank(sh[k], k == "status") for k in want}
-    p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+    L, blob, dims, num_envs, hq, hv = rb.emu_model(model, handle)
+    p, ref = rb.HOST.ptr, rb.ref
+    ctrl, kff, gain, xref, alpha, q0, v0, noise, xgoal, pgoal = [rb.HOST.f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0, noise, xgoal, pgoal)]
+    pidx, sidx = rb.HOST.i32(plan_index), rb.HOST.i32(state_index)
+    n, nknots, nstates, res = rb.prelude(rb.HOST, dims, want, ctrl.shape[0], ctrl.shape[1], q0, v0, num_envs, (noise, pidx, sidx, alpha), n, nknots, nstates, hold,
+                                         final_only)
     opt, plan, goal, out = records(p, res, ctrl, kff, gain, xref, alpha, pidx, noise, xgoal, pgoal, weights, dofs, nknots, hold, final_only, goal_per_knot,
                                    ctrl.shape[0] if nplans is None else nplans, ndofs, no_ctrl)
-    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-    rc = L.emu_rollout_cost(blob, len(blob), None if no_opt else cast(opt), None if frame is None else cast(frame), n, p(sidx), nstates, p(q0), p(v0),
-                            None if no_plan else cast(plan), None if no_goal else cast(goal), None if no_out else cast(out), num_envs, p(hq), p(hv))
-    try:
-        emu_binding.check(L, rc, "emu_rollout_cost")
-    except ValueError as e:
-        e.outputs = res
-        raise
-    return res
+    rc = L.emu_rollout_cost(blob, len(blob), ref(opt, no_opt), ref(frame), n, p(sidx), nstates, p(q0), p(v0), ref(plan, no_plan), ref(goal, no_goal),
+                            ref(out, no_out), num_envs, p(hq), p(hv))
+    return rb.checked(L, rc, "emu_rollout_cost", res)
 
 
 # ---- the fp64 reference
@@ -288,19 +242,9 @@ def case_bad_index(run, model=rb.MODEL):
     """Case 7: plan_idx and state_idx entries out of range write the status word alone: the sentinels of every other output stand, cost
     and terms included, and every other rollout is bitwise what it is without the bad entries."""
     g = shared(model)
-    m, P = 7, 4
-    sidx = np.array([0, 3, -1, 6, m, 2, 2, 5, 1, 4], np.int32)
-    pidx = np.array([0, 1, 2, P, 3, -1, 2, 0, 3, 1], np.int32)
-    bad = (sidx < 0) | (sidx >= m) | (pidx < 0) | (pidx >= P)
-    assert bad.sum() == 4
+    m, P = rb.BAD_STATES, rb.BAD_PLANS
     k = dict(hold=g["hold"], gain=g["gain"][:P], xref=g["xref"][:P], dofs=g["dofs"], **goal_args(g, 1, slice(0, P)))
-    r = run(model, g["c"][:P], g["q"][:m], g["v"][:m], plan_index=pidx, state_index=sidx, noise=g["noise"][:len(sidx)], **k)
-    ok = run(model, g["c"][:P], g["q"][:m], g["v"][:m], plan_index=pidx[~bad], state_index=sidx[~bad], noise=g["noise"][:len(sidx)][~bad], **k)
-    assert (r["status"][bad] == BAD_INDEX).all() and (r["status"][~bad] == 0).all()
-    for key in OUTS:
-        if key != "status":
-            assert (bits(r[key][bad]) == bits(np.float32(SENTINEL))).all(), key
-            assert (bits(r[key][~bad]) == bits(ok[key])).all(), key
+    rb.bad_index(lambda keep, **index: run(model, g["c"][:P], g["q"][:m], g["v"][:m], noise=g["noise"][keep], **index, **k), OUTS, plans=True)
 
 
 def case_non_finite(run, model=rb.MODEL):
@@ -360,26 +304,7 @@ def refusal_args(case):
     return k
 
 
-# ---- case 10: the Python tiers
-class CostEmuSim(emu_sim.EmuSim):
-    """emu_sim.EmuSim plus the launch method of jaco_rollout_cost."""
-
-    def __init__(self, model=None, qpos=None, qvel=None):
-        super().__init__(model, qpos, qvel)
-        self.launches["jaco_rollout_cost"] = 0
-
-    def _rollout_cost(self, plan, goal, alpha, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
-        self.launches["jaco_rollout_cost"] += 1
-        N = emu_sim._np
-        w = {k: options[k] for k in ("wx", "wxT", "wu", "wp", "wpT")}
-        return emu_sim._tensors(rollout_cost(self.model, N(plan["ctrl"]), N(qpos), N(qvel), N(goal.get("noise")), N(goal.get("xgoal")), N(goal.get("pgoal")), w,
-                                             options["goal_per_knot"], N(plan.get("kff")), N(plan.get("gain")), N(plan.get("xref")), options["dofs"], N(alpha),
-                                             N(plan_index), N(state_index), nstates, frame, tuple(want), options["hold"], options["final_only"],
-                                             handle=self._state(None, None), n=n))
-
-    rollout_cost = BatchedMujoco.rollout_cost   # (everything above the launch is the product's, as in EmuSim)
-
-
+# ---- case 10: the Python tiers.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 MPPI_MODELS = fbb.HOLD_MODELS
 MPPI_B, MPPI_K, MPPI_T, MPPI_HOLD, MPPI_ITERS = 3, 16, 6, 2, 4
 MPPI_SIGMA, MPPI_SEED, MPPI_TEMPERATURE = 2.0, 5, 0.05

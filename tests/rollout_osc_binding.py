@@ -1,12 +1,11 @@
 """The operational-space rollout kernel (mujoco_jaco_amd/csrc/rollout_osc.h, jaco_rollout_osc) under the wavefront emulator
-(emu_rollout_osc of tests/emu_rollout_osc/libjaco_emu_rollout_osc{,_d12,_d30}.so) -- TEST INFRASTRUCTURE ONLY.
+(emu_rollout_osc of tests/emu/libjaco_emu{,_d12,_d30}.so, through emu_binding.lib) -- TEST INFRASTRUCTURE ONLY.
 
 Also: the fp64 reference (the oracle with contacts disabled, stepped by rollout_binding.oracle_rollout's substeps, the law
 osc_binding.reference evaluated on the oracle's own state at each evaluation), the input sets -- rollout_binding.inputs' states and ctrl
 rows (starts that open with a joint-limit row, gripper words in the base ctrl) plus seeded targets a few centimetres and tenths of a
 radian from each start pose -- with the conditions they must meet asserted on the fp64 side, the cases shared by the CPU and the GPU
-tier, the refusals, and OscEmuSim: emu_sim.EmuSim with the one launch method _rollout_osc added, so that BatchedMujoco.rollout_osc and
-robot_config.BatchedOSC.rollout run on the emulated call.
+tier and the refusals.  emu_sim.EmuSim runs BatchedMujoco.rollout_osc and robot_config.BatchedOSC.rollout on the emulated call.
 
 A tier hands the cases these calls:
   run(model, frames, target_pos [P, T, F, 3], target_quat [P, T, F, 4], ctrl=None, qpos0=None, qvel0=None, plan_index=None,
@@ -19,13 +18,9 @@ A tier hands the cases these calls:
 Every output array is handed in filled with SENTINEL (status: STATUS_SENTINEL), so what a call leaves untouched shows.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-import emu_binding
-import emu_sim
 import fd_binding as fb
 import ik_binding as ib
 import osc_binding as ob
@@ -33,38 +28,13 @@ import rollout_binding as rb
 import rollout_fb_binding as fbb
 from fd_binding import bits, verr
 from mujoco_jaco_amd import _lib as product_lib
-from mujoco_jaco_amd.physics import BatchedMujoco
-from rollout_binding import BAD_INDEX, SENTINEL, STATUS_SENTINEL, same
+from rollout_binding import same
 
 OUTS = fbb.OUTS
 STATE = fbb.STATE
 SING0, SING1 = product_lib.JACO_ROLLOUT_OSC_SINGULAR0, product_lib.JACO_ROLLOUT_OSC_SINGULAR1
 SING = SING0 | SING1
 FLAG_NAN = product_lib.JACO_FLAG_NAN
-EMU_DIR = os.path.join(emu_binding.ROOT, "tests", "emu_rollout_osc")
-_libs = {}
-
-
-def lib(layout=""):
-    """The emulator build of one layout with the emu_rollout_osc entry (and everything emu_binding.lib has: it includes that driver)."""
-    if layout not in _libs:
-        name = "libjaco_emu_rollout_osc%s.so" % layout
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR, name])
-        L = ctypes.CDLL(os.path.join(EMU_DIR, name))
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.emu_rollout_osc.argtypes = [ctypes.c_char_p, ctypes.c_long, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
-        L.emu_last_error.restype = ctypes.c_char_p
-        _libs[layout] = L
-    return _libs[layout]
-
-
-def count(P, plan_index=None, state_index=None, n=None):
-    if n is not None:
-        return n
-    for a in (plan_index, state_index):
-        if a is not None:
-            return len(a)
-    return P
 
 
 def records(ptr, outs, frames, ctrl, tp, tq, pidx, nknots, hold, final_only, per_substep, nplans, nframes=None, opt_nframes=None, **gains):
@@ -84,37 +54,18 @@ def rollout_osc(model, frames, target_pos, target_quat, ctrl=None, qpos0=None, q
     """Emulated jaco_rollout_osc: {output: array} in the C ABI's layout.  n / nknots / nplans / nframes override what the arrays say
     (refusals); no_* hand NULL pointers.  Raises ValueError with the library's message when the call is refused, with the outputs it was
     handed in .outputs."""
-    blob, layout, nu = ob._model_info(model)
-    M = ib.load_model(model)
-    nq, nv = int(M["nq"][0]), int(M["nv"][0])
-    L = lib(layout)
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
-    tp, tq, ctrl, q0, v0 = [f32(a) for a in (target_pos, target_quat, ctrl, qpos0, qvel0)]
-    pidx, sidx = i32(plan_index), i32(state_index)
-    n = count(tp.shape[0], pidx, sidx, n)
-    nknots = tp.shape[1] if nknots is None else nknots
-    hq, hv = (None, None) if handle is None else (f32(handle[0]), f32(handle[1]))
-    num_envs = 0 if hq is None else hq.shape[0]
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else num_envs)
-    rows = 1 if final_only == 1 else max(nknots, 1)
-    sh = fbb.shapes(max(n, 0), rows, max(nknots, 1) * (max(hold, 1) if per_substep == 1 else 1), nq, nv, nu)
-    res = {k: rb.blank(sh[k], k == "status") for k in want}
-    p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+    L, blob, dims, num_envs, hq, hv = rb.emu_model(model, handle)
+    p, ref = rb.HOST.ptr, rb.ref
+    tp, tq, ctrl, q0, v0 = [rb.HOST.f32(a) for a in (target_pos, target_quat, ctrl, qpos0, qvel0)]
+    pidx, sidx = rb.HOST.i32(plan_index), rb.HOST.i32(state_index)
+    n, nknots, nstates, res = rb.prelude(rb.HOST, dims, want, tp.shape[0], tp.shape[1], q0, v0, num_envs, (pidx, sidx), n, nknots, nstates, hold, final_only,
+                                         per_substep)
     opt, arr, plan, out = records(p, res, frames, ctrl, None if no_pos else tp, None if no_quat else tq, pidx, nknots, hold, final_only, per_substep,
                                   tp.shape[0] if nplans is None else nplans, nframes, opt_nframes, **gains)
-    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
     nf = (0 if frames is None else len(frames)) if nframes is None else nframes
-    rc = L.emu_rollout_osc(blob, len(blob), None if no_opt else cast(opt), None if arr is None else ctypes.cast(arr, ctypes.c_void_p), nf,
-                           None if frame is None else cast(frame), n, p(sidx), nstates, p(q0), p(v0), None if no_plan else cast(plan),
-                           None if no_out else cast(out), num_envs, p(hq), p(hv))
-    try:
-        emu_binding.check(L, rc, "emu_rollout_osc")
-    except ValueError as e:
-        e.outputs = res
-        raise
-    return res
+    rc = L.emu_rollout_osc(blob, len(blob), ref(opt, no_opt), None if arr is None else ctypes.cast(arr, ctypes.c_void_p), nf, ref(frame), n, p(sidx), nstates,
+                           p(q0), p(v0), ref(plan, no_plan), ref(out, no_out), num_envs, p(hq), p(hv))
+    return rb.checked(L, rc, "emu_rollout_osc", res)
 
 
 # ---- the models and their controlled frames
@@ -152,7 +103,7 @@ def oracle_closed_loop(model, q, v, base, target6, plan_index=None, state_index=
     names = names_of(model)
     _, per = motors(model)
     P, T, F = target6.shape[:3]
-    n = count(P, plan_index, state_index)
+    n = rb.count(P, (plan_index, state_index))
     E = T * (hold if per_substep else 1)
     r = dict(qpos=np.zeros((n, T, o.nq)), qvel=np.zeros((n, T, o.nv)), u=np.zeros((n, E, o.nu)), det=np.zeros((n, E, F)), xpos=np.zeros((n, T, 3)))
     tab = ib.table_of(model)
@@ -390,19 +341,9 @@ def case_bad_index(run, model=rb.MODEL):
     """plan_idx and state_idx entries -1 and one past the end among valid ones: JACO_ROLLOUT_BAD_INDEX in their status words, their rows
     untouched (ctrl included), every other rollout bitwise what it is without the bad entries."""
     g = shared(model)
-    m, P = 7, 4
-    sidx = np.array([0, 3, -1, 6, m, 2, 2, 5, 1, 4], np.int32)
-    pidx = np.array([0, 1, 2, P, 3, -1, 2, 0, 3, 1], np.int32)
-    bad = (sidx < 0) | (sidx >= m) | (pidx < 0) | (pidx >= P)
-    assert bad.sum() == 4
+    m, P = rb.BAD_STATES, rb.BAD_PLANS
     k = dict(qpos0=g["q"][:m], qvel0=g["v"][:m], frame=g["ee"], hold=g["hold"], **args(g, slice(0, P)))
-    r = run(model, g["frames"], plan_index=pidx, state_index=sidx, **k)
-    ok = run(model, g["frames"], plan_index=pidx[~bad], state_index=sidx[~bad], **k)
-    assert (r["status"][bad] == BAD_INDEX).all() and (r["status"][~bad] == 0).all()
-    for key in OUTS:
-        if key != "status":
-            assert (bits(r[key][bad]) == bits(np.float32(SENTINEL))).all(), key
-            assert (bits(r[key][~bad]) == bits(ok[key])).all(), key
+    rb.bad_index(lambda keep, **index: run(model, g["frames"], **index, **k), OUTS, plans=True)
 
 
 # ---- the refusals: one argument set per JACO_EINVAL case of include/jaco_env.h, for the emulator's entry and the library's alike
@@ -451,25 +392,7 @@ def refusal_args(case):
     return k
 
 
-# ---- the Python tiers
-class OscEmuSim(emu_sim.EmuSim):
-    """emu_sim.EmuSim plus the launch method of jaco_rollout_osc."""
-
-    def __init__(self, model=None, qpos=None, qvel=None):
-        super().__init__(model, qpos, qvel)
-        self.launches["jaco_rollout_osc"] = 0
-
-    def _rollout_osc(self, frames, plan, plan_index, qpos, qvel, state_index, nstates, frame, want, n, **options):
-        self.launches["jaco_rollout_osc"] += 1
-        A = emu_sim._np
-        o = dict(options)
-        T = o.pop("nknots")
-        return emu_sim._tensors(rollout_osc(self.model, list(frames), A(plan["target_pos"]), A(plan["target_quat"]), A(plan.get("ctrl")), A(qpos), A(qvel),
-                                            A(plan_index), A(state_index), nstates, frame, tuple(want), handle=self._state(None, None), n=n, nknots=T, **o))
-
-    rollout_osc = BatchedMujoco.rollout_osc   # (everything above the launch is the product's, as in EmuSim)
-
-
+# ---- the Python tiers.  make_sim(model, qpos, qvel) -> a BatchedMujoco (GPU tier) or emu_sim.EmuSim.
 CONFIG_MODELS = {"jaco2_reaching_torque": ("EE",), "jaco2_dual_torque": ("EE_1", "EE_2")}
 CONFIG_K, CONFIG_T, CONFIG_HOLD = 3, 4, 2
 

@@ -1,6 +1,6 @@
-"""CPU tier: BatchedMujoco's own query / ik / osc / joint on the emulator (emu_sim.EmuSim replaces the launch under each, nothing else):
-the product's output selection, result dictionary, single-frame convenience, choice between jaco_osc and jaco_osc_task, and defaults,
-against the emulated entries called directly.  jaco2_curtain_torque, two or three envs."""
+"""CPU tier: BatchedMujoco's own query / ik / osc / joint / rollout_cost / rollout_osc on the emulator (emu_sim.EmuSim replaces the launch
+under each, nothing else): the product's output selection, result dictionary, single-frame convenience, choice between jaco_osc and
+jaco_osc_task, and defaults, against the emulated entries called directly.  jaco2_curtain_torque, two or three envs."""
 import numpy as np
 import pytest
 import torch
@@ -10,7 +10,9 @@ import joint_binding as jb
 import osc_binding as ob
 import osc_task_binding as tb
 import query_binding as qb
-from emu_sim import EmuSim
+import rollout_cost_binding as cb
+import rollout_osc_binding as rob
+from emu_sim import EmuSim, _tensors
 
 MODEL = "jaco2_curtain_torque"
 
@@ -81,3 +83,33 @@ def test_joint_defaults(sim):
     assert same_bits(u, jb.joint(MODEL, q, v, t, tv, ff))
     assert same_bits(u, sim.joint(t, tv, ff, ctrl=torch.zeros(3, sim.nu)))
     assert sim.calls[-2:] == [{}, {}]
+
+
+def launched(s):
+    return {k: n for k, n in s.launches.items() if n}
+
+
+def test_rollout_cost_is_the_emulated_entry():
+    """2 rollouts x 2 knots x hold 1 of rollout_cost_binding.shared: every output bit for bit the entry's called directly, one launch."""
+    g = cb.shared(MODEL)
+    c, q, v, w = g["c"][:2, :2], g["q"][:2], g["v"][:2], g["weights"]
+    plan = {k: np.ascontiguousarray(g[k][:2, :2]) for k in ("noise", "gain", "xref", "xgoal", "pgoal")}
+    s = EmuSim(MODEL, q, v)
+    r = s.rollout_cost(c, q, v, noise=plan["noise"], gain=plan["gain"], x_ref=plan["xref"], dofs=g["dofs"], frame=g["ee"], x_goal=plan["xgoal"],
+                       p_goal=plan["pgoal"], wx=w["wx"], wx_final=w["wxT"], wu=w["wu"], wp=w["wp"], wp_final=w["wpT"], want=cb.OUTS)
+    raw = _tensors(cb.rollout_cost(MODEL, c, q, v, plan["noise"], plan["xgoal"], plan["pgoal"], w, 1, gain=plan["gain"], xref=plan["xref"], dofs=g["dofs"],
+                                   frame=g["ee"]))
+    assert set(r) == set(cb.OUTS) and all(same_bits(r[k], raw[k]) for k in cb.OUTS)
+    assert (r["status"] == 0).all() and torch.isfinite(r["cost"]).all() and launched(s) == {"jaco_rollout_cost": 1}
+
+
+def test_rollout_osc_is_the_emulated_entry():
+    """2 rollouts x 2 knots x hold 1 of rollout_osc_binding.shared: every output bit for bit the entry's called directly, one launch."""
+    g = rob.shared(MODEL)
+    q, v = g["q"][:2], g["v"][:2]
+    tp, tq, c = [np.ascontiguousarray(g[k][:2, :2]) for k in ("tp", "tq", "c")]
+    s = EmuSim(MODEL, q, v)
+    r = s.rollout_osc(g["frames"], tp, tq, q, v, ctrl=c, frame=g["ee"])
+    raw = _tensors(rob.rollout_osc(MODEL, g["frames"], tp, tq, c, q, v, frame=g["ee"]))
+    assert set(r) == set(rob.OUTS) and all(same_bits(r[k], raw[k]) for k in rob.OUTS)
+    assert (r["status"] == 0).all() and launched(s) == {"jaco_rollout_osc": 1}

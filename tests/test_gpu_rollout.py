@@ -53,24 +53,23 @@ def sims():
         s.close()
 
 
+_TORCH = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32}
+# the GPU tier of rollout_binding.prelude: device tensors, and one rollout's rows for n <= 0, so that no output pointer is NULL
+GPU = rb.Tier(lambda a, dtype: _dev(a, _TORCH[dtype]), lambda shape, value, dtype: torch.full(shape, value, dtype=_TORCH[dtype], device="cuda:0"),
+              lambda t: ctypes.c_void_p(t.data_ptr()), 1)
+
+
 def abi_call(sim, ctrl, qpos0=None, qvel0=None, state_index=None, nstates=None, frame=None, want=rb.OUTS, hold=1, final_only=0, n=None, nknots=None,
              no_opt=False, no_out=False, no_ctrl=False):
     """jaco_rollout straight through the C ABI on device tensors, the arguments of rollout_binding.rollout: (return code, {output: device
     tensor handed in filled with the sentinels}); for n <= 0 the outputs have one rollout's rows, so that their pointers are not NULL."""
-    c, q0, v0, idx = _dev(ctrl), _dev(qpos0), _dev(qvel0), _dev(state_index, torch.int32)
-    n = c.shape[0] if n is None else n
-    nknots = c.shape[1] if nknots is None else nknots
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else sim.num_envs)
-    sh = rb.shapes(max(n, 1), 1 if final_only == 1 else max(nknots, 1), sim.nq, sim.nv)
-    outs = {k: (torch.full(sh[k], rb.STATUS_SENTINEL, dtype=torch.int32, device="cuda:0") if k == "status" else torch.full(sh[k], rb.SENTINEL, device="cuda:0"))
-            for k in want}
-    vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-    rec = _lib.JacoRolloutOut(*[vp(outs.get(k)) for k in rb.OUTS])
+    p, ref = GPU.ptr, rb.ref
+    c, q0, v0, idx = GPU.f32(ctrl), GPU.f32(qpos0), GPU.f32(qvel0), GPU.i32(state_index)
+    n, nknots, nstates, outs = rb.prelude(GPU, (sim.nq, sim.nv, sim.nu), want, c.shape[0], c.shape[1], q0, v0, sim.num_envs, n=n, nknots=nknots, nstates=nstates,
+                                          hold=hold, final_only=final_only)
+    rec = _lib.JacoRolloutOut(*[p(outs.get(k)) for k in rb.OUTS])
     opt = _lib.JacoRolloutOptions(nknots=nknots, hold=hold, final_only=final_only)
-    rc = sim.L.jaco_rollout(sim.h, None if no_opt else ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p),
-                            None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p), n, vp(idx), nstates, vp(q0), vp(v0),
-                            None if no_ctrl else vp(c), None if no_out else ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p), sim._stream())
+    rc = sim.L.jaco_rollout(sim.h, ref(opt, no_opt), ref(frame), n, p(idx), nstates, p(q0), p(v0), None if no_ctrl else p(c), ref(rec, no_out), sim._stream())
     return rc, outs
 
 

@@ -12,17 +12,13 @@ The MPPI loops' cost ratios are the emulator's to three digits (tests/test_rollo
 Bit for bit, across the kernels' translation units: the degenerate call against jaco_rollout_fb, the noisy call against jaco_rollout
 on the summed ctrl, cost-only against every output and final_only, two runs, the fan-out against materialised plans.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import rollout_binding as rb
 import rollout_cost_binding as cb
-import rollout_fb_binding as fbb
-from mujoco_jaco_amd import _lib
-from test_gpu_rollout_fb import _blank, _dev, _host, abi_call as fb_abi_call
+from test_gpu_rollout_fb import GPU, _dev, _host, abi_call as fb_abi_call, run_open  # noqa: F401  (run_open: the fixture, jaco_rollout)
 
 pytestmark = pytest.mark.gpu
 COST_BOUND, TERMS_BOUND, CONFIG_BOUND, EMU_BOUND = 4.4e-7, 3.9e-7, 4.9e-7, 7.1e-7
@@ -52,20 +48,15 @@ def abi_call(sim, ctrl, qpos0=None, qvel0=None, noise=None, xgoal=None, pgoal=No
     """jaco_rollout_cost straight through the C ABI on device tensors, the arguments of rollout_cost_binding.rollout_cost: (return code,
     {output: device tensor handed in filled with the sentinels}); for n <= 0 the outputs have one rollout's rows, so that their pointers
     are not NULL."""
-    c, kf, G, X, al, q0, v0, eps, xg, pg = [_dev(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0, noise, xgoal, pgoal)]
-    pidx, sidx = _dev(plan_index, torch.int32), _dev(state_index, torch.int32)
-    if n is None:
-        n = fbb.count(c, al, pidx, sidx) if eps is None else eps.shape[0]
-    nknots = c.shape[1] if nknots is None else nknots
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else sim.num_envs)
-    outs = _blank(cb.shapes(max(n, 1), 1 if final_only == 1 else max(nknots, 1), max(nknots, 1), sim.nq, sim.nv, sim.nu), want)
-    vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-    opt, plan, goal, rec = cb.records(vp, outs, c, kf, G, X, al, pidx, eps, xg, pg, weights, dofs, nknots, hold, final_only, goal_per_knot,
+    p, ref = GPU.ptr, rb.ref
+    c, kf, G, X, al, q0, v0, eps, xg, pg = [GPU.f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0, noise, xgoal, pgoal)]
+    pidx, sidx = GPU.i32(plan_index), GPU.i32(state_index)
+    n, nknots, nstates, outs = rb.prelude(GPU, (sim.nq, sim.nv, sim.nu), want, c.shape[0], c.shape[1], q0, v0, sim.num_envs, (eps, pidx, sidx, al), n, nknots,
+                                          nstates, hold, final_only)
+    opt, plan, goal, rec = cb.records(p, outs, c, kf, G, X, al, pidx, eps, xg, pg, weights, dofs, nknots, hold, final_only, goal_per_knot,
                                       c.shape[0] if nplans is None else nplans, ndofs, no_ctrl)
-    rc = sim.L.jaco_rollout_cost(sim.h, None if no_opt else cast(opt), None if frame is None else cast(frame), n, vp(sidx), nstates, vp(q0), vp(v0),
-                                 None if no_plan else cast(plan), None if no_goal else cast(goal), None if no_out else cast(rec), sim._stream())
+    rc = sim.L.jaco_rollout_cost(sim.h, ref(opt, no_opt), ref(frame), n, p(sidx), nstates, p(q0), p(v0), ref(plan, no_plan), ref(goal, no_goal), ref(rec, no_out),
+                                 sim._stream())
     return rc, outs
 
 
@@ -90,23 +81,6 @@ def run(sims):
 @pytest.fixture(scope="module")
 def run_fb(sims):
     return _caller(sims, fb_abi_call)
-
-
-@pytest.fixture(scope="module")
-def run_open(sims):
-    def call(model, ctrl, qpos0, qvel0, state_index=None, frame=None, want=rb.OUTS, hold=1):
-        """jaco_rollout through the C ABI on device tensors."""
-        sim = sims(model, 2)
-        c, q0, v0, idx = _dev(ctrl), _dev(qpos0), _dev(qvel0), _dev(state_index, torch.int32)
-        outs = _blank(rb.shapes(c.shape[0], c.shape[1], sim.nq, sim.nv), want)
-        vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-        rec = _lib.JacoRolloutOut(*[vp(outs.get(k)) for k in rb.OUTS])
-        opt = _lib.JacoRolloutOptions(nknots=c.shape[1], hold=hold, final_only=0)
-        rc = sim.L.jaco_rollout(sim.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p),
-                                c.shape[0], vp(idx), q0.shape[0], vp(q0), vp(v0), vp(c), ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p), sim._stream())
-        assert rc == 0, sim.L.jaco_last_error(sim.h).decode()
-        return _host(outs)
-    return call
 
 
 @pytest.fixture(scope="module")

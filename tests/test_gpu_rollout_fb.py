@@ -11,26 +11,20 @@ The law against its fp64 recomputation: the derived bound of rollout_fb_binding.
 Bit for bit, across the two kernels' translation units: the degenerate call and the zero-deviation call against jaco_rollout, the
 closed loop against jaco_rollout on its own commands, the fan-out through the indices against materialised plans and states.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import rollout_binding as rb
 import rollout_fb_binding as fbb
-from mujoco_jaco_amd import _lib
 from mujoco_jaco_amd.physics import BatchedMujoco, JacoError
+from test_gpu_rollout import GPU, _dev, abi_call as open_abi_call
 
 pytestmark = pytest.mark.gpu
 ORACLE_BOUNDS = (1.2e-6, 8.5e-4, 2.8e-4)
 LONG_BOUNDS = (2.0e-7, 9.9e-5, 3.8e-5)
 EMU_BOUNDS = (1.9e-7, 3.0e-5, 1.3e-5)
 SETS = [(m, False) for m in (rb.MODEL,) + rb.SMALL] + [(rb.LONG_MODEL, True)]
-
-
-def _dev(a, dtype=torch.float32):
-    return None if a is None else torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda:0")
 
 
 def within(m, bounds):
@@ -51,34 +45,19 @@ def sims():
         s.close()
 
 
-def _blank(sh, want):
-    return {k: (torch.full(sh[k], rb.STATUS_SENTINEL, dtype=torch.int32, device="cuda:0") if k == "status" else torch.full(sh[k], rb.SENTINEL, device="cuda:0"))
-            for k in want}
-
-
 def abi_call(sim, ctrl, qpos0=None, qvel0=None, kff=None, gain=None, xref=None, dofs=(), alpha=None, plan_index=None, state_index=None, nstates=None,
              frame=None, want=fbb.OUTS, hold=1, final_only=0, per_substep=0, n=None, nknots=None, nplans=None, ndofs=None, no_opt=False, no_out=False,
              no_ctrl=False, no_plan=False):
     """jaco_rollout_fb straight through the C ABI on device tensors, the arguments of rollout_fb_binding.rollout_fb: (return code,
     {output: device tensor handed in filled with the sentinels}); for n <= 0 the outputs have one rollout's rows, so that their pointers
     are not NULL."""
-    c, kf, G, X, al, q0, v0 = [_dev(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0)]
-    pidx, sidx = _dev(plan_index, torch.int32), _dev(state_index, torch.int32)
-    n = fbb.count(c, al, pidx, sidx, n)
-    nknots = c.shape[1] if nknots is None else nknots
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else sim.num_envs)
-    sh = fbb.shapes(max(n, 1), 1 if final_only == 1 else max(nknots, 1), max(nknots, 1) * (max(hold, 1) if per_substep == 1 else 1), sim.nq, sim.nv, sim.nu)
-    outs = _blank(sh, want)
-    vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-    rec = _lib.JacoRolloutFbOut(*[vp(outs.get(k)) for k in fbb.OUTS])
-    opt = _lib.JacoRolloutFbOptions(nknots=nknots, hold=hold, final_only=final_only, per_substep=per_substep, dofs=dofs)
-    if ndofs is not None:
-        opt.ndofs = ndofs
-    plan = _lib.JacoRolloutPlan(None if no_ctrl else vp(c), vp(kf), vp(G), vp(X), vp(al), vp(pidx), c.shape[0] if nplans is None else nplans)
-    rc = sim.L.jaco_rollout_fb(sim.h, None if no_opt else cast(opt), None if frame is None else cast(frame), n, vp(sidx), nstates, vp(q0), vp(v0),
-                               None if no_plan else cast(plan), None if no_out else cast(rec), sim._stream())
+    p, ref = GPU.ptr, rb.ref
+    c, kf, G, X, al, q0, v0 = [GPU.f32(a) for a in (ctrl, kff, gain, xref, alpha, qpos0, qvel0)]
+    pidx, sidx = GPU.i32(plan_index), GPU.i32(state_index)
+    n, nknots, nstates, outs = rb.prelude(GPU, (sim.nq, sim.nv, sim.nu), want, c.shape[0], c.shape[1], q0, v0, sim.num_envs, (pidx, sidx, al), n, nknots, nstates,
+                                          hold, final_only, per_substep)
+    opt, plan, rec = fbb.records(p, outs, c, kf, G, X, al, pidx, dofs, nknots, hold, final_only, per_substep, c.shape[0] if nplans is None else nplans, ndofs, no_ctrl)
+    rc = sim.L.jaco_rollout_fb(sim.h, ref(opt, no_opt), ref(frame), n, p(sidx), nstates, p(q0), p(v0), ref(plan, no_plan), ref(rec, no_out), sim._stream())
     return rc, outs
 
 
@@ -105,13 +84,7 @@ def run_open(sims):
     def call(model, ctrl, qpos0, qvel0, state_index=None, frame=None, want=rb.OUTS, hold=1):
         """jaco_rollout through the C ABI on device tensors."""
         sim = sims(model, 2)
-        c, q0, v0, idx = _dev(ctrl), _dev(qpos0), _dev(qvel0), _dev(state_index, torch.int32)
-        outs = _blank(rb.shapes(c.shape[0], c.shape[1], sim.nq, sim.nv), want)
-        vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-        rec = _lib.JacoRolloutOut(*[vp(outs.get(k)) for k in rb.OUTS])
-        opt = _lib.JacoRolloutOptions(nknots=c.shape[1], hold=hold, final_only=0)
-        rc = sim.L.jaco_rollout(sim.h, ctypes.cast(ctypes.pointer(opt), ctypes.c_void_p), None if frame is None else ctypes.cast(ctypes.pointer(frame), ctypes.c_void_p),
-                                c.shape[0], vp(idx), q0.shape[0], vp(q0), vp(v0), vp(c), ctypes.cast(ctypes.pointer(rec), ctypes.c_void_p), sim._stream())
+        rc, outs = open_abi_call(sim, ctrl, qpos0, qvel0, state_index, frame=frame, want=want, hold=hold)
         assert rc == 0, sim.L.jaco_last_error(sim.h).decode()
         return _host(outs)
     return call

@@ -22,11 +22,9 @@ import pytest
 import torch
 
 import rollout_binding as rb
-import rollout_fb_binding as fbb
 import rollout_osc_binding as rob
-from mujoco_jaco_amd import _lib
 from mujoco_jaco_amd.physics import BatchedMujoco, JacoError
-from test_gpu_rollout_fb import _blank, _dev, _host, run_open, sims, within  # noqa: F401  (the fixtures: one handle per model and size, jaco_rollout)
+from test_gpu_rollout_fb import GPU, _dev, _host, run_open, sims, within  # noqa: F401  (the fixtures: one handle per model and size, jaco_rollout)
 
 pytestmark = pytest.mark.gpu
 ORACLE_BOUNDS = (1.2e-6, 9.1e-4, 3.9e-5, 2.5e-7)
@@ -43,22 +41,16 @@ def abi_call(sim, frames, target_pos, target_quat, ctrl=None, qpos0=None, qvel0=
     """jaco_rollout_osc straight through the C ABI on device tensors, the arguments of rollout_osc_binding.rollout_osc: (return code,
     {output: device tensor handed in filled with the sentinels}); for n <= 0 the outputs have one rollout's rows, so that their pointers
     are not NULL."""
-    tp, tq, c, q0, v0 = [_dev(a) for a in (target_pos, target_quat, ctrl, qpos0, qvel0)]
-    pidx, sidx = _dev(plan_index, torch.int32), _dev(state_index, torch.int32)
-    n = rob.count(tp.shape[0], pidx, sidx, n)
-    nknots = tp.shape[1] if nknots is None else nknots
-    if nstates is None:
-        nstates = q0.shape[0] if q0 is not None else (v0.shape[0] if v0 is not None else sim.num_envs)
-    sh = fbb.shapes(max(n, 1), 1 if final_only == 1 else max(nknots, 1), max(nknots, 1) * (max(hold, 1) if per_substep == 1 else 1), sim.nq, sim.nv, sim.nu)
-    outs = _blank(sh, want)
-    vp = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
-    cast = lambda s: ctypes.cast(ctypes.pointer(s), ctypes.c_void_p)
-    opt, arr, plan, rec = rob.records(vp, outs, frames, c, None if no_pos else tp, None if no_quat else tq, pidx, nknots, hold, final_only, per_substep,
+    p, ref = GPU.ptr, rb.ref
+    tp, tq, c, q0, v0 = [GPU.f32(a) for a in (target_pos, target_quat, ctrl, qpos0, qvel0)]
+    pidx, sidx = GPU.i32(plan_index), GPU.i32(state_index)
+    n, nknots, nstates, outs = rb.prelude(GPU, (sim.nq, sim.nv, sim.nu), want, tp.shape[0], tp.shape[1], q0, v0, sim.num_envs, (pidx, sidx), n, nknots, nstates,
+                                          hold, final_only, per_substep)
+    opt, arr, plan, rec = rob.records(p, outs, frames, c, None if no_pos else tp, None if no_quat else tq, pidx, nknots, hold, final_only, per_substep,
                                       tp.shape[0] if nplans is None else nplans, nframes, opt_nframes, **gains)
     nf = (0 if frames is None else len(frames)) if nframes is None else nframes
-    rc = sim.L.jaco_rollout_osc(sim.h, None if no_opt else cast(opt), None if arr is None else ctypes.cast(arr, ctypes.c_void_p), nf,
-                                None if frame is None else cast(frame), n, vp(sidx), nstates, vp(q0), vp(v0), None if no_plan else cast(plan),
-                                None if no_out else cast(rec), sim._stream())
+    rc = sim.L.jaco_rollout_osc(sim.h, ref(opt, no_opt), None if arr is None else ctypes.cast(arr, ctypes.c_void_p), nf, ref(frame), n, p(sidx), nstates, p(q0), p(v0),
+                                ref(plan, no_plan), ref(rec, no_out), sim._stream())
     return rc, outs
 
 

@@ -23,6 +23,7 @@ import pytest
 import rollout_binding as rb
 import rollout_cost_binding as cb
 import rollout_fb_binding as fbb
+from emu_sim import EmuSim
 
 COST_BOUND, TERMS_BOUND, CONFIG_BOUND = 4.7e-7, 3.5e-7, 4.5e-7
 SETS = [(m, False) for m in (rb.MODEL,) + rb.SMALL] + [(rb.LONG_MODEL, True)]
@@ -43,7 +44,7 @@ def run_open(model, ctrl, qpos0=None, qvel0=None, **k):
 
 
 def make_sim(model, q, v):
-    return cb.CostEmuSim(model, q, v)
+    return EmuSim(model, q, v)
 
 
 @pytest.mark.parametrize("model,long", SETS)

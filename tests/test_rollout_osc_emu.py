@@ -30,6 +30,7 @@ import emu_binding
 import osc_binding as ob
 import rollout_binding as rb
 import rollout_osc_binding as rob
+from emu_sim import EmuSim
 
 ORACLE_BOUNDS = (1.1e-6, 6.0e-4, 5.0e-5, 2.8e-7)
 LONG_BOUNDS = (1.2e-7, 2.2e-5, 5.2e-5, 2.3e-7)
@@ -67,7 +68,7 @@ def loop(model, frames, q, v, target_pos, target_quat, base):
 
 
 def make_sim(model, q, v):
-    return rob.OscEmuSim(model, q, v)
+    return EmuSim(model, q, v)
 
 
 def within(m, bounds):
