@@ -643,6 +643,65 @@ typedef struct JacoLqrProblem {      /* device pointers */
 typedef struct JacoLqrOut { float* gain; float* kff; float* dV; float* Vxx0; float* Vx0; uint32_t* status; } JacoLqrOut;
 int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream);
 
+/* ---- transition Jacobians of the rollout step: the A_t, B_t that jaco_lqr reads, from the very step the rollouts simulate.  MuJoCo's
+ * mjd_transitionFD: finite differences of the step function itself -- `hold` contact-free substeps with joint-limit rows, their
+ * warm-started Newton solve, the compensated Euler stage and the position update, exactly jaco_rollout's substep -- for n (state, ctrl)
+ * pairs in ONE kernel launch (mujoco_jaco_amd/csrc/transition.h).  n is NOT tied to num_envs: the typical input is every knot of every
+ * trajectory, straight from jaco_rollout_fb's outputs.
+ * Inputs (device, fp32): qpos_dev [n][nq] and qvel_dev [n][nv], given together or both NULL = the handle's fp32 state, and then
+ * n == num_envs; ctrl_dev [n][nu] (NULL = zeros).  An evaluation starts from a pair exactly as jaco_rollout starts from a state row (low
+ * words zero, zero warm start) and holds the ctrl row for `hold` substeps: the nominal evaluation is jaco_rollout(nknots = 1, hold) bit
+ * for bit.
+ * Coordinates, with nd = ndofs, nx = 2 nd, na = nacts:  x_j = qpos[qposadr(dofs[j])] for j < nd, qvel[dofs[j - nd]] for nd <= j < nx
+ * (jaco_rollout_fb's convention and limit);  u_a = ctrl[acts[a]].  Column c perturbs ONE word: x_c +- eps_qpos (c < nd), x_c +- eps_qvel
+ * (c < nx) or u_(c - nx) +- eps_ctrl, formed in fp32.
+ * THE INCREMENT FORM; this order of fp32 operations is part of the interface.  Every evaluation forms, for j < nx,
+ *   D_j = (x'_j.hi - x_j.start) + x'_j.lo
+ * x'.hi / x'.lo the compensated pair of the coordinate after the last substep, x_j.start the word the evaluation started from (the
+ * perturbed word where j is the perturbed coordinate) -- held as two fp32 words, so that the subtraction costs no rounding where it is
+ * not exact (a velocity that decays or changes sign):
+ *   D_j.hi = fl(x'_j.hi - x_j.start),   D_j.lo = e_j + x'_j.lo,   e_j = (x'_j.hi - x_j.start) - D_j.hi exactly (two-sum)
+ * Then, with H = D_r(+).hi - D_r(-).hi as two words (H.hi the fp32 difference, H.lo its exact rounding error) and
+ * L = H.lo + (D_r(+).lo - D_r(-).lo),
+ *   A[i][r][c] = (((r == c ? S.hi : 0.0f) + H.hi) + (L + (r == c ? S.lo : 0.0f))) * (1.0f / S.hi)
+ *   B[i][r][a] =                           (H.hi  +  L)                           * (1.0f / S.hi)
+ * S = c(+) - c(-) (u(+) - u(-)), the perturbed words as actually rounded: S.hi their fp32 difference, S.lo its exact rounding error.  The
+ * identity enters as the step itself, before the quotient: 1 + dD / step with dD / step near -1 (a strongly damped velocity) would keep
+ * roundings of the size of 1 in an entry near 0.  The reciprocal is the build's fp32 divide.  So an entry differs from the same quotient formed in fp64 from the high words that jaco_rollout returns by the low
+ * words, at most half a spacing of x' per side, the reciprocal and the roundings of dD and of the product -- nothing else.  Differencing
+ * the increments rather than the end states keeps the fp32 spacing of a joint angle (2.4e-7 .. 4.8e-7 at |q| in [2, 8)) from being
+ * divided by 2 eps.  With option "compensated" = 0 the x'.lo are zero and the quotient is that of the end states' words.
+ * centered = 0: forward differences, D_r(+) - D_r(0) over c(+) - c0, against the nominal.
+ * Outputs (device; each pointer of JacoTransitionOut may be NULL, at least one is required), in the layout jaco_lqr reads:
+ *   A [n][nx][nx], B [n][nx][na] fp32;
+ *   next_qpos [n][nq], next_qvel [n][nv]: the nominal's fp32 state after the `hold` substeps;
+ *   status [n] uint32: the nominal's JACO_FLAG_NAN / JACO_FLAG_SOLVER_MAXITER, as jaco_rollout reports them.  A perturbed evaluation that
+ *                 goes non-finite shows as a non-finite entry of its column; no status bit is defined for it.
+ * A ctrl word further than eps_ctrl beyond its limited ctrlrange gives a B column of exactly 0.0f (the actuators clamp both sides alike).
+ * groups: the columns of a pair are dealt to `groups` wavefronts (column c to c % groups); 0 = the library chooses from n.  No result
+ * depends on groups or on which outputs are asked for.
+ * Nothing of the handle is written.  Asynchronous on `stream`: one kernel launch (none for n == 0, which returns JACO_OK), no
+ * allocation, no synchronisation, no host copy; the options travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for NULL options; hold outside [1, JACO_TRANSITION_MAX_HOLD]; centered not 0 / 1; n < 0; a NULL
+ * out or all five outputs NULL; only one of qpos_dev / qvel_dev; n != num_envs with the handle's state; an eps that is not finite and
+ * positive; ndofs outside [1, JACO_ROLLOUT_FB_MAX_DOFS], a dof outside [0, nv), a dof of a free joint, a dof listed twice; nacts outside
+ * [0, JACO_ROLLOUT_FB_MAX_DOFS], a ctrl word outside [0, nu) or listed twice; B with nacts = 0; groups outside [0, 2 ndofs + nacts]. */
+#define JACO_TRANSITION_MAX_HOLD 1024
+typedef struct JacoTransitionOptions {
+  int32_t hold;                              /* substeps per evaluation, 1 .. JACO_TRANSITION_MAX_HOLD; 1 */
+  int32_t centered;                          /* 1: central differences; 0: forward differences against the nominal; 1 */
+  int32_t groups;                            /* wavefronts per pair, 1 .. 2 ndofs + nacts; 0: the library chooses; 0 */
+  int32_t ndofs;                             /* 1 .. JACO_ROLLOUT_FB_MAX_DOFS */
+  int32_t dofs[JACO_ROLLOUT_FB_MAX_DOFS];    /* distinct hinge dofs */
+  int32_t nacts;                             /* 0 .. JACO_ROLLOUT_FB_MAX_DOFS */
+  int32_t acts[JACO_ROLLOUT_FB_MAX_DOFS];    /* distinct ctrl words */
+  float eps_qpos, eps_qvel, eps_ctrl;        /* rad, rad/s, ctrl units: > 0, finite; 2^-8, 2^-3 (JACO_FD_DEFAULTS'), 2^-6 */
+  int32_t reserved;
+} JacoTransitionOptions;
+typedef struct JacoTransitionOut { float* A; float* B; float* next_qpos; float* next_qvel; uint32_t* status; } JacoTransitionOut;
+int jaco_transition_fd(JacoHandle* h, const JacoTransitionOptions* opt_host, int n, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
+                       const JacoTransitionOut* out, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

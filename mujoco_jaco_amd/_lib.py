@@ -219,6 +219,38 @@ class JacoRolloutOscPlan(ctypes.Structure):
                 ("nplans", ctypes.c_int32)]
 
 
+JACO_TRANSITION_MAX_HOLD = 1024
+
+
+class JacoTransitionOptions(ctypes.Structure):
+    """JacoTransitionOptions of include/jaco_env.h; a fresh instance holds hold = 1, centered = 1, groups = 0 (the library chooses), no
+    dofs, no ctrl words and the default steps.  dofs / acts: at most JACO_ROLLOUT_FB_MAX_DOFS hinge dofs / ctrl words each (ndofs and
+    nacts are their lengths; the library checks the entries themselves)."""
+    _fields_ = [("hold", ctypes.c_int32), ("centered", ctypes.c_int32), ("groups", ctypes.c_int32),
+                ("ndofs", ctypes.c_int32), ("dofs", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS),
+                ("nacts", ctypes.c_int32), ("acts", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS),
+                ("eps_qpos", ctypes.c_float), ("eps_qvel", ctypes.c_float), ("eps_ctrl", ctypes.c_float), ("reserved", ctypes.c_int32)]
+    DEFAULTS = dict(hold=1, centered=1, groups=0, dofs=(), acts=(), eps_qpos=JacoFdOptions.DEFAULTS["eps_qpos"], eps_qvel=JacoFdOptions.DEFAULTS["eps_qvel"],
+                    eps_ctrl=2.0 ** -6)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown transition option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        o = {**self.DEFAULTS, **options}
+        dofs, acts = [int(d) for d in o.pop("dofs")], [int(a) for a in o.pop("acts")]
+        for what, lst in (("dofs", dofs), ("ctrl words", acts)):
+            if len(lst) > JACO_ROLLOUT_FB_MAX_DOFS:
+                raise ValueError("%d %s: a transition Jacobian takes at most %d" % (len(lst), what, JACO_ROLLOUT_FB_MAX_DOFS))
+        super().__init__(ndofs=len(dofs), nacts=len(acts), **o)
+        self.dofs[:len(dofs)] = dofs
+        self.acts[:len(acts)] = acts
+
+
+class JacoTransitionOut(ctypes.Structure):
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("next_qpos", ctypes.c_void_p), ("next_qvel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 JACO_LQR_MAX_NX, JACO_LQR_MAX_NU = 36, 18
 JACO_LQR_BAD_INDEX = 0x80000   # jaco_lqr: the solve's problem index was outside [0, nprob); only its status word was written
 JACO_LQR_NOT_PD = 0x100000     # jaco_lqr: Quu + mu I not positive definite, or a non-finite number, at knot (status & 0xffff)
@@ -342,6 +374,7 @@ SYMBOLS = {
     "jaco_lqr": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
     "jaco_rollout_cost": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout_osc": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_transition_fd": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

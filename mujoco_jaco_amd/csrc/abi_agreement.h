@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h, rollout_cost.h and rollout_osc.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h, rollout_cost.h, rollout_osc.h and transition.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -105,3 +105,14 @@ static_assert(sizeof(JacoRolloutOscPlan) == sizeof(JacoRolloutOscTargets) && off
 static_assert(JACO_ROLLOUT_OSC_SINGULAR0 == JROLLOUT_OSC_SINGULAR0 && JACO_ROLLOUT_OSC_SINGULAR1 == (JROLLOUT_OSC_SINGULAR0 << 1) && JACO_OSC_MAX_FRAMES == 2 &&
                   (JACO_ROLLOUT_OSC_SINGULAR0 & (JACO_ROLLOUT_BAD_INDEX | JACO_FLAG_NAN | JACO_FLAG_SOLVER_MAXITER)) == 0 && offsetof(JacoRolloutOscArgs, R) == 0,
               "the singular bits of the public header and rollout_osc.h must agree and lie clear of the rollout's other status bits");
+static_assert(sizeof(JacoTransitionOptions) == sizeof(JacoTransitionOpts) && offsetof(JacoTransitionOptions, hold) == offsetof(JacoTransitionOpts, hold) &&
+                  offsetof(JacoTransitionOptions, centered) == offsetof(JacoTransitionOpts, centered) && offsetof(JacoTransitionOptions, groups) == offsetof(JacoTransitionOpts, groups) &&
+                  offsetof(JacoTransitionOptions, ndofs) == offsetof(JacoTransitionOpts, ndofs) && offsetof(JacoTransitionOptions, dofs) == offsetof(JacoTransitionOpts, dofs) &&
+                  offsetof(JacoTransitionOptions, nacts) == offsetof(JacoTransitionOpts, nacts) && offsetof(JacoTransitionOptions, acts) == offsetof(JacoTransitionOpts, acts) &&
+                  offsetof(JacoTransitionOptions, eps_qpos) == offsetof(JacoTransitionOpts, eps_qpos) && offsetof(JacoTransitionOptions, eps_qvel) == offsetof(JacoTransitionOpts, eps_qvel) &&
+                  offsetof(JacoTransitionOptions, eps_ctrl) == offsetof(JacoTransitionOpts, eps_ctrl) && JACO_TRANSITION_MAX_HOLD == JTRANSITION_MAX_HOLD,
+              "JacoTransitionOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoTransitionOut) == sizeof(JacoTransitionOutp) && offsetof(JacoTransitionOut, A) == offsetof(JacoTransitionOutp, A) &&
+                  offsetof(JacoTransitionOut, B) == offsetof(JacoTransitionOutp, B) && offsetof(JacoTransitionOut, next_qpos) == offsetof(JacoTransitionOutp, next_qpos) &&
+                  offsetof(JacoTransitionOut, next_qvel) == offsetof(JacoTransitionOutp, next_qvel) && offsetof(JacoTransitionOut, status) == offsetof(JacoTransitionOutp, status),
+              "JacoTransitionOut of the public header and the kernel's output record must agree");

@@ -1,5 +1,5 @@
-// From the C ABI's arguments to the kernel's argument block, for the eleven query-style entries (jaco_query, jaco_ik, jaco_osc,
-// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost, jaco_rollout_osc).  Host only: included by the library's host unit (jaco_env.hip)
+// From the C ABI's arguments to the kernel's argument block, for the twelve query-style entries (jaco_query, jaco_ik, jaco_osc,
+// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost, jaco_rollout_osc, jaco_transition_fd).  Host only: included by the library's host unit (jaco_env.hip)
 // and by the CPU tests' host build (tests/emu/emu_driver.cpp), after include/jaco_env.h, physics_kernel.h and abi_agreement.h -- the
 // public records are copied into the kernel-side records that restate them, which the feature headers (query.h ... rollout_fb.h)
 // cannot do: they do not see the public header.  kernels.hip does not include this file.
@@ -180,6 +180,17 @@ static inline std::string jaco_rollout_osc_bind(const JacoModelDev& m, const Jac
                                                    reinterpret_cast<const JacoRolloutOscTargets*>(plan), out != nullptr, Q);
   if (!why.empty()) return "jaco_rollout_osc: " + why;
   if (!Q->R.qpos0) { Q->R.qpos0 = state_qpos; Q->R.qvel0 = state_qvel; }
+  return why;
+}
+// (n pairs, not tied to num_envs; an accepted call with n = 0 launches nothing, which is the entry's to see to)
+static inline std::string jaco_transition_bind(const JacoModelDev& m, const JacoTransitionOptions* opt, int n, const float* qpos, const float* qvel, const float* ctrl,
+                                               const JacoTransitionOut* out, int num_envs, const float* state_qpos, const float* state_qvel, JacoTransitionArgs* Q) {
+  *Q = JacoTransitionArgs{};
+  Q->qpos = qpos; Q->qvel = qvel; Q->ctrl = ctrl;
+  if (out) { Q->A = out->A; Q->B = out->B; Q->next_qpos = out->next_qpos; Q->next_qvel = out->next_qvel; Q->status = out->status; }
+  const std::string why = jaco_transition_resolve(m, reinterpret_cast<const JacoTransitionOpts*>(opt), n, num_envs, out != nullptr, Q);
+  if (!why.empty()) return "jaco_transition_fd: " + why;
+  if (!Q->qpos) { Q->qpos = state_qpos; Q->qvel = state_qvel; }
   return why;
 }
 #endif   // JACO_ENTRY_ARGS_LQR_ONLY

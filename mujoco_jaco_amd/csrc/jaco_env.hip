@@ -1068,6 +1068,17 @@ extern "C" int jaco_rollout_osc(JacoHandle* h, const JacoRolloutOscOptions* opt_
   return launch_entry(h, jaco_launch_rollout_osc, n, stream, Q);
 }
 
+// transition Jacobians of the rollout step (transition.h): n (state, ctrl) pairs, the columns of each dealt to Q.groups wavefronts
+extern "C" int jaco_transition_fd(JacoHandle* h, const JacoTransitionOptions* opt_host, int n, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
+                                  const JacoTransitionOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoTransitionArgs Q;
+  if (refused(h, jaco_transition_bind(h->model_host, opt_host, n, qpos_dev, qvel_dev, ctrl_dev, out, h->num_envs, h->env.qpos, h->env.qvel, &Q))) return JACO_EINVAL;
+  if (n == 0) return JACO_OK;
+  Q.model = h->model_dev;
+  return launch_entry(h, jaco_launch_transition_fd, n * Q.groups, stream, Q);
+}
+
 // the iLQR / TVLQR backward pass (lqr.h): the whole recursion of every problem in one launch; the model is not read
 extern "C" int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream) {
   if (!h) return JACO_EINVAL;

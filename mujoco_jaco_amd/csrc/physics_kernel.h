@@ -2826,3 +2826,4 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #include "lqr.h"            // 17  jaco_lqr: the iLQR / TVLQR backward pass
 #include "rollout_cost.h"   // 18  jaco_rollout_cost: rollouts costed inside the kernel
 #include "rollout_osc.h"    // 19  jaco_rollout_osc: rollouts under the operational-space controller
+#include "transition.h"     // 20  jaco_transition_fd: transition Jacobians of the rollout step

@@ -583,6 +583,60 @@ class BatchedMujoco:
         return self._rollout_osc(list(frames), a["plan"], a["plan_index"], a["qpos"], a["qvel"], a["state_index"], a["nstates"], frame, want, a["n"],
                                  nknots=a["T"], hold=int(hold), final_only=int(bool(final_only)), per_substep=int(bool(per_substep)), **options)
 
+    # ---- transition Jacobians of the rollout step (jaco_transition_fd: finite differences of `hold` substeps over n pairs, one launch)
+    def _transition(self, ctrl, qpos, qvel, n, want, **options):
+        """One jaco_transition_fd launch: {name: tensor} of the outputs in `want` (names of JacoTransitionOut), in the C ABI's layout.
+        ctrl [n, nu] fp32 or None, qpos [n, nq] / qvel [n, nv] fp32 or None: contiguous device tensors; options: the keywords of
+        _lib.JacoTransitionOptions."""
+        nx, na = 2 * len(options["dofs"]), len(options["acts"])
+        shapes = {"A": (n, nx, nx), "B": (n, nx, na), "next_qpos": (n, self.nq), "next_qvel": (n, self.nv), "status": (n,)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=self.device) for k in want}
+        if n == 0:   # (no launch: the entry returns JACO_OK for n == 0)
+            return res
+        opt, out = _lib.JacoTransitionOptions(**options), _lib.JacoTransitionOut(*[_ptr(res.get(k)) for k in shapes])
+        self._chk(self.L.jaco_transition_fd(self.h, _ref(opt), int(n), _ptr(qpos), _ptr(qvel), _ptr(ctrl), _ref(out), self._stream()))
+        return res
+
+    def transition_fd(self, ctrl, qpos=None, qvel=None, dofs=(), acts=(), hold=1, centered=True, groups=None,
+                      eps_qpos=_lib.JacoTransitionOptions.DEFAULTS["eps_qpos"], eps_qvel=_lib.JacoTransitionOptions.DEFAULTS["eps_qvel"],
+                      eps_ctrl=_lib.JacoTransitionOptions.DEFAULTS["eps_ctrl"], want=("A", "B")):
+        """The transition Jacobians of the step the rollouts simulate -- mjd_transitionFD on `hold` contact-free substeps, joint-limit
+        rows and their warm-started solve included: x' = f(x, u), A = df/dx, B = df/du with x = [qpos at the hinge dofs `dofs`, qvel at
+        them] (rollout_feedback's convention) and u = ctrl at the words `acts`, by central (centered=False: forward) differences of
+        half-width eps_qpos / eps_qvel / eps_ctrl, formed on the increments of the compensated state (include/jaco_env.h states the
+        exact fp32 order).  ctrl [..., nu] (None: zeros) with qpos [..., nq] / qvel [..., nv] of the same leading shape (both, or neither:
+        the current state of the num_envs envs): the pairs are not tied to num_envs -- every knot of every trajectory, straight from
+        rollout_feedback's outputs.  groups: wavefronts per pair (None: the library chooses from the number of pairs).
+        Returns, for what `want` names: {"A": [..., nx, nx], "B": [..., nx, na]: the layout lqr_backward reads;  "next_qpos": [..., nq],
+        "next_qvel": [..., nv], "status": [...] int32: the nominal step, rollout(hold=hold)'s bits on one knot}.  One launch on the
+        current stream, no synchronisation; the sim's state is not touched."""
+        dev = self.device
+        known = ("A", "B", "next_qpos", "next_qvel", "status")
+        want = tuple(want)
+        if not want or set(want) - set(known):
+            raise ValueError("transition_fd: want %s names none or not only outputs (%s)" % (want, ", ".join(known)))
+        given = [(name, torch.as_tensor(t, dtype=torch.float32, device=dev), width) for name, t, width in
+                 (("ctrl", ctrl, self.nu), ("qpos", qpos, self.nq), ("qvel", qvel, self.nv)) if t is not None]
+        lead = None
+        for name, t, width in given:
+            if t.dim() < 1 or t.shape[-1] != width:
+                raise ValueError("transition_fd: %s has shape %s, not [..., %d]" % (name, tuple(t.shape), width))
+            if lead is not None and tuple(t.shape[:-1]) != lead:
+                raise ValueError("transition_fd: %s has the leading shape %s, not %s" % (name, tuple(t.shape[:-1]), lead))
+            lead = tuple(t.shape[:-1])
+        if (qpos is None) != (qvel is None):
+            raise ValueError("transition_fd: qpos and qvel are given together or not at all")
+        if lead is None or qpos is None:
+            if lead not in (None, (self.num_envs,)):
+                raise ValueError("transition_fd: ctrl has the leading shape %s, but the current state has %d envs" % (lead, self.num_envs))
+            lead = (self.num_envs,)
+        n = int(np.prod(lead, dtype=np.int64))
+        c, q, v = (_rows(t, dev, width) for t, width in ((ctrl, self.nu), (qpos, self.nq), (qvel, self.nv)))
+        r = self._transition(c, q, v, n, want, dofs=tuple(int(d) for d in dofs), acts=tuple(int(a) for a in acts), hold=int(hold),
+                             centered=int(bool(centered)), groups=0 if groups is None else int(groups), eps_qpos=float(eps_qpos), eps_qvel=float(eps_qvel),
+                             eps_ctrl=float(eps_ctrl))
+        return {k: t.reshape(lead + tuple(t.shape[1:])) for k, t in r.items()}
+
     # ---- the iLQR / TVLQR backward pass (jaco_lqr: the whole recursion of every problem in one launch)
     def _lqr(self, opt, prob, out, n):
         """One jaco_lqr launch.  opt: the keywords of _lib.JacoLqrOptions; prob: {field of JacoLqrProblem: contiguous device tensor or

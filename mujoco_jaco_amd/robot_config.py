@@ -409,6 +409,48 @@ class BatchedMujocoConfig:
         out["status"] = r["status"].reshape(B, A)
         return {key: t[:, 0] for key, t in out.items()} if alphas is None else out
 
+    def linearize_rollout(self, u, K=None, x_ref=None, k=None, alpha=None, joints=None, ctrl=None, q=None, dq=None, hold=1, **steps):
+        """The trajectory of rollout_feedback's plan and the transition Jacobians of every knot of it, of the very step the rollouts
+        simulate (`hold` substeps, joint-limit rows included) -- what one iLQR iteration linearises: the arguments are rollout_feedback's
+        (alpha: one step size, a scalar or [B]; needs k), on the joints and motor words linearize(joints=...) uses.
+        (A [B, T, 2 n, 2 n], Bm [B, T, 2 n, m], x [B, T + 1, 2 n], u_applied [B, T, m], status [B]):  x_(t+1) ~ x_(t+1) + A_t dx_t + Bm_t du_t
+        about the trajectory x (x[:, 0] the start) under the applied motor words u_applied; A and Bm go straight into ilqr_backward, x and
+        u_applied into rollout_feedback(..., alphas=) as x_ref and u.  Two launches on this handle: one rollout_feedback for the full state
+        and applied ctrl of every knot, one transition_fd over the B * T (state at the start of knot t, applied ctrl of knot t) pairs;
+        steps: eps_qpos, eps_qvel, eps_ctrl, centered, groups.  The sim's state is not touched."""
+        import torch
+        sim = self.sim
+        B, dev, nu = sim.num_envs, sim.device, sim.nu
+        dofs, qadr, acts = self._joint_subset(joints, "linearize_rollout")
+        n, m = len(dofs), len(acts)
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+        u, K, x_ref, k = f32(u), f32(K), f32(x_ref), f32(k)
+        if u.dim() != 3 or u.shape[0] != B or u.shape[2] != m:
+            raise ValueError("linearize_rollout: u has shape %s, not [%d, T, %d]" % (tuple(u.shape), B, m))
+        T = int(u.shape[1])
+        if alpha is not None and k is None:
+            raise ValueError("linearize_rollout: alpha needs k")
+        base = torch.zeros(B, nu, dtype=torch.float32, device=dev) if ctrl is None else f32(ctrl).reshape(B, nu)
+        full = base[:, None, :].repeat(1, T, 1)
+        full[:, :, acts] = u
+        kff = gain = None
+        if k is not None:
+            kff = torch.zeros_like(full)
+            kff[:, :, acts] = k
+        if K is not None:
+            gain = torch.zeros(B, T, nu, 2 * n, dtype=torch.float32, device=dev)
+            gain[:, :, acts] = K
+        if alpha is not None:
+            alpha = f32(alpha).reshape(-1).expand(B).contiguous()
+        qpos, qvel = self._spliced(q, dq)
+        r = sim.rollout_feedback(full, qpos, qvel, gain=gain, x_ref=x_ref, dofs=dofs, feedforward=kff, alpha=alpha, hold=hold)
+        if qpos is None:
+            qpos, qvel, _ = sim.get_state()
+        Q, V = torch.cat([qpos[:, None], r["qpos"]], 1), torch.cat([qvel[:, None], r["qvel"]], 1)   # [B, T + 1, ..]: the state at the start of every knot, and the end
+        lin = sim.transition_fd(r["ctrl"], Q[:, :T].contiguous(), V[:, :T].contiguous(), dofs=dofs, acts=acts, hold=hold, want=("A", "B") if acts else ("A",), **steps)
+        Bm = lin["B"] if acts else torch.zeros(B, T, 2 * n, 0, dtype=torch.float32, device=dev)   # (no motor on the chosen joints: as linearize, no column)
+        return lin["A"], Bm, torch.cat([Q[..., qadr], V[..., dofs]], 2), r["ctrl"][..., acts], r["status"]
+
     def rollout_cost(self, u, noise=None, K=None, x_ref=None, k=None, alphas=None, joints=None, q_goal=None, dq_goal=None, ee_goal=None, w_q=0.0,
                      w_dq=0.0, w_ee=0.0, w_u=0.0, w_q_final=None, w_dq_final=None, w_ee_final=None, ctrl=None, hold=1, q=None, dq=None,
                      trajectories=False):
