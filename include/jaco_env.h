@@ -702,6 +702,66 @@ typedef struct JacoTransitionOut { float* A; float* B; float* next_qpos; float* 
 int jaco_transition_fd(JacoHandle* h, const JacoTransitionOptions* opt_host, int n, const float* qpos_dev, const float* qvel_dev, const float* ctrl_dev,
                        const JacoTransitionOut* out, void* stream);
 
+/* ---- the quadratic expansion of jaco_rollout_cost's cost along trajectories: the lx, lxx, lu, Vx, Vxx that jaco_lqr reads, for R
+ * trajectories of T = nknots knots in ONE kernel launch (mujoco_jaco_amd/csrc/cost_quad.h).  R is NOT tied to num_envs and nothing of
+ * the handle but its model is read.
+ * Inputs (device, fp32), exactly what jaco_rollout_fb / jaco_rollout_cost write: qpos_dev [R][T][nq], qvel_dev [R][T][nv]: the state
+ * AFTER knot k, x_(k+1);  ctrl_dev [R][T][nu]: the commanded row of knot k (NULL = zeros).  The start state x_0 is not an input:
+ * jaco_rollout_cost does not cost it, so its expansion is zero.
+ * Coordinates, with nd = ndofs, nx = 2 nd, na = nacts: x_j = qpos[qposadr(dofs[j])] for j < nd, qvel[dofs[j - nd]] for nd <= j < nx
+ * (jaco_rollout_fb's convention);  u_a = ctrl[acts[a]].  wu[a] weighs u_a: it is indexed by the position in acts, where
+ * JacoRolloutCostOptions.wu is indexed by the ctrl word.
+ * Goals (JacoCostQuadGoal, device): xgoal [ngoals][G][nx], pgoal [ngoals][G][3], G = goal_per_knot ? T : 1; trajectory r takes goal
+ * goal_idx[r] (goal_idx NULL: goal r).  Without a state and a pose weight no goal is read and the record may be NULL.
+ * THE COST EXPANDED is jaco_rollout_cost's, term for term, re-indexed to jaco_lqr's convention: l_t(x_t, u_t) for t = 0 .. T - 1 plus a
+ * terminal cost on x_T.  Work item (r, k):  x = x_(k+1), pos = the position of frame_host's ORIGIN at that state (the point
+ * jaco_rollout's xpos reports and the cost uses; JacoFrame.point is ignored), g = goal_per_knot ? k : 0, (W, Wp) = (wx, wp) for
+ * k < T - 1 and (wxT, wpT) for k = T - 1,
+ *   d_j = x_j - xgoal[.][g][j]   (not wrapped),      e_c = pos_c - pgoal[.][g][c],
+ *   Jp [3][nd]: column j the translational Jacobian of dof dofs[j] at pos, exactly 0 where the frame's body is not on that dof's chain
+ *               -- jaco_query's jac rows 0 .. 2 for the same frame with point = 0, composed by the same expressions,
+ *   gx_j = W_j d_j + [j < nd] Wp sum_c Jp[c][j] e_c,      H_ji = delta_ji W_j + [j, i < nd] Wp sum_c Jp[c][j] Jp[c][i].
+ * GAUSS-NEWTON: the pose term's second-order part, e . d2pos/dq2, is dropped, as every iLQR does; H is positive semi-definite.
+ * Outputs (device; each pointer of JacoCostQuadOut may be NULL, at least one is required), in the layout jaco_lqr reads:
+ *   lx [R][T][nx], lxx [R][T][nx][nx]: row 0 exact zeros (written by item k = 0), row k + 1 = gx, H of item k for k < T - 1;
+ *   Vx [R][nx], Vxx [R][nx][nx]: gx, H of item k = T - 1 (the final weights);
+ *   lu [R][T][na]: lu_a = wu[a] * u_a of knot k.  luu is the constant diag(wu) and lux is zero: neither is written (hand luu to jaco_lqr
+ *                  once, through shared_knots | shared_probs, and leave lux NULL);
+ *   l [R][T]: knot k's own summand of jaco_rollout_cost's cost, 1/2 sum_a wu[a] u_a^2 + 1/2 sum_j W_j d_j^2 + 1/2 Wp |e|^2; its sum over k
+ *             is that rollout's cost to rounding;
+ *   status [R][T] uint32: JACO_FLAG_NAN where a word of the item's qpos / qvel / ctrl rows, a goal word it reads or a result is not
+ *             finite; JACO_ROLLOUT_BAD_INDEX for a goal_idx entry outside [0, ngoals), and that item writes nothing else.
+ * fp32 order that is part of the interface: where Wp == 0, gx_j = W_j * (x_j - xgoal_j), one subtraction and one multiplication (0.0f
+ * where no state weight is set at all); always lu_a = wu[a] * u_a; lxx and Vxx are symmetric bit for bit (H_ji and H_ij are one fmaf
+ * chain over c on commuted products); the cross blocks between positions and velocities and the off-diagonal velocity entries are
+ * exactly 0.0f.  Two runs of the same call agree bit for bit, and no output depends on which others are asked for.
+ * Asynchronous on `stream`: one kernel launch (none for R == 0, which returns JACO_OK), no allocation, no synchronisation, no host copy,
+ * nothing of the handle written; the options, the frame and the goal record travel in the kernel arguments.
+ * JACO_EINVAL, with no output touched, for NULL options or out, or all seven outputs NULL; R < 0; nknots < 1; goal_per_knot not 0 / 1;
+ * R x nknots beyond 2^31 - 1; ndofs outside [1, JACO_ROLLOUT_FB_MAX_DOFS], a dof outside [0, nv), of a free joint or listed twice; nacts
+ * outside [0, JACO_ROLLOUT_FB_MAX_DOFS], a ctrl word outside [0, nu) or listed twice; only one of qpos_dev / qvel_dev; a weight that is
+ * negative or not finite (every word of wx, wxT and wu is checked; the state weights behind the first 2 ndofs are otherwise not used); a
+ * non-zero state weight without xgoal; a non-zero pose weight without pgoal, without a frame or with a frame that is world-fixed or on
+ * no body of the model; lu with nacts = 0; a non-zero state or pose weight with qpos_dev or qvel_dev NULL, with ngoals < 1, or with
+ * R > ngoals and no goal_idx. */
+typedef struct JacoCostQuadOptions {
+  int32_t nknots;                            /* T >= 1 */
+  int32_t goal_per_knot;                     /* 0: one goal per goal row; 1: one per goal row and knot */
+  int32_t ndofs;                             /* 1 .. JACO_ROLLOUT_FB_MAX_DOFS */
+  int32_t dofs[JACO_ROLLOUT_FB_MAX_DOFS];    /* distinct hinge dofs */
+  int32_t nacts;                             /* 0 .. JACO_ROLLOUT_FB_MAX_DOFS */
+  int32_t acts[JACO_ROLLOUT_FB_MAX_DOFS];    /* distinct ctrl words */
+  float wx[2 * JACO_ROLLOUT_FB_MAX_DOFS];    /* state weights of the knots k < T - 1; finite, >= 0 */
+  float wxT[2 * JACO_ROLLOUT_FB_MAX_DOFS];   /* state weights of the last knot */
+  float wu[JACO_ROLLOUT_FB_MAX_DOFS];        /* ctrl weights, by position in acts */
+  float wp, wpT;                             /* pose weights: running, last knot */
+  int32_t reserved;
+} JacoCostQuadOptions;
+typedef struct JacoCostQuadGoal { const float* xgoal; const float* pgoal; const int32_t* goal_idx; int32_t ngoals; } JacoCostQuadGoal;   /* device pointers */
+typedef struct JacoCostQuadOut { float* lx; float* lxx; float* lu; float* Vx; float* Vxx; float* l; uint32_t* status; } JacoCostQuadOut;
+int jaco_cost_quad(JacoHandle* h, const JacoCostQuadOptions* opt_host, const JacoFrame* frame_host, int R, const float* qpos_dev, const float* qvel_dev,
+                   const float* ctrl_dev, const JacoCostQuadGoal* goal_host, const JacoCostQuadOut* out, void* stream);
+
 /* ---- contact readout: data.contact and mj_contactForce / efc_force (what the reference reads through sim.data.contact), batched.
  * jaco_set_contact_record turns the record on: from then on every jaco_physics_step (any nsub) and jaco_step writes, for every env, the
  * contacts of the LAST INTEGRATING SUBSTEP of that call -- those of the forward pass at the start of that substep, which is what

@@ -251,6 +251,49 @@ class JacoTransitionOut(ctypes.Structure):
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("next_qpos", ctypes.c_void_p), ("next_qvel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class JacoCostQuadOptions(ctypes.Structure):
+    """JacoCostQuadOptions of include/jaco_env.h; a fresh instance holds goal_per_knot = 0, no dofs, no ctrl words and zero weights
+    (nknots has no default: it is the trajectories' knot count).  dofs / acts: at most JACO_ROLLOUT_FB_MAX_DOFS hinge dofs / ctrl words;
+    wx / wxT: at most 2 x that many state weights (running / last knot), wu: one weight per entry of acts, each zero-filled to its
+    array's length; wp / wpT: the pose weights."""
+    _fields_ = [("nknots", ctypes.c_int32), ("goal_per_knot", ctypes.c_int32),
+                ("ndofs", ctypes.c_int32), ("dofs", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS),
+                ("nacts", ctypes.c_int32), ("acts", ctypes.c_int32 * JACO_ROLLOUT_FB_MAX_DOFS),
+                ("wx", ctypes.c_float * (2 * JACO_ROLLOUT_FB_MAX_DOFS)), ("wxT", ctypes.c_float * (2 * JACO_ROLLOUT_FB_MAX_DOFS)),
+                ("wu", ctypes.c_float * JACO_ROLLOUT_FB_MAX_DOFS), ("wp", ctypes.c_float), ("wpT", ctypes.c_float), ("reserved", ctypes.c_int32)]
+    DEFAULTS = dict(nknots=0, goal_per_knot=0, dofs=(), acts=(), wx=(), wxT=(), wu=(), wp=0.0, wpT=0.0)
+
+    def __init__(self, **options):
+        unknown = set(options) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown cost expansion option(s) %s: the options are %s" % (sorted(unknown), sorted(self.DEFAULTS)))
+        o = {**self.DEFAULTS, **options}
+        dofs, acts = [int(d) for d in o.pop("dofs")], [int(a) for a in o.pop("acts")]
+        for what, lst in (("dofs", dofs), ("ctrl words", acts)):
+            if len(lst) > JACO_ROLLOUT_FB_MAX_DOFS:
+                raise ValueError("%d %s: a cost expansion takes at most %d" % (len(lst), what, JACO_ROLLOUT_FB_MAX_DOFS))
+        arrays = {k: [float(w) for w in o.pop(k)] for k in ("wx", "wxT", "wu")}
+        for k, w in arrays.items():
+            if len(w) > len(getattr(self, k)):
+                raise ValueError("%d weights in %s: a cost expansion takes at most %d" % (len(w), k, len(getattr(self, k))))
+        super().__init__(ndofs=len(dofs), nacts=len(acts), **o)
+        self.dofs[:len(dofs)] = dofs
+        self.acts[:len(acts)] = acts
+        for k, w in arrays.items():
+            getattr(self, k)[:len(w)] = w
+
+
+class JacoCostQuadGoal(ctypes.Structure):
+    _fields_ = [("xgoal", ctypes.c_void_p), ("pgoal", ctypes.c_void_p), ("goal_idx", ctypes.c_void_p), ("ngoals", ctypes.c_int32)]
+    DEFAULTS = dict(xgoal=None, pgoal=None, goal_idx=None, ngoals=0)
+
+
+class JacoCostQuadOut(ctypes.Structure):
+    _fields_ = [("lx", ctypes.c_void_p), ("lxx", ctypes.c_void_p), ("lu", ctypes.c_void_p), ("Vx", ctypes.c_void_p), ("Vxx", ctypes.c_void_p),
+                ("l", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+    DEFAULTS = dict.fromkeys(("lx", "lxx", "lu", "Vx", "Vxx", "l", "status"))
+
+
 JACO_LQR_MAX_NX, JACO_LQR_MAX_NU = 36, 18
 JACO_LQR_BAD_INDEX = 0x80000   # jaco_lqr: the solve's problem index was outside [0, nprob); only its status word was written
 JACO_LQR_NOT_PD = 0x100000     # jaco_lqr: Quu + mu I not positive definite, or a non-finite number, at knot (status & 0xffff)
@@ -375,6 +418,7 @@ SYMBOLS = {
     "jaco_rollout_cost": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_rollout_osc": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "jaco_transition_fd": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "jaco_cost_quad": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jaco_set_contact_record": (_ci, [_vp, _vp, _vp, _ci]),
     "jaco_snapshot_words": (_ci, [_vp]),
     "jaco_save_envs": (_ci, [_vp, _vp, _ci, _vp, _vp]),

@@ -1,5 +1,5 @@
 // The agreement between the public header (include/jaco_env.h) and the kernel-side records and constants that restate it, field by
-// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h, rollout_cost.h, rollout_osc.h and transition.h) and snapshot.h.  The library's host unit
+// field.  Include it after both sides: jaco_env.h, physics_kernel.h (with query.h, ik.h, osc.h, osc_task.h, joint.h, fd.h, rollout.h, rollout_fb.h, lqr.h, rollout_cost.h, rollout_osc.h, transition.h and cost_quad.h) and snapshot.h.  The library's host unit
 // (jaco_env.hip) and the CPU tests' host build (tests/emu/emu_driver.cpp) both do.
 #pragma once
 #include <cstddef>
@@ -116,3 +116,20 @@ static_assert(sizeof(JacoTransitionOut) == sizeof(JacoTransitionOutp) && offseto
                   offsetof(JacoTransitionOut, B) == offsetof(JacoTransitionOutp, B) && offsetof(JacoTransitionOut, next_qpos) == offsetof(JacoTransitionOutp, next_qpos) &&
                   offsetof(JacoTransitionOut, next_qvel) == offsetof(JacoTransitionOutp, next_qvel) && offsetof(JacoTransitionOut, status) == offsetof(JacoTransitionOutp, status),
               "JacoTransitionOut of the public header and the kernel's output record must agree");
+#define JACO_ABI_SAME(A, B, f) (offsetof(A, f) == offsetof(B, f))
+static_assert(sizeof(JacoCostQuadOptions) == sizeof(JacoCostQuadOpts) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, nknots) &&
+                  JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, goal_per_knot) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, ndofs) &&
+                  JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, dofs) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, nacts) &&
+                  JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, acts) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, wx) &&
+                  JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, wxT) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, wu) &&
+                  JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, wp) && JACO_ABI_SAME(JacoCostQuadOptions, JacoCostQuadOpts, wpT),
+              "JacoCostQuadOptions of the public header and the kernel's option record must agree");
+static_assert(sizeof(JacoCostQuadGoal) == sizeof(JacoCostQuadGoals) && JACO_ABI_SAME(JacoCostQuadGoal, JacoCostQuadGoals, xgoal) &&
+                  JACO_ABI_SAME(JacoCostQuadGoal, JacoCostQuadGoals, pgoal) && JACO_ABI_SAME(JacoCostQuadGoal, JacoCostQuadGoals, goal_idx) &&
+                  JACO_ABI_SAME(JacoCostQuadGoal, JacoCostQuadGoals, ngoals),
+              "JacoCostQuadGoal of the public header and the kernel's goal record must agree");
+static_assert(sizeof(JacoCostQuadOut) == sizeof(JacoCostQuadOutp) && JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, lx) && JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, lxx) &&
+                  JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, lu) && JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, Vx) && JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, Vxx) &&
+                  JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, l) && JACO_ABI_SAME(JacoCostQuadOut, JacoCostQuadOutp, status),
+              "JacoCostQuadOut of the public header and the kernel's output record must agree");
+#undef JACO_ABI_SAME

@@ -1,5 +1,5 @@
-// From the C ABI's arguments to the kernel's argument block, for the twelve query-style entries (jaco_query, jaco_ik, jaco_osc,
-// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost, jaco_rollout_osc, jaco_transition_fd).  Host only: included by the library's host unit (jaco_env.hip)
+// From the C ABI's arguments to the kernel's argument block, for the thirteen query-style entries (jaco_query, jaco_ik, jaco_osc,
+// jaco_osc_task, jaco_joint, jaco_fd, jaco_rollout, jaco_rollout_fb, jaco_lqr, jaco_rollout_cost, jaco_rollout_osc, jaco_transition_fd, jaco_cost_quad).  Host only: included by the library's host unit (jaco_env.hip)
 // and by the CPU tests' host build (tests/emu/emu_driver.cpp), after include/jaco_env.h, physics_kernel.h and abi_agreement.h -- the
 // public records are copied into the kernel-side records that restate them, which the feature headers (query.h ... rollout_fb.h)
 // cannot do: they do not see the public header.  kernels.hip does not include this file.
@@ -192,5 +192,15 @@ static inline std::string jaco_transition_bind(const JacoModelDev& m, const Jaco
   if (!why.empty()) return "jaco_transition_fd: " + why;
   if (!Q->qpos) { Q->qpos = state_qpos; Q->qvel = state_qvel; }
   return why;
+}
+// (R trajectories of opt->nknots knots, not tied to num_envs and reading nothing of a handle; R = 0 launches nothing, the entry's to see to)
+static inline std::string jaco_cost_quad_bind(const JacoModelDev& m, const JacoCostQuadOptions* opt, const JacoFrame* frame, int R, const float* qpos, const float* qvel,
+                                              const float* ctrl, const JacoCostQuadGoal* goal, const JacoCostQuadOut* out, JacoCostQuadArgs* Q) {
+  *Q = JacoCostQuadArgs{};
+  Q->qpos = qpos; Q->qvel = qvel; Q->ctrl = ctrl;
+  if (out) Q->out = *reinterpret_cast<const JacoCostQuadOutp*>(out);
+  const std::string why = jaco_cost_quad_resolve(m, reinterpret_cast<const JacoCostQuadOpts*>(opt), reinterpret_cast<const JacoQueryFrame*>(frame), R,
+                                                 reinterpret_cast<const JacoCostQuadGoals*>(goal), out != nullptr, Q);
+  return why.empty() ? why : "jaco_cost_quad: " + why;
 }
 #endif   // JACO_ENTRY_ARGS_LQR_ONLY

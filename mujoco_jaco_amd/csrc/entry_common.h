@@ -1,7 +1,8 @@
 // What the query-style entries (query.h .. rollout_fb.h) share: the frame record and its pose, the state load, the forward pass made of
 // the step kernel's own stages, row `lane` of the mass matrix, a wave OR, and the kernel / launcher definition.
-// WHO CALLS THE FUNCTIONS BELOW: run_osc_task, run_joint, run_fd (fd_pass), run_rollout (both rollout kernels) and run_transition
-// (entry_walk, wave_or and the entry macro; its restore of a pair is written out in transition.h).  Among those, "the same
+// WHO CALLS THE FUNCTIONS BELOW: run_osc_task, run_joint, run_fd (fd_pass), run_rollout (both rollout kernels), run_transition
+// (entry_walk, wave_or and the entry macro; its restore of a pair is written out in transition.h) and run_cost_quad (entry_state, entry_walk,
+// frame_pose, wave_or).  Among those, "the same
 // prologue", "the same forward pass", "run_rollout's loop" hold by construction.
 // WHO DOES NOT: run_query, run_ik and run_osc keep prologue, forward pass and pose written out in their own headers, because built on
 // these functions their kernels measured slower on the MI355X.  For them entry_state, entry_forward and body_frame_pose are

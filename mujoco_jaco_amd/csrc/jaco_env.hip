@@ -1079,6 +1079,17 @@ extern "C" int jaco_transition_fd(JacoHandle* h, const JacoTransitionOptions* op
   return launch_entry(h, jaco_launch_transition_fd, n * Q.groups, stream, Q);
 }
 
+// the quadratic expansion of jaco_rollout_cost's cost along trajectories (cost_quad.h): one work item per trajectory and knot
+extern "C" int jaco_cost_quad(JacoHandle* h, const JacoCostQuadOptions* opt_host, const JacoFrame* frame_host, int R, const float* qpos_dev, const float* qvel_dev,
+                              const float* ctrl_dev, const JacoCostQuadGoal* goal_host, const JacoCostQuadOut* out, void* stream) {
+  if (!h) return JACO_EINVAL;
+  JacoCostQuadArgs Q;
+  if (refused(h, jaco_cost_quad_bind(h->model_host, opt_host, frame_host, R, qpos_dev, qvel_dev, ctrl_dev, goal_host, out, &Q))) return JACO_EINVAL;
+  if (R == 0) return JACO_OK;
+  Q.model = h->model_dev;
+  return launch_entry(h, jaco_launch_cost_quad, R * Q.T, stream, Q);
+}
+
 // the iLQR / TVLQR backward pass (lqr.h): the whole recursion of every problem in one launch; the model is not read
 extern "C" int jaco_lqr(JacoHandle* h, const JacoLqrOptions* opt_host, int n, const JacoLqrProblem* prob_host, const JacoLqrOut* out, void* stream) {
   if (!h) return JACO_EINVAL;

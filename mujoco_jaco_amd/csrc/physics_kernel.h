@@ -2827,3 +2827,4 @@ JACO_DEFINE_LAUNCHER(8, jaco_physics_kernel_arm)
 #include "rollout_cost.h"   // 18  jaco_rollout_cost: rollouts costed inside the kernel
 #include "rollout_osc.h"    // 19  jaco_rollout_osc: rollouts under the operational-space controller
 #include "transition.h"     // 20  jaco_transition_fd: transition Jacobians of the rollout step
+#include "cost_quad.h"      // 21  jaco_cost_quad: the quadratic expansion of jaco_rollout_cost's cost along trajectories

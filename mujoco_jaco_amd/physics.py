@@ -637,6 +637,89 @@ class BatchedMujoco:
                              eps_ctrl=float(eps_ctrl))
         return {k: t.reshape(lead + tuple(t.shape[1:])) for k, t in r.items()}
 
+    # ---- the quadratic expansion of rollout_cost's cost along trajectories (jaco_cost_quad: R x T work items, one launch)
+    def _cost_quad(self, qpos, qvel, ctrl, goal, frame, R, T, want, **options):
+        """One jaco_cost_quad launch: {name: tensor} of the outputs in `want` (names of JacoCostQuadOut), in the C ABI's layout.  qpos
+        [R, T, nq] / qvel [R, T, nv] / ctrl [R, T, nu] fp32 or None; goal: {"xgoal": [P, G, nx], "pgoal": [P, G, 3], "goal_idx": [R] int32:
+        tensors or None, "ngoals": P}; options: the keywords of _lib.JacoCostQuadOptions."""
+        nx, na = 2 * len(options["dofs"]), len(options["acts"])
+        shapes = {"lx": (R, T, nx), "lxx": (R, T, nx, nx), "lu": (R, T, na), "Vx": (R, nx), "Vxx": (R, nx, nx), "l": (R, T), "status": (R, T)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float32, device=self.device) for k in want}
+        opt = _lib.JacoCostQuadOptions(**options)
+        if R == 0:   # (no launch, as the entry for R == 0; empty tensors have no address to hand it, so what it would refuse is not seen here)
+            return res
+        out = _lib.JacoCostQuadOut(*[_ptr(res.get(k)) for k, _ in _lib.JacoCostQuadOut._fields_])
+        g = _lib.JacoCostQuadGoal(_ptr(goal.get("xgoal")), _ptr(goal.get("pgoal")), _ptr(goal.get("goal_idx")), int(goal.get("ngoals", 0)))
+        self._chk(self.L.jaco_cost_quad(self.h, _ref(opt), None if frame is None else _ref(frame), int(R), _ptr(qpos), _ptr(qvel), _ptr(ctrl), _ref(g), _ref(out),
+                                        self._stream()))
+        return res
+
+    def cost_quad(self, qpos, qvel, ctrl=None, dofs=(), acts=(), frame=None, x_goal=None, p_goal=None, goal_index=None, wx=None, wx_final=None,
+                  wu=None, wp=0.0, wp_final=0.0, want=("lx", "lxx", "lu", "Vx", "Vxx", "l", "status")):
+        """The quadratic expansion of rollout_cost()'s cost along R trajectories of T knots, in the layout lqr_backward reads -- iLQR's cost
+        expansion in one launch.  qpos [R, T, nq], qvel [R, T, nv]: the state AFTER each knot (x_1 .. x_T), ctrl [R, T, nu] (None: zeros):
+        the commanded row of each knot -- rollout_feedback's / rollout_cost's outputs as they are.  x = [qpos at the hinge dofs `dofs`,
+        qvel at them] (2 nd), u = ctrl at the words `acts`; goals x_goal [P, 2 nd] or [P, T, 2 nd], p_goal [P, 3] or [P, T, 3] (both the
+        same way), trajectory r taking goal goal_index[r] (None: goal r); weights wx / wx_final [2 nd], wu [len(acts)] (scalars broadcast),
+        wp / wp_final, all finite and >= 0, None: zeros.  The cost is rollout_cost()'s, re-indexed to lqr_backward's convention: l_t(x_t,
+        u_t) for t < T -- the start state is not costed, so row 0 of lx / lxx is zero -- and a terminal cost on x_T with the final weights.
+        The pose term is expanded in Gauss-Newton form on the positional Jacobian of `frame`'s origin (include/jaco_env.h).
+        Returns, for what `want` names: {"lx": [R, T, 2 nd], "lxx": [R, T, 2 nd, 2 nd], "lu": [R, T, na], "Vx": [R, 2 nd], "Vxx": [R, 2 nd,
+        2 nd], "l": [R, T]: knot k's own summand of rollout_cost()'s cost, "status": [R, T] int32: JACO_FLAG_NAN, or
+        _lib.JACO_ROLLOUT_BAD_INDEX where goal_index was out of range: that item wrote nothing else}; luu is diag(wu) and lux zero.  No
+        output depends on `want`.  One launch on the current stream, no synchronisation; the sim's state is not touched."""
+        what, dev = "cost_quad", self.device
+        known = ("lx", "lxx", "lu", "Vx", "Vxx", "l", "status")
+        want = tuple(want)
+        if not want or set(want) - set(known):
+            raise ValueError("%s: want %s names none or not only outputs (%s)" % (what, want, ", ".join(known)))
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()
+        qpos, qvel, ctrl = f32(qpos), f32(qvel), f32(ctrl)
+        lead = None
+        for name, t, width in (("qpos", qpos, self.nq), ("qvel", qvel, self.nv), ("ctrl", ctrl, self.nu)):
+            if t is None:
+                continue
+            if t.dim() != 3 or t.shape[2] != width or (lead is not None and tuple(t.shape[:2]) != lead):
+                raise ValueError("%s: %s has shape %s, not [%s, %d]" % (what, name, tuple(t.shape), "R, T" if lead is None else "%d, %d" % lead, width))
+            lead = tuple(t.shape[:2])
+        if lead is None:
+            raise ValueError("%s: one of qpos, qvel and ctrl is required" % what)
+        if (qpos is None) != (qvel is None):
+            raise ValueError("%s: qpos and qvel are given together or not at all" % what)
+        R, T = int(lead[0]), int(lead[1])
+        dofs, acts = tuple(int(d) for d in dofs), tuple(int(a) for a in acts)
+        nx = 2 * len(dofs)
+        idx = self._index(goal_index)
+        if idx is not None and idx.numel() != R:
+            raise ValueError("%s: %d trajectories but %d goal indices" % (what, R, idx.numel()))
+
+        def goal(t, width, name):
+            if t is None:
+                return None, None, None
+            t = f32(t)
+            if t.dim() == 2 and t.shape[1] == width:
+                return t.reshape(t.shape[0], 1, width), 0, int(t.shape[0])
+            if t.dim() == 3 and tuple(t.shape[1:]) == (T, width):
+                return t, 1, int(t.shape[0])
+            raise ValueError("%s: %s has shape %s, not [P, %d] or [P, %d, %d]" % (what, name, tuple(t.shape), width, T, width))
+        xg, per_x, Px = goal(x_goal, nx, "x_goal")
+        pg, per_p, Pp = goal(p_goal, 3, "p_goal")
+        if per_x is not None and per_p is not None and (per_x != per_p or Px != Pp):
+            raise ValueError("%s: x_goal %s and p_goal %s are not given the same way" % (what, tuple(xg.shape), tuple(pg.shape)))
+
+        def weights(w, width, name):
+            if w is None:
+                return ()
+            w = np.asarray(torch.as_tensor(w).detach().cpu().numpy() if torch.is_tensor(w) else w, np.float64)
+            if w.ndim == 0:
+                w = np.full(width, float(w))
+            if w.shape != (width,):
+                raise ValueError("%s: %s has shape %s, not [%d]" % (what, name, tuple(w.shape), width))
+            return w
+        options = dict(nknots=T, goal_per_knot=int(bool(per_x or per_p)), dofs=dofs, acts=acts, wx=weights(wx, nx, "wx"), wxT=weights(wx_final, nx, "wx_final"),
+                       wu=weights(wu, len(acts), "wu"), wp=float(wp), wpT=float(wp_final))
+        return self._cost_quad(qpos, qvel, ctrl, {"xgoal": xg, "pgoal": pg, "goal_idx": idx, "ngoals": Px if Px is not None else (Pp or 0)}, frame, R, T, want, **options)
+
     # ---- the iLQR / TVLQR backward pass (jaco_lqr: the whole recursion of every problem in one launch)
     def _lqr(self, opt, prob, out, n):
         """One jaco_lqr launch.  opt: the keywords of _lib.JacoLqrOptions; prob: {field of JacoLqrProblem: contiguous device tensor or

@@ -208,6 +208,7 @@ class BatchedMujocoConfig:
         self.n_arm = len(self.arm)
         self._names, self._frames = [], []
         self._cache, self._cache_key = None, None
+        self._word_index = {}   # (_words: index lists as device tensors)
         self._register(ee)
 
     def _register(self, name):
@@ -418,28 +419,47 @@ class BatchedMujocoConfig:
         u_applied into rollout_feedback(..., alphas=) as x_ref and u.  Two launches on this handle: one rollout_feedback for the full state
         and applied ctrl of every knot, one transition_fd over the B * T (state at the start of knot t, applied ctrl of knot t) pairs;
         steps: eps_qpos, eps_qvel, eps_ctrl, centered, groups.  The sim's state is not touched."""
+        p = self._closed_loop("linearize_rollout", u, K, x_ref, k, alpha, joints, ctrl, q, dq, hold)
+        return self._linearized(p, hold, steps)
+
+    def _words(self, words):
+        """A list of dofs, addresses or ctrl words as an index tensor on the sim's device, uploaded once per list: indexing with it
+        enqueues a gather / scatter, where a Python list is uploaded, synchronously, at every use."""
+        import torch
+        key = tuple(int(w) for w in words)
+        cache = self._word_index
+        if key not in cache:
+            cache[key] = torch.tensor(key, dtype=torch.long, device=self.sim.device)
+        return cache[key]
+
+    def _closed_loop(self, what, u, K, x_ref, k, alpha, joints, ctrl, q, dq, hold):
+        """What linearize_rollout, ilqr_expand and ilqr's last evaluation share: one rollout_feedback launch of every env's plan (alpha: one
+        step size per env) on the joints' dofs and motor words.  {"r": sim.rollout_feedback's dict, "Q" [B, T + 1, nq], "V" [B, T + 1, nv]:
+        the full state at the start of every knot and at the end, "x" [B, T + 1, 2 n], "u" [B, T, m]: the applied motor words, "dofs",
+        "qadr", "acts", "T"}."""
         import torch
         sim = self.sim
         B, dev, nu = sim.num_envs, sim.device, sim.nu
-        dofs, qadr, acts = self._joint_subset(joints, "linearize_rollout")
+        dofs, qadr, acts = self._joint_subset(joints, what)
         n, m = len(dofs), len(acts)
         f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
         u, K, x_ref, k = f32(u), f32(K), f32(x_ref), f32(k)
         if u.dim() != 3 or u.shape[0] != B or u.shape[2] != m:
-            raise ValueError("linearize_rollout: u has shape %s, not [%d, T, %d]" % (tuple(u.shape), B, m))
+            raise ValueError("%s: u has shape %s, not [%d, T, %d]" % (what, tuple(u.shape), B, m))
         T = int(u.shape[1])
         if alpha is not None and k is None:
-            raise ValueError("linearize_rollout: alpha needs k")
+            raise ValueError("%s: alpha needs k" % what)
+        at = self._words(acts)
         base = torch.zeros(B, nu, dtype=torch.float32, device=dev) if ctrl is None else f32(ctrl).reshape(B, nu)
         full = base[:, None, :].repeat(1, T, 1)
-        full[:, :, acts] = u
+        full[:, :, at] = u
         kff = gain = None
         if k is not None:
             kff = torch.zeros_like(full)
-            kff[:, :, acts] = k
+            kff[:, :, at] = k
         if K is not None:
             gain = torch.zeros(B, T, nu, 2 * n, dtype=torch.float32, device=dev)
-            gain[:, :, acts] = K
+            gain[:, :, at] = K
         if alpha is not None:
             alpha = f32(alpha).reshape(-1).expand(B).contiguous()
         qpos, qvel = self._spliced(q, dq)
@@ -447,9 +467,140 @@ class BatchedMujocoConfig:
         if qpos is None:
             qpos, qvel, _ = sim.get_state()
         Q, V = torch.cat([qpos[:, None], r["qpos"]], 1), torch.cat([qvel[:, None], r["qvel"]], 1)   # [B, T + 1, ..]: the state at the start of every knot, and the end
+        return dict(r=r, Q=Q, V=V, x=torch.cat([Q[..., self._words(qadr)], V[..., self._words(dofs)]], 2), u=r["ctrl"][..., at], dofs=dofs, qadr=qadr, acts=acts, T=T)
+
+    def _linearized(self, p, hold, steps):
+        """linearize_rollout's five results from _closed_loop's: the one transition_fd launch over the B * T (state at the start of knot t,
+        applied ctrl of knot t) pairs."""
+        import torch
+        sim, T, dofs, acts = self.sim, p["T"], p["dofs"], p["acts"]
+        r, Q, V = p["r"], p["Q"], p["V"]
         lin = sim.transition_fd(r["ctrl"], Q[:, :T].contiguous(), V[:, :T].contiguous(), dofs=dofs, acts=acts, hold=hold, want=("A", "B") if acts else ("A",), **steps)
-        Bm = lin["B"] if acts else torch.zeros(B, T, 2 * n, 0, dtype=torch.float32, device=dev)   # (no motor on the chosen joints: as linearize, no column)
-        return lin["A"], Bm, torch.cat([Q[..., qadr], V[..., dofs]], 2), r["ctrl"][..., acts], r["status"]
+        Bm = lin["B"] if acts else torch.zeros(sim.num_envs, T, 2 * len(dofs), 0, dtype=torch.float32, device=sim.device)   # (no motor on the chosen joints: as linearize, no column)
+        return lin["A"], Bm, p["x"], p["u"], r["status"]
+
+    def _cost_arguments(self, what, n, m, T, q_goal, dq_goal, ee_goal, w_q, w_dq, w_ee, w_u, w_q_final, w_dq_final, w_ee_final):
+        """The goals and weights of rollout_cost, ilqr_expand and ilqr, checked and put into the sim tier's form: {"x_goal": [B, 2 n] or
+        [B, T, 2 n] or None (no state weight), "p_goal", "wx", "wxT" [2 n], "wu" [m] fp64 arrays, "wp", "wpT"}."""
+        import torch
+        B, dev = self.sim.num_envs, self.sim.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev)
+        # the goals: x_goal = [q_goal, dq_goal], per env or per env and knot
+        goals = {name: f32(t) for name, t in (("q_goal", q_goal), ("dq_goal", dq_goal), ("ee_goal", ee_goal)) if t is not None}
+        for name, t in goals.items():
+            width = 3 if name == "ee_goal" else n
+            if tuple(t.shape) not in ((B, width), (B, T, width)):
+                raise ValueError("%s: %s has shape %s, not [%d, %d] or [%d, %d, %d]" % (what, name, tuple(t.shape), B, width, B, T, width))
+        if len({t.dim() for t in goals.values()}) > 1:
+            raise ValueError("%s: the goals (%s) are given all per env or all per env and knot" % (what, ", ".join(goals)))
+        x_goal = None
+        if "q_goal" in goals or "dq_goal" in goals:
+            like = goals.get("q_goal", goals.get("dq_goal"))
+            x_goal = torch.cat([goals.get("q_goal", torch.zeros_like(like)), goals.get("dq_goal", torch.zeros_like(like))], -1)
+
+        def vec(w, width, name):
+            w = np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, np.float64)
+            if w.ndim == 0:
+                return np.full(width, float(w))
+            if w.shape != (width,):
+                raise ValueError("%s: %s has shape %s, not [%d]" % (what, name, tuple(w.shape), width))
+            return w
+        on = lambda name, w: vec(w, n, name) * (name.split("_")[1] + "_goal" in goals)   # (a goal that is not given weighs nothing)
+        last = lambda w, running: running if w is None else w
+        wx = np.concatenate([on("w_q", w_q), on("w_dq", w_dq)])
+        wxT = np.concatenate([on("w_q_final", last(w_q_final, w_q)), on("w_dq_final", last(w_dq_final, w_dq))])
+        pose = "ee_goal" in goals
+        return dict(x_goal=x_goal if wx.any() or wxT.any() else None, p_goal=goals.get("ee_goal"), wx=wx, wxT=wxT, wu=vec(w_u, m, "w_u"),
+                    wp=float(w_ee) * pose, wpT=float(last(w_ee_final, w_ee)) * pose)
+
+    def ilqr_expand(self, u, K=None, x_ref=None, k=None, alpha=None, joints=None, ctrl=None, q=None, dq=None, hold=1, q_goal=None, dq_goal=None,
+                    ee_goal=None, w_q=0.0, w_dq=0.0, w_ee=0.0, w_u=0.0, w_q_final=None, w_dq_final=None, w_ee_final=None, **steps):
+        """Everything iLQR's backward pass reads, about the trajectory of rollout_feedback's plan: linearize_rollout's five results and the
+        quadratic expansion of rollout_cost's cost (its goals, weights and conventions) along that trajectory.  {"A" [B, T, 2 n, 2 n], "B"
+        [B, T, 2 n, m], "x" [B, T + 1, 2 n], "u" [B, T, m], "status" [B]: linearize_rollout's, bit for bit;  "lx" [B, T, 2 n], "lxx" [B, T,
+        2 n, 2 n], "lu" [B, T, m], "luu" [m, m] = diag(w_u), "Vx" [B, 2 n], "Vxx" [B, 2 n, 2 n]: ilqr_backward's arguments as they are (the
+        start state is not costed: row 0 of lx / lxx is zero; the pose term in Gauss-Newton form);  "l" [B, T]: knot t's own summand of
+        rollout_cost's cost}.  Three launches on this handle: rollout_feedback, transition_fd, cost_quad (BatchedMujoco.cost_quad); steps:
+        linearize_rollout's.  The sim's state is not touched."""
+        import torch
+        p = self._closed_loop("ilqr_expand", u, K, x_ref, k, alpha, joints, ctrl, q, dq, hold)
+        n, m, T = len(p["dofs"]), len(p["acts"]), p["T"]
+        c = self._cost_arguments("ilqr_expand", n, m, T, q_goal, dq_goal, ee_goal, w_q, w_dq, w_ee, w_u, w_q_final, w_dq_final, w_ee_final)
+        A, Bm, x, ua, status = self._linearized(p, hold, steps)
+        r = p["r"]
+        e = self.sim.cost_quad(r["qpos"], r["qvel"], r["ctrl"], dofs=p["dofs"], acts=p["acts"], frame=self._frames[0], x_goal=c["x_goal"], p_goal=c["p_goal"],
+                               wx=c["wx"], wx_final=c["wxT"], wu=c["wu"], wp=c["wp"], wp_final=c["wpT"],
+                               want=("lx", "lxx", "Vx", "Vxx", "l") + (("lu",) if m else ()))
+        if not m:
+            e["lu"] = torch.zeros(x.shape[0], T, 0, dtype=torch.float32, device=x.device)
+        return dict(A=A, B=Bm, x=x, u=ua, status=status, luu=torch.diag(self._filled(c["wu"])), **e)
+
+    def _filled(self, values):
+        """The numbers `values` as an fp32 vector on the sim's device, built there by fills: nothing is uploaded, so nothing synchronises."""
+        import torch
+        dev = self.sim.device
+        return torch.cat([torch.full((1,), float(x), dtype=torch.float32, device=dev) for x in values]) if len(values) else torch.zeros(0, dtype=torch.float32, device=dev)
+
+    ILQR_ALPHAS = (0.0,) + tuple(2.0 ** -i for i in range(7))
+
+    def ilqr(self, u0, iterations, alphas=ILQR_ALPHAS, mu0=1e-3, mu_up=10.0, mu_down=0.1, mu_max=1e6, joints=None, ctrl=None, q=None, dq=None, hold=1,
+             q_goal=None, dq_goal=None, ee_goal=None, w_q=0.0, w_dq=0.0, w_ee=0.0, w_u=0.0, w_q_final=None, w_dq_final=None, w_ee_final=None):
+        """`iterations` iLQR iterations on this handle from the plan u0 [B, T, m], on rollout_cost's cost (its goals and weights) and the
+        joints and motor words linearize uses; every env is its own problem with its own regularisation and step.  One iteration is five
+        launches: ilqr_expand (the current trajectory, A, B and the cost's expansion), ilqr_backward with mu [B] on Quu's diagonal, and
+        rollout_cost over the ladder `alphas` of step sizes, which must hold 0: the current plan's true cost comes from the same kernel
+        in the same call.  Per env the step is the argmin over the ladder's costs that are finite and carry no flag but
+        JACO_FLAG_SOLVER_MAXITER; a strict improvement on the alpha = 0 entry accepts it and multiplies mu by mu_down, anything else (a
+        solve with JACO_LQR_NOT_PD too) keeps alpha = 0 and multiplies mu by mu_up (at most mu_max).  The next ilqr_expand re-simulates
+        the chosen closed loop (u, K, x_ref, k, alpha [B]) and its applied motor words become the plan, so the line search materialises
+        no trajectory; after the last iteration one more rollout_feedback launch does that for the result: 5 iterations + 1 launches.
+        All selection happens on the device: nothing is read back, no synchronisation.
+        {"u" [B, T, m]: the plan, "x" [B, T + 1, 2 n]: its trajectory, "K" [B, T, m, 2 n], "k" [B, T, m]: the last backward pass's, about
+        the plan before the last step, "cost" [iterations + 1, B]: cost[i] is the alpha = 0 entry of iteration i's ladder, the cost of the
+        plan that iteration started from, and cost[iterations] the chosen entry of the last ladder; a rollout fed its own applied ctrl
+        reproduces itself bit for bit, so cost[i + 1] is also the chosen entry of iteration i's ladder and cost never rises, bit for bit,
+        "accepted" [iterations, B] bool, "mu" [B], "status" [B] int32: the OR of the rollouts' status words (JACO_FLAG_NAN /
+        JACO_FLAG_SOLVER_MAXITER) along the way to the result -- every ilqr_expand's rollout, every chosen ladder entry and the last
+        rollout_feedback.  The backward pass's words are not in it: a solve with JACO_LQR_NOT_PD is an ordinary rejection and shows in
+        "accepted" and "mu"}."""
+        import torch
+        sim = self.sim
+        B, dev = sim.num_envs, sim.device
+        ladder = [float(a) for a in alphas]
+        if 0.0 not in ladder:
+            raise ValueError("ilqr: the step sizes %s do not hold 0, the current plan" % (ladder,))
+        if iterations < 1:
+            raise ValueError("ilqr: %d iterations" % iterations)
+        zero = ladder.index(0.0)
+        alphas = self._filled(ladder)
+        cost_args = dict(q_goal=q_goal, dq_goal=dq_goal, ee_goal=ee_goal, w_q=w_q, w_dq=w_dq, w_ee=w_ee, w_u=w_u, w_q_final=w_q_final, w_dq_final=w_dq_final,
+                         w_ee_final=w_ee_final)
+        where = dict(joints=joints, ctrl=ctrl, q=q, dq=dq, hold=hold)
+        mu = torch.full((B,), float(mu0), dtype=torch.float32, device=dev)
+        cost = torch.zeros(iterations + 1, B, dtype=torch.float32, device=dev)
+        accepted = torch.zeros(iterations, B, dtype=torch.bool, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        u, K, x_ref, k, step = torch.as_tensor(u0, dtype=torch.float32, device=dev), None, None, None, None
+        for i in range(iterations):
+            e = self.ilqr_expand(u, K=K, x_ref=x_ref, k=k, alpha=step, **where, **cost_args)
+            u, x_ref = e["u"], e["x"][:, :-1].contiguous()
+            K, k, _, solved = self.ilqr_backward(e["A"], e["B"], e["lxx"], e["luu"], lx=e["lx"], lu=e["lu"], Vxx=e["Vxx"], Vx=e["Vx"], mu=mu, joints=joints)
+            pd = solved == 0
+            # (a solve that stopped at a knot leaves the rows below it unwritten: such an env keeps its plan, with zero gains)
+            K, k = torch.where(pd[:, None, None, None], K, torch.zeros_like(K)), torch.where(pd[:, None, None], k, torch.zeros_like(k))
+            c = self.rollout_cost(u, K=K, x_ref=x_ref, k=k, alphas=alphas, **where, **cost_args)
+            usable = torch.isfinite(c["cost"]) & ((c["status"] & ~_lib.JACO_FLAG_SOLVER_MAXITER) == 0)
+            ranked = torch.where(usable, c["cost"], torch.full_like(c["cost"], float("inf")))
+            best = ranked.argmin(1, keepdim=True)
+            here = c["cost"][:, zero]
+            ok = pd & (ranked.gather(1, best)[:, 0] < here)
+            chosen = torch.where(ok[:, None], best, torch.full_like(best, zero))
+            step = alphas[chosen[:, 0]]
+            mu = torch.where(ok, mu * float(mu_down), (mu * float(mu_up)).clamp(max=float(mu_max)))
+            cost[i], cost[i + 1], accepted[i] = here, c["cost"].gather(1, chosen)[:, 0], ok
+            status = status | e["status"] | c["status"].gather(1, chosen)[:, 0]
+        p = self._closed_loop("ilqr", u, K, x_ref, k, step, joints, ctrl, q, dq, hold)
+        return dict(u=p["u"], x=p["x"], K=K, k=k, cost=cost, accepted=accepted, mu=mu, status=status | p["r"]["status"])
 
     def rollout_cost(self, u, noise=None, K=None, x_ref=None, k=None, alphas=None, joints=None, q_goal=None, dq_goal=None, ee_goal=None, w_q=0.0,
                      w_dq=0.0, w_ee=0.0, w_u=0.0, w_q_final=None, w_dq_final=None, w_ee_final=None, ctrl=None, hold=1, q=None, dq=None,
@@ -492,14 +643,15 @@ class BatchedMujocoConfig:
             raise ValueError("rollout_cost: noise has shape %s, not [%d, S, %d, %d]" % (tuple(noise.shape), B, T, m))
         base = torch.zeros(B, nu, dtype=torch.float32, device=dev) if ctrl is None else f32(ctrl).reshape(B, nu)
         full = base[:, None, :].repeat(1, T, 1)
-        full[:, :, acts] = u
+        at = self._words(acts)
+        full[:, :, at] = u
         kff = gain = None
         if k is not None:
             kff = torch.zeros_like(full)
-            kff[:, :, acts] = k
+            kff[:, :, at] = k
         if K is not None:
             gain = torch.zeros(B, T, nu, 2 * n, dtype=torch.float32, device=dev)
-            gain[:, :, acts] = K
+            gain[:, :, at] = K
         index = alpha = eps = None
         S = 1
         if alphas is not None:
@@ -509,42 +661,17 @@ class BatchedMujocoConfig:
         if noise is not None:
             S = int(noise.shape[1])
             eps = torch.zeros(B * S, T, nu, dtype=torch.float32, device=dev)
-            eps[:, :, acts] = noise.reshape(B * S, T, m)
+            eps[:, :, at] = noise.reshape(B * S, T, m)
         if alphas is not None or noise is not None:
             index = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(S)
-        # the goals: x_goal = [q_goal, dq_goal], per env or per env and knot
-        goals = {name: f32(t) for name, t in (("q_goal", q_goal), ("dq_goal", dq_goal), ("ee_goal", ee_goal)) if t is not None}
-        for name, t in goals.items():
-            width = 3 if name == "ee_goal" else n
-            if tuple(t.shape) not in ((B, width), (B, T, width)):
-                raise ValueError("rollout_cost: %s has shape %s, not [%d, %d] or [%d, %d, %d]" % (name, tuple(t.shape), B, width, B, T, width))
-        if len({t.dim() for t in goals.values()}) > 1:
-            raise ValueError("rollout_cost: the goals (%s) are given all per env or all per env and knot" % ", ".join(goals))
-        x_goal = None
-        if "q_goal" in goals or "dq_goal" in goals:
-            like = goals.get("q_goal", goals.get("dq_goal"))
-            x_goal = torch.cat([goals.get("q_goal", torch.zeros_like(like)), goals.get("dq_goal", torch.zeros_like(like))], -1)
-
-        def vec(w, width, name):
-            w = np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, np.float64)
-            if w.ndim == 0:
-                return np.full(width, float(w))
-            if w.shape != (width,):
-                raise ValueError("rollout_cost: %s has shape %s, not [%d]" % (name, tuple(w.shape), width))
-            return w
-        on = lambda name, w: vec(w, n, name) * (name.split("_")[1] + "_goal" in goals)   # (a goal that is not given weighs nothing)
-        last = lambda w, running: running if w is None else w
-        wx = np.concatenate([on("w_q", w_q), on("w_dq", w_dq)])
-        wxT = np.concatenate([on("w_q_final", last(w_q_final, w_q)), on("w_dq_final", last(w_dq_final, w_dq))])
+        c = self._cost_arguments("rollout_cost", n, m, T, q_goal, dq_goal, ee_goal, w_q, w_dq, w_ee, w_u, w_q_final, w_dq_final, w_ee_final)
         wu = np.zeros(nu)
-        wu[acts] = vec(w_u, m, "w_u")
-        pose = "ee_goal" in goals
+        wu[acts] = c["wu"]
         qpos, qvel = self._spliced(q, dq)
         want = ("cost", "terms", "status") + (("qpos", "qvel", "xpos", "xmat", "ctrl") if trajectories else ())
         r = self.sim.rollout_cost(full, qpos, qvel, noise=eps, gain=gain, x_ref=x_ref, dofs=dofs, feedforward=kff, alpha=alpha, plan_index=index,
-                                  state_index=index, hold=hold, frame=self._frames[0], x_goal=x_goal if wx.any() or wxT.any() else None,
-                                  p_goal=goals.get("ee_goal"), wx=wx, wx_final=wxT, wu=wu, wp=float(w_ee) * pose,
-                                  wp_final=float(last(w_ee_final, w_ee)) * pose, want=want)
+                                  state_index=index, hold=hold, frame=self._frames[0], x_goal=c["x_goal"], p_goal=c["p_goal"], wx=c["wx"], wx_final=c["wxT"], wu=wu,
+                                  wp=c["wp"], wp_final=c["wpT"], want=want)
         out = {"cost": r["cost"].reshape(B, S), "terms": r["terms"].reshape(B, S, 3), "status": r["status"].reshape(B, S)}
         if trajectories:
             tr = {"q": r["qpos"][..., qadr], "dq": r["qvel"][..., dofs], "ee_pos": r["xpos"], "ee_mat": r["xmat"], "u": r["ctrl"][..., acts]}
